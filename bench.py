@@ -4,18 +4,21 @@
 Metric (BASELINE.json): decoded values/sec + achieved HBM GB/s, Zipf uint64 column, 1/2/4/8 GPU.
 Workload at N=1 (config C2): 100 M-row uint64 column, values Zipf(n = 2^32-1, s = 1.0) drawn with the
 reference's rejection-inversion sampler on mt19937 (seed 42 + rank), cut into segments the way the reference's
-Appender does (2048 / 32767 / ... rows), encoded on the device (analyze + plan + pack, timed separately) and
+Appender does (2048 / 32767 / ... rows), encoded on the device (analyze + plan + pack; --full times it) and
 then fully scanned.  One STEP = one full scan: adac_unpack over every segment of the rank's column (the
 whole-column form of SuccinctScanPartial, src/storage/compression/succinct.cpp:123-144), inputs and outputs
 resident in HBM.  N > 1: one process per GPU; the workload is ONE global column of --total-rows rows (default
 --rows x N: weak scaling; config C4 is `--gpus 8 --total-rows 1000000000`) whose Appender segment list is
 partitioned by segment id into N contiguous ranges (sharding.column_shard): rank k generates, encodes and scans
 only the segments of its range in its own per-GPU pool, no data-path collective; value = total rows decoded by all
-ranks / max-over-ranks time, and rank 0 checks the sum of the per-rank checksums against the column's.
+ranks / max-over-ranks time, and (--full) rank 0 checks the sum of the per-rank checksums against the column's.
 
-One JSON line on rank 0.  Extra objects: "roofline" (dominant kernel k_unpack, algorithmic bytes / HIP-event
-launch time vs the 8 TB/s HBM peak), "cpu_baseline" (the oracle's port of the reference scan loop on the host
-cores, same packed words), "encode", "fused_scan", "sweep".
+One JSON line on rank 0, with "roofline" (dominant kernel k_unpack, algorithmic bytes / HIP-event launch time vs the
+8 TB/s HBM peak).  A plain run does only what that line needs: generate, encode once, W warm-up scans, K timed scans.
+--full adds the secondary measurements and checks: "parity" (full-size round trip + checksums), "encode",
+"fused_scan", "roofline_read", "point_fetch", "device_copy_GBps", "cpu_baseline" (the oracle's port of the reference
+scan loop on the host cores, same packed words) and "sweep".  --dump-outputs DIR writes a fixed sample of what the
+last timed scan decoded (see dump_outputs).
 """
 import argparse
 import importlib
@@ -32,6 +35,7 @@ if ROOT not in sys.path:
 
 PKG = "duckdb-adaptive-compression_amd"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s spec, ~6.3 TB/s achievable copy)
+DUMP_ROWS = 1 << 22    # decoded rows --dump-outputs writes, all ranks together (float64: 32 MiB)
 
 
 def kernel_source_sha256():
@@ -145,6 +149,21 @@ def time_launches(ctx, fn, reps, rounds=1):
             fn()
         out.append(ctx.timer_stop() / reps)
     return float(np.median(out))
+
+
+def dump_outputs(out_dir, torch, col, rank, world):
+    """--dump-outputs DIR: what the last timed step computed, the decoded column adac_unpack leaves in HBM, so that two
+    builds can be compared output for output.  A fixed sample: DUMP_ROWS // world rows of this rank's shard drawn with
+    seed 1234 + rank, in row order, as float64 (exact: the workload's values are below 2^53).  DIR/decoded.npy on one
+    GPU, DIR/decoded_rank<k>.npy from every rank on several."""
+    k = min(col.n, DUMP_ROWS // world)
+    rows = np.sort(np.random.default_rng(1234 + rank).integers(0, col.n, size=k, dtype=np.int64))
+    got = col.d_out[:col.n].index_select(0, torch.from_numpy(rows).to(col.d_out.device)).cpu().numpy().view(col.dtype)
+    if k and int(got.max()) >= 2 ** 53:
+        raise RuntimeError("--dump-outputs: decoded values of 2^53 or more do not fit float64 exactly")
+    os.makedirs(out_dir, exist_ok=True)
+    name = "decoded" if world == 1 else "decoded_rank%d" % rank
+    np.save(os.path.join(out_dir, name + ".npy"), got.astype(np.float64))
 
 
 def cpu_baseline(orc, col, vals, seconds, threads, all_threads):
@@ -325,8 +344,14 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--cpu-threads", type=int, default=16, help="host threads of the CPU baseline (the box's CPU share per GPU)")
     ap.add_argument("--sweep-rows", type=int, default=200_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements and checks (full-size parity, encode timings, fused scans, "
+                         "point fetch, device copy rate, CPU baseline, sweep); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the last step's decoded column to "
+                         "DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: leave out the sweep")
     ap.add_argument("--backend", default=None)
     ap.add_argument("--plumbing-only", action="store_true")
     ap.add_argument("--single-device-rehearsal", action="store_true",
@@ -373,43 +398,45 @@ def main():
         % (rank, seg_lo, seg_hi, row_lo, row_hi, total_rows_cfg, time.perf_counter() - t0))
     col = DeviceColumn(adac, torch, ctx, vals, counts, dtype)
 
-    # ---- encode (timed separately; not part of the step) ----
+    # ---- encode (not part of the step; --full times it separately) ----
     col.encode(adac.RULE_APPEND)
     ctx.sync()
-    enc_ms = time_launches(ctx, lambda: col.encode(adac.RULE_APPEND), 10)
-    # the same kernel with first-come arena placement (offsets in order of completion instead of segment order)
-    adac.set_tuning("encode_placement", 1)
-    col.encode(adac.RULE_APPEND)
-    ctx.sync()
-    enc_fc_ms = time_launches(ctx, lambda: col.encode(adac.RULE_APPEND), 10)
-    adac.set_tuning("encode_placement", 0)
-    col.encode(adac.RULE_APPEND)
-    ctx.sync()
-    # A2 alone: the append path carries min/max (succinct.cpp:286-299), so Compact() is width decision + one pack pass
+    if args.full:
+        enc_ms = time_launches(ctx, lambda: col.encode(adac.RULE_APPEND), 10)
+        # the same kernel with first-come arena placement (offsets in order of completion instead of segment order)
+        adac.set_tuning("encode_placement", 1)
+        col.encode(adac.RULE_APPEND)
+        ctx.sync()
+        enc_fc_ms = time_launches(ctx, lambda: col.encode(adac.RULE_APPEND), 10)
+        adac.set_tuning("encode_placement", 0)
+        col.encode(adac.RULE_APPEND)
+        ctx.sync()
+        # A2 alone: the append path carries min/max (succinct.cpp:286-299): Compact() = width decision + one pack pass
 
-    def plan_pack():
-        col.layout.plan(adac.RULE_APPEND, False)
-        col.layout.pack(col.d_vals, col.d_words)
-    pack_ms = time_launches(ctx, plan_pack, 10)
+        def plan_pack():
+            col.layout.plan(adac.RULE_APPEND, False)
+            col.layout.pack(col.d_vals, col.d_words)
+        pack_ms = time_launches(ctx, plan_pack, 10)
     descs = col.fetch_descs()
     rd, wr, meta = algorithmic_bytes(descs, dtype.itemsize)
     wh = {}
     for w, c in zip(descs["width"].tolist(), descs["count"].tolist()):
         wh[w] = wh.get(w, 0) + c
 
-    # ---- correctness at full size (not timed): round trip + checksum ----
-    col.unpack()
-    ctx.sync()
-    roundtrip_ok = col.verify_roundtrip()
-    d_sums = torch.zeros(len(counts), dtype=torch.int64, device=col.d_vals.device)
-    torch.cuda.synchronize()
-    col.layout.scan_sum(col.d_words, d_sums)
-    ctx.sync()
-    dev_checksum = int(d_sums.sum().item()) & (2 ** 64 - 1)   # sum mod 2^64 of the rank's per-segment device SUMs
-    host_checksum = int(vals.sum(dtype=np.uint64))
-    checksum_ok = dev_checksum == host_checksum
-    if not (roundtrip_ok and checksum_ok):
-        raise RuntimeError("parity failure at full size: roundtrip=%s checksum=%s" % (roundtrip_ok, checksum_ok))
+    if args.full:
+        # ---- correctness at full size (not timed): round trip + checksum ----
+        col.unpack()
+        ctx.sync()
+        roundtrip_ok = col.verify_roundtrip()
+        d_sums = torch.zeros(len(counts), dtype=torch.int64, device=col.d_vals.device)
+        torch.cuda.synchronize()
+        col.layout.scan_sum(col.d_words, d_sums)
+        ctx.sync()
+        dev_checksum = int(d_sums.sum().item()) & (2 ** 64 - 1)   # sum mod 2^64 of the rank's per-segment device SUMs
+        host_checksum = int(vals.sum(dtype=np.uint64))
+        checksum_ok = dev_checksum == host_checksum
+        if not (roundtrip_ok and checksum_ok):
+            raise RuntimeError("parity failure at full size: roundtrip=%s checksum=%s" % (roundtrip_ok, checksum_ok))
 
     # ---- the timed region: W warm-up scans, then exactly K scans between barriers ----
     for _ in range(args.warmup):
@@ -426,15 +453,20 @@ def main():
     torch.cuda.synchronize()
     comm.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, col, rank, world)
     elapsed = comm.max(elapsed)
     total_rows = comm.sum(my_rows)
-    # checksum of checksums: the ranks' device SUMs add up to the whole column's (each rank checked its own above)
-    global_dev_checksum = comm.sum_u64(dev_checksum)
-    global_host_checksum = comm.sum_u64(host_checksum)
     total_segments = comm.sum(len(counts))
-    if total_rows != total_rows_cfg or global_dev_checksum != global_host_checksum:
-        raise RuntimeError("parity failure across ranks: rows %d/%d checksum %x/%x"
-                           % (total_rows, total_rows_cfg, global_dev_checksum, global_host_checksum))
+    if total_rows != total_rows_cfg:
+        raise RuntimeError("rows across ranks: %d of %d" % (total_rows, total_rows_cfg))
+    if args.full:
+        # checksum of checksums: the ranks' device SUMs add up to the whole column's (each rank checked its own above)
+        global_dev_checksum = comm.sum_u64(dev_checksum)
+        global_host_checksum = comm.sum_u64(host_checksum)
+        if global_dev_checksum != global_host_checksum:
+            raise RuntimeError("parity failure across ranks: checksum %x/%x"
+                               % (global_dev_checksum, global_host_checksum))
     value = total_rows * args.steps / elapsed
     launch_ms = ev_ms / args.steps
     launch_ms_max = comm.max(launch_ms)
@@ -459,7 +491,7 @@ def main():
         "data": "synthetic",
         "config": {
             "workload": "%s: ONE %d-row uint64 Zipf(s=%.1f, n=%d) column (mt19937 seed 42 + 2^20-row block id), "
-                        "Appender segment layout, full scan (decode to HBM); encode timed separately"
+                        "Appender segment layout, full scan (decode to HBM); encode outside the step"
                         % ("C2" if world == 1 and total_rows_cfg == 100_000_000 else
                            "C4" if total_rows_cfg == 1_000_000_000 else "C2-shaped", total_rows_cfg, args.skew,
                            args.domain),
@@ -475,12 +507,14 @@ def main():
         "per_gpu_values_per_s": {"min": min(r["values_per_s"] for r in per_rank),
                                  "max": max(r["values_per_s"] for r in per_rank)},
         "achieved_HBM_GBps_aggregate": comm.sum(rd + wr + meta) / (launch_ms_max * 1e-3) / 1e9,
-        "parity": {"roundtrip_full_size": roundtrip_ok, "checksum_full_size": checksum_ok,
-                   "checksum_of_checksums": "%016x" % global_dev_checksum,
-                   "oracle_pin": "unpinned: the reference holds no tests, golden vectors or fixtures for this path and "
-                                 "its SDSL library is absent; the oracle is anchored by the known answers recorded in "
-                                 "SURVEY.md §8c (tests/golden/survey_known_answers.json)"},
     }
+    if args.full:
+        result["parity"] = {
+            "roundtrip_full_size": roundtrip_ok, "checksum_full_size": checksum_ok,
+            "checksum_of_checksums": "%016x" % global_dev_checksum,
+            "oracle_pin": "unpinned: the reference holds no tests, golden vectors or fixtures for this path and "
+                          "its SDSL library is absent; the oracle is anchored by the known answers recorded in "
+                          "SURVEY.md §8c (tests/golden/survey_known_answers.json)"}
 
     # roofline of the dominant kernel (k_unpack<u64>) on this rank
     ach = (rd + wr + meta) / (launch_ms * 1e-3) / 1e9
@@ -493,26 +527,29 @@ def main():
         "launch_ms": launch_ms,
         "read_GBps": rd / (launch_ms * 1e-3) / 1e9, "read_frac_of_peak": rd / (launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
     }
-    result["encode"] = {
-        "values_per_s": my_rows / (enc_ms * 1e-3), "ms": enc_ms,
-        "algorithmic_GBps": (wr + rd) / (enc_ms * 1e-3) / 1e9,
-        "note": "adac_encode: single-pass kernel (k_encode_1p, persistent: a segment stays in the registers of one "
-                "workgroup across min/max, width, arena placement and pack; the raw column is read once: "
-                "algorithmic bytes = raw + packed) for 4- and 8-byte types; BitCompressFromUncompressed's two passes "
-                "(column_segment.cpp:385-456) in one; arena offsets = exclusive prefix in segment order (deterministic)",
-        "first_come_placement": {
-            "ms": enc_fc_ms, "values_per_s": my_rows / (enc_fc_ms * 1e-3),
-            "algorithmic_GBps": (wr + rd) / (enc_fc_ms * 1e-3) / 1e9,
-            "note": "adac_set_tuning(\"encode_placement\", 1): a segment takes its arena space from a cursor when its "
-                    "width is known, no ordered look-back; same words, widths and mins, offsets differ run to run"},
-        "compact_after_append": {
-            "ms": pack_ms, "values_per_s": my_rows / (pack_ms * 1e-3),
-            "algorithmic_GBps": (wr + rd) / (pack_ms * 1e-3) / 1e9,
-            "note": "plan + pack with the min/max the append path carries: BitCompressFromSuccinct "
-                    "(column_segment.cpp:348-383)"},
-    }
+    if args.full:
+        result["encode"] = {
+            "values_per_s": my_rows / (enc_ms * 1e-3), "ms": enc_ms,
+            "algorithmic_GBps": (wr + rd) / (enc_ms * 1e-3) / 1e9,
+            "note": "adac_encode: single-pass kernel (k_encode_1p, persistent: a segment stays in the registers of "
+                    "one workgroup across min/max, width, arena placement and pack; the raw column is read once: "
+                    "algorithmic bytes = raw + packed) for 4- and 8-byte types; BitCompressFromUncompressed's two "
+                    "passes (column_segment.cpp:385-456) in one; arena offsets = exclusive prefix in segment order "
+                    "(deterministic)",
+            "first_come_placement": {
+                "ms": enc_fc_ms, "values_per_s": my_rows / (enc_fc_ms * 1e-3),
+                "algorithmic_GBps": (wr + rd) / (enc_fc_ms * 1e-3) / 1e9,
+                "note": "adac_set_tuning(\"encode_placement\", 1): a segment takes its arena space from a cursor "
+                        "when its width is known, no ordered look-back; same words, widths and mins, offsets differ "
+                        "run to run"},
+            "compact_after_append": {
+                "ms": pack_ms, "values_per_s": my_rows / (pack_ms * 1e-3),
+                "algorithmic_GBps": (wr + rd) / (pack_ms * 1e-3) / 1e9,
+                "note": "plan + pack with the min/max the append path carries: BitCompressFromSuccinct "
+                        "(column_segment.cpp:348-383)"},
+        }
 
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         # fused scan+sum (no materialisation): the read-roofline variant
         ms_sum = time_launches(ctx, lambda: col.layout.scan_sum(col.d_words, d_sums), args.steps)
         result["fused_scan"] = {

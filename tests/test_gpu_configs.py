@@ -3,7 +3,7 @@ properties (round trips, checksums, known end-to-end sizes) because the oracle w
   C1  10 M uint32 sequential + 10 000 Zipf(1.0) point look-ups   (benchmark/micro/succinct/zipf_distribution.cpp)
   C3  TPC-H SF10 lineitem integer columns (l_orderkey / l_partkey / l_quantity as INTEGER)
   C5  adaptive hot/cold re-compaction under a Zipf segment-access trace, s in {0.5, 1.0, 2.0}
-(C2 and C4 are bench.py's workload: its full-size round trip + checksum run inside every bench invocation.)"""
+(C2 and C4 are bench.py's workload: its full-size round trip + checksum run inside every `bench.py --full`.)"""
 import importlib
 
 import numpy as np

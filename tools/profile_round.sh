@@ -12,13 +12,13 @@ PREV=${2:-$(ls -t profiles/r*_bench.json 2>/dev/null | grep -v "profiles/${1:-r0
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
+python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
 echo "bench done"
-SHORT="--steps 20 --warmup 3 --no-sweep --no-cpu-baseline"
+SHORT="--full --steps 20 --warmup 3 --no-sweep --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats -d "$OUT/trace" --output-format csv -- python3 bench.py $SHORT > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.err" || exit 1
 echo "trace done"
-rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-sweep --no-cpu-baseline > /dev/null 2> "$OUT/pmc_fetch.err" || exit 1
-rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-sweep --no-cpu-baseline > /dev/null 2> "$OUT/pmc_write.err" || exit 1
+rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" --output-format csv -- python3 bench.py --full --steps 5 --warmup 1 --no-sweep --no-cpu-baseline > /dev/null 2> "$OUT/pmc_fetch.err" || exit 1
+rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" --output-format csv -- python3 bench.py --full --steps 5 --warmup 1 --no-sweep --no-cpu-baseline > /dev/null 2> "$OUT/pmc_write.err" || exit 1
 echo "pmc done"
 python3 profiles/summarize.py "$TAG" "$OUT/trace" "$OUT/pmc_fetch" "$OUT/pmc_write" 100000000 > "$OUT/summary.json" || exit 1
 cp "$OUT/bench.json" "profiles/${TAG}_bench.json"
