@@ -44,6 +44,22 @@ def oracle_encode(orc, seg_vals, rule, padded, validity=None, val_offs=None):
     return out
 
 
+def check_placement(adac, descs, max_arena_words):
+    """Footprints of a first-come placement (the single-pass encode, encode_placement = 1): 16-word aligned, disjoint
+    and inside the layout's arena (ordered placement is the prefix case of this)."""
+    foot = ((descs["count"].astype(np.uint64) * descs["width"] + 64) >> np.uint64(6)) + np.uint64(15) & ~np.uint64(15)
+    order = np.argsort(descs["word_off"], kind="stable")
+    ends = descs["word_off"][order] + foot[order]
+    assert np.all(descs["word_off"] % 16 == 0), "word_off not 16-word aligned"
+    assert np.all(ends[:-1] <= descs["word_off"][order][1:]), "footprints overlap"
+    assert len(ends) == 0 or int(ends.max()) <= max_arena_words, "footprint past the arena"
+
+
+# offsets run_encode_decode accepts: False = arena order is segment order (prefix offsets); True = any placement that
+# check_placement accepts (tools/soak_fuzz.py sets it when it soaks with encode_placement = 1)
+FIRST_COME = False
+
+
 def wide_sum(v):
     """What adac_scan_sum reports: the values widened to 64 bits by T's signedness, summed mod 2^64."""
     wide = np.int64 if v.dtype.kind == "i" else np.uint64
@@ -74,6 +90,8 @@ def run_encode_decode(adac, orc, ctx, dtype, counts, seg_vals, rule=0, padded=Fa
             assert (int(mm[s, 0]), int(mm[s, 1])) == (mn, mx), "min/max of segment %d" % s
         assert int(d["width"]) == w, "width of segment %d" % s
         assert bool(d["flags"] & adac.SEG_PACKED) == packed
+        if FIRST_COME:
+            woff = int(d["word_off"])
         assert int(d["word_off"]) == woff and woff % 16 == 0
         if packed:
             assert int(d["min"]) == adac.stored_min(mn, mx, w)   # mn, except for the all-ones sentinel collision
@@ -81,6 +99,8 @@ def run_encode_decode(adac, orc, ctx, dtype, counts, seg_vals, rule=0, padded=Fa
         assert np.array_equal(got, words), "packed words of segment %d (w=%d)" % (s, w)
         assert adac.size_in_bytes(len(seg_vals[s]), w) == orc.size_in_bytes(len(seg_vals[s]) * w)
         woff += adac.arena_words(len(seg_vals[s]), w)
+    if FIRST_COME:
+        check_placement(adac, descs, lay.max_arena_words)
     # decode
     d_out = ctx.alloc(span * dtype.itemsize + 16)
     ctx_fill = np.full(span, 0x5A, dtype=np.uint8).repeat(dtype.itemsize).view(dtype)[:span]
@@ -720,11 +740,7 @@ def test_single_pass_encode_mixes_its_flows(adac, oracle, gpu_ctx, dtype):
         assert np.array_equal(df[f], d1[f]), f
     wf = d_words.download(np.uint64, layf.max_arena_words)
     w_ord = w1.download(np.uint64, lay1.max_arena_words)
-    foot = ((df["count"].astype(np.uint64) * df["width"] + 64) >> np.uint64(6)) + np.uint64(15) & ~np.uint64(15)
-    order = np.argsort(df["word_off"], kind="stable")
-    ends = df["word_off"][order] + foot[order]
-    assert np.all(df["word_off"] % 16 == 0) and np.all(ends[:-1] <= df["word_off"][order][1:])   # disjoint
-    assert int(ends.max()) <= layf.max_arena_words
+    check_placement(adac, df, layf.max_arena_words)
     for s in range(nseg):
         nw = int((int(df["count"][s]) * int(df["width"][s]) + 63) // 64)
         a, b = int(df["word_off"][s]), int(d1["word_off"][s])
