@@ -1359,7 +1359,9 @@ inline int64_t bp_s64(const BpType &t, uint64_t x) {
 }
 
 // TrySubtractOperator::Operation (src/function/scalar/operators/subtract.cpp:82-160) in T (as_signed = T's
-// signedness) or in T_S (as_signed = true)
+// signedness) or in T_S (as_signed = true).  The int64_t form (:141-146) stores the wrapped difference even when it
+// reports overflow, and Flush reads it: an int64 group whose max - min overflows takes DELTA_FOR when its deltas are
+// narrower than MinimumBitWidth(wrapped difference).  The narrower forms leave *res untouched.
 inline bool bp_try_sub(const BpType &t, bool as_signed, uint64_t l, uint64_t r, uint64_t *res) {
 	if (!as_signed) {
 		if ((r & t.mask) > (l & t.mask)) return false;
@@ -1368,9 +1370,9 @@ inline bool bp_try_sub(const BpType &t, bool as_signed, uint64_t l, uint64_t r, 
 	}
 	if (t.ts == 8) {
 		int64_t o;
-		if (__builtin_sub_overflow((int64_t)l, (int64_t)r, &o)) return false;
+		const bool ovf = __builtin_sub_overflow((int64_t)l, (int64_t)r, &o);
 		*res = (uint64_t)o;
-		return true;
+		return !ovf;
 	}
 	const int64_t d = bp_s64(t, l) - bp_s64(t, r);
 	const int64_t lim = (int64_t)(t.mask >> 1);

@@ -59,7 +59,11 @@ static inline int lt_t(ty t, uint64_t a, uint64_t b) {
 static inline uint64_t t_max(ty t) { return t.sg ? (t.mask >> 1) : t.mask; }
 static inline uint64_t t_min(ty t) { return t.sg ? trunc_t(t, ~(t.mask >> 1)) : 0; }
 
-/* TrySubtractOperator::Operation for T (subtract.cpp:82-160) */
+/* TrySubtractOperator::Operation for T (subtract.cpp:82-160).  The int64_t form (subtract.cpp:141-146) is
+ * __builtin_sub_overflow, which stores the wrapped difference even when it reports overflow; the 8/16/32-bit forms
+ * (OverflowCheckedSubtract, :82-92) leave *res untouched.  Flush reads min_max_diff after a failed FOR subtraction
+ * (MinimumBitWidth(min_max_diff), bitpacking.cpp:245), so an int64 group whose span overflows can still take
+ * DELTA_FOR. */
 static int try_sub(ty t, uint64_t l, uint64_t r, uint64_t *res) {
 	if (!t.sg) {
 		if ((r & t.mask) > (l & t.mask)) return 0;
@@ -68,9 +72,9 @@ static int try_sub(ty t, uint64_t l, uint64_t r, uint64_t *res) {
 	}
 	if (t.ts == 8) {
 		int64_t o;
-		if (__builtin_sub_overflow((int64_t)l, (int64_t)r, &o)) return 0;
+		int ovf = __builtin_sub_overflow((int64_t)l, (int64_t)r, &o);
 		*res = (uint64_t)o;
-		return 1;
+		return !ovf;
 	}
 	int64_t d = as_s64(t, l) - as_s64(t, r);
 	if (d < as_s64(t, t_min(t)) || d > as_s64(t, t_max(t))) return 0;
