@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <climits>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -339,28 +340,34 @@ extern "C" int adac_debug_encode_stamps(void *host, uint64_t bytes) {
 }
 
 extern "C" int adac_set_tuning(const char *name, int value) {
+	static const struct {
+		const char *name;
+		int adac::Tuning::*member;
+		int min; // smallest accepted value
+	} kKnobs[] = {
+	    {"sel_debug", &adac::Tuning::sel_debug, INT_MIN},
+	    {"single_pass_encode", &adac::Tuning::single_pass_encode, INT_MIN},
+	    {"encode_stamps", &adac::Tuning::encode_stamps, INT_MIN},
+	    {"encode_placement", &adac::Tuning::encode_placement, INT_MIN},
+	    {"encode_big_image", &adac::Tuning::encode_big_image, INT_MIN},
+	    {"encode_publish_ahead", &adac::Tuning::encode_publish_ahead, INT_MIN},
+	    {"scan_cells", &adac::Tuning::scan_cells, INT_MIN},
+	    {"tile_records", &adac::Tuning::tile_records, INT_MIN},
+	    {"gather_compact", &adac::Tuning::gather_compact, INT_MIN},
+	    {"group_sum_wide", &adac::Tuning::group_sum_wide, INT_MIN},
+	    {"group_sum_rw", &adac::Tuning::group_sum_rw, INT_MIN},
+	    {"templated_scan", &adac::Tuning::templated_scan, INT_MIN},
+	    {"scan_tiles_per_wg", &adac::Tuning::scan_tiles_per_wg, 0}, // 0 = by type
+	    {"num_cus", &adac::Tuning::num_cus, 0},                     // 0 = the device's own count
+	};
 	if (!name) return 1;
-	const std::string n(name);
-	if (n == "persistent_unpack") adac::g_tuning.persistent_unpack = value;
-	else if (n == "scan_probe") adac::g_tuning.scan_probe = value;
-	else if (n == "sel_debug") adac::g_tuning.sel_debug = value;
-	else if (n == "grouped_repack") adac::g_tuning.grouped_repack = value;
-	else if (n == "single_pass_encode") adac::g_tuning.single_pass_encode = value;
-	else if (n == "encode_stamps") adac::g_tuning.encode_stamps = value;
-	else if (n == "encode_placement") adac::g_tuning.encode_placement = value;
-	else if (n == "encode_big_image") adac::g_tuning.encode_big_image = value;
-	else if (n == "encode_publish_ahead") adac::g_tuning.encode_publish_ahead = value;
-	else if (n == "scan_cells") adac::g_tuning.scan_cells = value;
-	else if (n == "tile_records") adac::g_tuning.tile_records = value;
-	else if (n == "gather_compact") adac::g_tuning.gather_compact = value;
-	else if (n == "group_sum_wide") adac::g_tuning.group_sum_wide = value;
-	else if (n == "group_sum_rw") adac::g_tuning.group_sum_rw = value;
-	else if (n == "templated_scan") adac::g_tuning.templated_scan = value;
-	else if (n == "scan_tiles_per_wg" && value >= 0) adac::g_tuning.scan_tiles_per_wg = value; // 0 = by type
-	else if (n == "blocks_per_cu" && value > 0) adac::g_tuning.blocks_per_cu = value;
-	else if (n == "num_cus" && value >= 0) adac::g_tuning.num_cus = value;
-	else return 1;
-	return 0;
+	for (const auto &k : kKnobs) {
+		if (std::strcmp(name, k.name) != 0) continue;
+		if (value < k.min) return 1;
+		adac::g_tuning.*k.member = value;
+		return 0;
+	}
+	return 1;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -802,16 +809,10 @@ extern "C" adac_status adac_analyze_packed(adac_layout *src, const uint64_t *d_s
 	if ((!d_src_words && src->total_values) || !aligned16(d_src_words)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(src->ctx->device));
 	ADAC_HIP(adac::launch_minmax_init(src->ctx->stream, dst->d_minmax, dst->nseg));
-	if (adac::g_tuning.grouped_repack) {
-		adac_status gst = ensure_scan_groups(src);
-		if (gst != ADAC_OK) return gst;
-		ADAC_HIP(adac::launch_analyze_packed_g(src->ctx->stream, src->type_size, src->is_signed, src->null_bits, rule,
-		                                       src->d_groups, src->ngroups, d_src_words, d_validity, dst->d_minmax));
-		return ADAC_OK;
-	}
-	ADAC_HIP(adac::launch_analyze_packed(src->ctx->stream, src->type_size, src->is_signed, src->null_bits, rule,
-	                                     src->d_descs, src->d_tiles, src->ntiles, d_src_words, d_validity,
-	                                     dst->d_minmax));
+	adac_status gst = ensure_scan_groups(src);
+	if (gst != ADAC_OK) return gst;
+	ADAC_HIP(adac::launch_analyze_packed_g(src->ctx->stream, src->type_size, src->is_signed, src->null_bits, rule,
+	                                       src->d_groups, src->ngroups, d_src_words, d_validity, dst->d_minmax));
 	return ADAC_OK;
 }
 
@@ -822,15 +823,10 @@ extern "C" adac_status adac_repack(adac_layout *src, const uint64_t *d_src_words
 	if (!aligned16(d_src_words) || !aligned16(d_dst_words) || d_src_words == d_dst_words)
 		return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(src->ctx->device));
-	if (adac::g_tuning.grouped_repack) {
-		adac_status gst = ensure_scan_groups(src);
-		if (gst != ADAC_OK) return gst;
-		ADAC_HIP(adac::launch_repack_g(src->ctx->stream, src->type_size, src->null_bits, src->d_groups, src->ngroups,
-		                               dst->d_descs, d_src_words, d_validity, d_dst_words));
-		return ADAC_OK;
-	}
-	ADAC_HIP(adac::launch_repack(src->ctx->stream, src->type_size, src->null_bits, src->d_descs, dst->d_descs,
-	                             src->d_tiles, src->ntiles, d_src_words, d_validity, d_dst_words));
+	adac_status gst = ensure_scan_groups(src);
+	if (gst != ADAC_OK) return gst;
+	ADAC_HIP(adac::launch_repack_g(src->ctx->stream, src->type_size, src->null_bits, src->d_groups, src->ngroups,
+	                               dst->d_descs, d_src_words, d_validity, d_dst_words));
 	return ADAC_OK;
 }
 

@@ -97,7 +97,6 @@ hipError_t launch_unpack_jobs(hipStream_t s, uint32_t type_size, const UnpackJob
 // Launch-shape knobs (adac_set_tuning): which kernel form the scan entry points use and how many persistent
 // workgroups are launched.  Defaults are the measured-best settings on MI355X.
 struct Tuning {
-	int persistent_unpack = 0;  // measured 5-15 % slower than one tile per workgroup (profiles/r01_ab_*.json)
 	int single_pass_encode = 1; // A/B: 0 = analyze + plan + pack as three kernels (the raw column is read twice)
 	int group_sum_wide = 0;     // A/B: adac_scan_group_sum always in 64-bit arithmetic
 	int group_sum_rw = 1;       // A/B: 0 = adac_scan_group_sum without the register-walk kernel (k_group_sum only)
@@ -105,16 +104,13 @@ struct Tuning {
 	int encode_big_image = 1;   // single-pass encode, ordered placement: a segment whose packed words fit the LDS pool is packed there whole and publishes the NEXT footprint before it waits (A/B: 0)
 	int encode_publish_ahead = 1; // single-pass encode, ordered placement: the parked flow publishes the NEXT footprint before it waits (A/B: 0)
 	int encode_stamps = 0;      // diagnostic: phase time stamps of the single-pass encode (adac_debug_encode_stamps)
-	int grouped_repack = 1;     // A/B: 0 = one tile per workgroup with the 16 KiB row image (the first version)
 	int tile_records = 1;       // expanded 32-byte tile records (TileRec): bit 0 = the gather (k_gather_c: +4 - 7 %), bit 1 = the decode (k_unpack: 4 - 17 % SLOWER, off)
 	int scan_cells = 1;         // fused scans: 1 = results (and shared bitmap words) finished inside the scan kernel through arrival cells, 0 = clearing pass + atomics (+ merge kernel)
 	int gather_compact = 3;     // adac_unpack_selected: 0 = a store per selected row (k_gather), 1 = wave-level compaction + dense stores (k_gather_c), 3 = the same with non-temporal stores
 	int sel_debug = 0;          // diagnostic: selection scan without its flush (1) / without any bitmap emit (2)
-	int scan_probe = 0;         // diagnostic: fused-scan loop + loads only (no field walk)
 	int templated_scan = 1;     // width-templated register path of the fused scans for 4 <= w <= 32
 	int scan_tiles_per_wg = 0; // tiles per fused-scan workgroup; 0 = by type (12 tiles of u64, 6 of u32, 8 of u16, 4 of u8)
 	int num_cus = 0;        // 0 = the device's own count (256 on a whole MI355X: 8 XCDs x 32 CUs); > 0 overrides
-	int blocks_per_cu = 8;  // 256-thread workgroups resident per CU (2048 threads, <= 16.5 KiB LDS each)
 };
 extern Tuning g_tuning;
 
@@ -138,12 +134,6 @@ hipError_t launch_unpack_range(hipStream_t s, uint32_t type_size, const adac_seg
                                const uint64_t *d_words, void *d_out);
 hipError_t launch_fetch(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs, const uint64_t *d_words,
                         const uint32_t *d_segs, const uint32_t *d_rows, uint64_t n, void *d_out);
-hipError_t launch_analyze_packed(hipStream_t s, uint32_t type_size, bool sign_extend, uint64_t null_bits, int rule,
-                                 const adac_segment_desc *d_src_descs, const TileRef *d_tiles, uint64_t ntiles,
-                                 const uint64_t *d_src_words, const uint64_t *d_validity, uint64_t *d_minmax);
-hipError_t launch_repack(hipStream_t s, uint32_t type_size, uint64_t null_bits, const adac_segment_desc *d_src_descs,
-                         const adac_segment_desc *d_dst_descs, const TileRef *d_tiles, uint64_t ntiles,
-                         const uint64_t *d_src_words, const uint64_t *d_validity, uint64_t *d_dst_words);
 // single-pass encode (adac_encode_1p.inl): every segment must fit sixteen 16-byte chunks per thread of a 1024-thread
 // workgroup, counted from the 16-byte boundary at or before its first element
 constexpr uint64_t kEncodeOnePassBytes = 16ull * 1024 * 16;

@@ -877,10 +877,6 @@ __device__ __forceinline__ void scan_run_w(const uint4 *__restrict__ seg16, uint
 		nrm[4] = e >> o0;
 		q = qn;
 		e = en;
-		if (OP == 2) { // load-only probe (diagnostic): same loop and loads, no field walk
-			acc += nrm[0] + nrm[1] + nrm[2] + nrm[3] + nrm[4];
-			continue;
-		}
 		const uint32_t starting = (128u - o0 + (W - 1)) / W; // rows starting in the chunk: MAXV-1 or MAXV
 		const uint32_t lim = r1 > i0 ? r1 - i0 : 0u;
 		if (OP == 1 && !V) {
@@ -1053,11 +1049,11 @@ __global__ void k_sel_merge_edges(const SelEdge *__restrict__ edges, uint64_t nr
 	bitmap32[me.word] = bits;
 }
 
-// OP 0: SUM, 1: COUNT(lo <= v <= hi), 2: load-only probe, 3: COUNT + selection bitmap; V: validity mask given.
+// OP 0: SUM, 1: COUNT(lo <= v <= hi), 3: COUNT + selection bitmap; V: validity mask given.
 // One workgroup per ScanGroup: up to scan_tiles_per_wg consecutive tiles of ONE segment.
 // NARROW: the kernel of the groups at widths 2 and 3 (listed in narrow_idx by k_expand_groups); the common kernel
 // leaves those groups alone.  The SUM under a validity mask has no narrow form (its widths 2 and 3 take the LDS path).
-template <int OP, bool V> constexpr bool kScanHasNarrowKernel = !(OP == 0 && V) && OP != 2;
+template <int OP, bool V> constexpr bool kScanHasNarrowKernel = !(OP == 0 && V);
 
 template <typename U, int OP, bool V, bool NARROW>
 __global__ __launch_bounds__(kWorkgroup, NARROW ? 4 : 6) void k_scan_agg(
@@ -1177,98 +1173,8 @@ __global__ __launch_bounds__(kWorkgroup, NARROW ? 4 : 6) void k_scan_agg(
 	}
 }
 
-// ---------------------------------------------------------------------------------------------
-// Persistent form of the decode kernel (A/B option).  A single tile's chain (tile table -> descriptor -> packed loads ->
-// barrier -> decode [-> wave reduce -> atomic]) is serial and its fixed part is as long as the decode of a
-// 16 KiB tile, so read-only scans leave HBM idle.  Here a workgroup owns a CONTIGUOUS run of tiles and keeps
-// the next tile's packed bytes in flight with LDS-DMA (global_load_lds_dwordx4: global -> LDS, no VGPRs)
-// into the other half of a double-buffered LDS image while it decodes the current half; one barrier per
-// tile; aggregates are carried in registers across the tiles of a segment and flushed once per segment.
-// (A first version prefetched into registers under `if (c < nchunks)`: hipcc put s_waitcnt vmcnt(0) behind
-// every conditional load — cdna_hip_programming.md §5 item 4(c) — and it ran 0.6x; LDS-DMA has no
-// destination register to merge, so nothing forces an early wait.)
-// ---------------------------------------------------------------------------------------------
-constexpr int kMaxChunks = kTileBytes / 16 + 2;
-
-struct TileJob {
-	const uint4 *src;  // first 16-byte chunk of the tile's packed bits
-	uint64_t elem0;    // element index of the tile's first row in the value buffer
-	uint64_t add;      // frame of reference to add back (0 if none)
-	uint32_t seg, n, w, bit0, nchunks;
-};
-
-template <int TILE>
-__device__ __forceinline__ TileJob make_job(const adac_segment_desc *__restrict__ descs,
-                                            const TileRef *__restrict__ tiles, uint32_t t,
-                                            const uint64_t *__restrict__ words) {
-	const TileRef r = tiles[t];
-	const adac_segment_desc d = descs[r.seg];
-	TileJob j;
-	j.seg = r.seg;
-	const uint32_t left = d.count - r.first;
-	j.n = left < (uint32_t)TILE ? left : (uint32_t)TILE;
-	j.w = d.width;
-	j.elem0 = d.val_off + r.first;
-	j.add = effective_add(d);
-	const uint64_t bitpos = (uint64_t)r.first * j.w;
-	j.bit0 = (uint32_t)(bitpos & 127);
-	j.nchunks = (j.bit0 + j.n * j.w + 127u) >> 7;
-	j.src = reinterpret_cast<const uint4 *>(words + d.word_off) + (bitpos >> 7);
-	return j;
-}
-
 using gptr_t = const __attribute__((address_space(1))) void *;
 using lptr_t = __attribute__((address_space(3))) void *;
-
-// Fire-and-forget copy of `nchunks` 16-byte chunks global -> LDS.  One wave instruction moves 1 KiB; its LDS
-// destination is the wave-uniform base + lane*16 (M0), so each wave copies 64 consecutive chunks per round.
-__device__ __forceinline__ void dma_chunks(const uint4 *__restrict__ src, uint32_t nchunks, uint4 *lds_buf) {
-	const uint32_t lane = threadIdx.x & 63u;
-	for (uint32_t base = threadIdx.x & ~63u; base < nchunks; base += kWorkgroup) {
-		const uint32_t c = base + lane;
-		if (c < nchunks) {
-			__builtin_amdgcn_global_load_lds((gptr_t)(src + c), (lptr_t)(lds_buf + base), 16, 0, 0);
-		}
-	}
-}
-
-__device__ __forceinline__ void tile_range(uint32_t ntiles, uint32_t &lo, uint32_t &hi) {
-	const uint32_t per = (ntiles + gridDim.x - 1) / gridDim.x;
-	lo = blockIdx.x * per;
-	hi = lo + per < ntiles ? lo + per : ntiles;
-}
-
-template <typename U>
-__global__ __launch_bounds__(kWorkgroup) void k_unpack_p(const adac_segment_desc *__restrict__ descs,
-                                                         const TileRef *__restrict__ tiles, uint32_t ntiles,
-                                                         const uint64_t *__restrict__ words, U *__restrict__ out) {
-	constexpr int TILE = kTileBytes / (int)sizeof(U);
-	constexpr uint32_t K = 16 / sizeof(U);
-	__shared__ uint4 lds[2][kMaxChunks];
-	uint32_t t, hi;
-	tile_range(ntiles, t, hi);
-	if (t >= hi) return;
-	TileJob cur = make_job<TILE>(descs, tiles, t, words);
-	dma_chunks(cur.src, cur.nchunks, lds[0]);
-	uint32_t buf = 0;
-	for (;;) {
-		__syncthreads(); // drains this wave's DMA (vmcnt) and publishes the image; also fences the other half
-		const bool more = t + 1 < hi;
-		TileJob nxt = cur;
-		if (more) {
-			nxt = make_job<TILE>(descs, tiles, t + 1, words);
-			dma_chunks(nxt.src, nxt.nchunks, lds[buf ^ 1]); // lands while this tile is decoded
-		}
-		const uint32_t *lds32 = reinterpret_cast<const uint32_t *>(lds[buf]);
-		StoreSink<U> sink {out + cur.elem0, cur.n};
-		const uint32_t align = (uint32_t)(cur.elem0 & (K - 1));
-		decode_tile<U>(lds32, cur.bit0, cur.w, cur.add, cur.n, align, sink);
-		if (!more) break;
-		cur = nxt;
-		buf ^= 1;
-		t++;
-	}
-}
 
 // ---------------------------------------------------------------------------------------------
 // Raw value access shared by k_analyze and k_pack: chunks of K rows aligned to 16 bytes of the element index.
@@ -1552,134 +1458,17 @@ __global__ __launch_bounds__(kWorkgroup) void k_pack(const adac_segment_desc *__
 // ---------------------------------------------------------------------------------------------
 // Re-compaction packed -> packed (SURVEY.md §8b `adac_repack`, §8d "old_w -> new_w: n (old_w + new_w) / 8 bytes").
 // The reference only ever compacts from full-width slots (BitCompressFromSuccinct, column_segment.cpp:348-383);
-// these two kernels are the same two passes with a PACKED source: the tile's values come from decoding the
-// source segment's staged bits instead of from a raw array, everything downstream (min/max rules, width, the
-// word-owner pack) is shared with k_analyze / k_pack.  Source and destination layouts have the same counts.
-// ---------------------------------------------------------------------------------------------
-template <typename U>
-__global__ __launch_bounds__(kWorkgroup) void k_analyze_packed(const adac_segment_desc *__restrict__ src_descs,
-                                                               const TileRef *__restrict__ tiles,
-                                                               const uint64_t *__restrict__ src_words,
-                                                               const uint64_t *__restrict__ validity, int sign_extend,
-                                                               uint64_t null_bits, int rule,
-                                                               uint64_t *__restrict__ minmax) {
-	constexpr int TILE = kTileBytes / (int)sizeof(U);
-	using S = typename std::make_signed<U>::type;
-	__shared__ uint4 lds[kTileBytes / 16 + 2];
-	__shared__ uint64_t pmin[kWorkgroup / 64], pmax[kWorkgroup / 64];
-	const TileCtx t = resolve_tile<TILE>(src_descs, tiles);
-	const uint32_t bit0 = stage_packed(src_words + t.d.word_off, t.first, t.n, t.d.width, lds);
-	__syncthreads();
-	uint64_t mn = ~0ull, mx = 0;
-	auto sink = [&](int32_t base, const U *v, bool full) { // align 0: base >= 0
-		constexpr int K = 16 / (int)sizeof(U);
-		const uint32_t rows_here = full || t.n - (uint32_t)base >= (uint32_t)K ? (uint32_t)K : t.n - (uint32_t)base;
-		const uint32_t vbits = validity ? validity_window(validity, t.elem0 + (uint32_t)base, rows_here) : 0xffffffffu;
-#pragma unroll
-		for (int j = 0; j < K; j++) {
-			if (!full && (uint32_t)(base + j) >= t.n) continue;
-			const bool valid = (vbits >> j) & 1u;
-			uint64_t x;
-			if (rule == ADAC_RULE_APPEND) { // succinct.cpp:286-287: NULL rows do not take part
-				if (!valid) continue;
-				x = sign_extend ? (uint64_t)(int64_t)(S)v[j] : (uint64_t)v[j];
-			} else { // column_segment.cpp:392-399: every slot, zero-extended; NULL slots hold NullValue<T>
-				x = valid ? (uint64_t)v[j] : null_bits;
-			}
-			mn = x < mn ? x : mn;
-			mx = x > mx ? x : mx;
-		}
-	};
-	decode_tile<U>(reinterpret_cast<const uint32_t *>(lds), bit0, t.d.width, effective_add(t.d), t.n, 0u, sink);
-	mn = wave_min(mn);
-	mx = wave_max(mx);
-	if ((threadIdx.x & 63) == 0) {
-		pmin[threadIdx.x >> 6] = mn;
-		pmax[threadIdx.x >> 6] = mx;
-	}
-	__syncthreads();
-	if (threadIdx.x == 0) {
-#pragma unroll
-		for (int i = 1; i < kWorkgroup / 64; i++) {
-			mn = pmin[i] < mn ? pmin[i] : mn;
-			mx = pmax[i] > mx ? pmax[i] : mx;
-		}
-		atomicMin(reinterpret_cast<unsigned long long *>(minmax + 2 * (uint64_t)t.seg), (unsigned long long)mn);
-		atomicMax(reinterpret_cast<unsigned long long *>(minmax + 2 * (uint64_t)t.seg + 1), (unsigned long long)mx);
-	}
-}
-
-template <typename U>
-__global__ __launch_bounds__(kWorkgroup) void k_repack(const adac_segment_desc *__restrict__ src_descs,
-                                                       const adac_segment_desc *__restrict__ dst_descs,
-                                                       const TileRef *__restrict__ tiles,
-                                                       const uint64_t *__restrict__ src_words,
-                                                       const uint64_t *__restrict__ validity, uint64_t null_bits,
-                                                       uint64_t *__restrict__ dst_words) {
-	constexpr int TILE = kTileBytes / (int)sizeof(U);
-	__shared__ uint4 lds[kTileBytes / 16 + 2];
-	__shared__ __attribute__((aligned(16))) U delta[TILE];
-	const TileCtx t = resolve_tile<TILE>(src_descs, tiles);
-	const adac_segment_desc dd = dst_descs[t.seg];
-	const uint32_t w = dd.width;
-	const bool packed = (dd.flags & ADAC_SEG_PACKED) != 0;
-	const U sub = (U)((packed && dd.min != ADAC_NO_MIN) ? dd.min : 0ull); // column_segment.cpp:371-373
-	const U wmask = (U)mask64(w);
-	const uint32_t bit0 = stage_packed(src_words + t.d.word_off, t.first, t.n, t.d.width, lds);
-	__syncthreads();
-	auto sink = [&](int32_t base, const U *v, bool full) {
-		constexpr int K = 16 / (int)sizeof(U);
-		const uint32_t rows_here = full || t.n - (uint32_t)base >= (uint32_t)K ? (uint32_t)K : t.n - (uint32_t)base;
-		const uint32_t vbits = validity ? validity_window(validity, t.elem0 + (uint32_t)base, rows_here) : 0xffffffffu;
-		if (full) {
-			U o[K];
-#pragma unroll
-			for (int j = 0; j < K; j++) {
-				const U x = ((vbits >> j) & 1u) ? v[j] : (U)null_bits;
-				o[j] = (U)(x - sub) & wmask;
-			}
-			uint4 q;
-			__builtin_memcpy(&q, o, 16);
-			*reinterpret_cast<uint4 *>(delta + base) = q; // base is a multiple of K: ds_write_b128
-		} else {
-#pragma unroll
-			for (int j = 0; j < K; j++) {
-				if ((uint32_t)(base + j) >= t.n) continue;
-				const U x = ((vbits >> j) & 1u) ? v[j] : (U)null_bits;
-				delta[base + j] = (U)(x - sub) & wmask;
-			}
-		}
-	};
-	decode_tile<U>(reinterpret_cast<const uint32_t *>(lds), bit0, t.d.width, effective_add(t.d), t.n, 0u, sink);
-	__syncthreads();
-	const uint64_t word0 = ((uint64_t)t.first * w) >> 6;
-	const uint32_t nwords = (t.n * w + 63u) >> 6;
-	uint64_t *__restrict__ dst = dst_words + dd.word_off + word0;
-	for (uint32_t q = threadIdx.x; q < nwords; q += kWorkgroup) { // word-owner gather, as in k_pack
-		const uint32_t bitlo = q << 6;
-		uint32_t i = bitlo / w;
-		uint32_t last = (bitlo + 63u) / w;
-		last = last < t.n ? last : t.n - 1;
-		uint64_t acc = 0;
-		for (; i <= last; i++) {
-			const uint64_t v = (uint64_t)delta[i];
-			const int32_t pos = (int32_t)(i * w) - (int32_t)bitlo;
-			acc |= pos >= 0 ? (v << pos) : (v >> (-pos));
-		}
-		__builtin_nontemporal_store(acc, &dst[q]); // written once, read much later
-	}
-}
-
-// ---------------------------------------------------------------------------------------------
-// Grouped re-compaction (the default form).  One tile per workgroup moves only n (old_w + new_w) / 8 bytes — 4 KiB at
-// 8 -> 8 bits — behind a full HBM round trip and two barriers, and the 16 KiB row image allows four workgroups per
-// CU: ~8 KiB in flight per CU, i.e. ~1.2 TB/s at narrow widths whatever the inner loops do (measured, DESIGN.md
-// §2).  Here a workgroup owns a ScanGroup of the source layout (several tiles of one segment) and walks it in stages
-// of as many whole tiles as fit 16 KiB of PACKED bytes on both sides, so the bytes in flight per workgroup no longer
-// shrink with the width; and the row image is gone: a lane combines the K rows of its chunk into one bit string of
-// K * new_w <= 128 bits in registers and ORs it into a zeroed LDS image of the OUTPUT words (ds_or_b64, one to three
-// per chunk), which the workgroup then copies out with 16-byte stores.  Adjacent lanes touch adjacent words, so
-// there is no strided LDS access left to conflict.
+// k_analyze_packed_g / k_repack_g are the same two passes with a PACKED source: the values come from decoding the
+// source segment's staged bits instead of from a raw array, the min/max rules and the width are those of k_analyze /
+// k_pack.  Source and destination layouts have the same counts.
+// One tile per workgroup would move only n (old_w + new_w) / 8 bytes — 4 KiB at 8 -> 8 bits — behind a full HBM round
+// trip and two barriers, and a 16 KiB row image allows four workgroups per CU: ~8 KiB in flight per CU, i.e.
+// ~1.2 TB/s at narrow widths whatever the inner loops do (measured).  Here a workgroup owns a ScanGroup
+// of the source layout (several tiles of one segment) and walks it in stages of as many whole tiles as fit 16 KiB of
+// PACKED bytes on both sides, so the bytes in flight per workgroup do not shrink with the width; and there is no row
+// image: a lane combines the K rows of its chunk into one bit string of K * new_w <= 128 bits in registers and ORs it
+// into a zeroed LDS image of the OUTPUT words (ds_or_b64, one to three per chunk), which the workgroup then copies out
+// with 16-byte stores.  Adjacent lanes touch adjacent words, so there is no strided LDS access left to conflict.
 // ---------------------------------------------------------------------------------------------
 // K masked fields of `w` bits (w <= 8 * sizeof(U)), row order -> the K * w-bit string {lo, hi}
 template <typename U>
@@ -2239,11 +2028,6 @@ uint64_t device_cus() {
 	return (uint64_t)cached[dev];
 }
 
-unsigned persistent_grid(uint64_t ntiles) {
-	const uint64_t cap = device_cus() * (uint64_t)g_tuning.blocks_per_cu;
-	return (unsigned)(ntiles < cap ? ntiles : cap);
-}
-
 } // namespace
 
 hipError_t launch_minmax_init(hipStream_t s, uint64_t *d_minmax, uint64_t nseg) {
@@ -2280,30 +2064,6 @@ hipError_t launch_pack(hipStream_t s, uint32_t type_size, uint64_t null_bits, co
 		using U = decltype(tag);
 		hipLaunchKernelGGL(k_pack<U>, dim3((unsigned)ntiles), dim3(kWorkgroup), 0, s, d_descs, d_tiles,
 		                   static_cast<const U *>(d_vals), d_validity, null_bits, d_words);
-		return hipGetLastError();
-	});
-}
-
-hipError_t launch_analyze_packed(hipStream_t s, uint32_t type_size, bool sign_extend, uint64_t null_bits, int rule,
-                                 const adac_segment_desc *d_src_descs, const TileRef *d_tiles, uint64_t ntiles,
-                                 const uint64_t *d_src_words, const uint64_t *d_validity, uint64_t *d_minmax) {
-	if (ntiles == 0) return hipSuccess;
-	return dispatch_size(type_size, [&](auto tag) {
-		using U = decltype(tag);
-		hipLaunchKernelGGL(k_analyze_packed<U>, dim3((unsigned)ntiles), dim3(kWorkgroup), 0, s, d_src_descs, d_tiles,
-		                   d_src_words, d_validity, sign_extend ? 1 : 0, null_bits, rule, d_minmax);
-		return hipGetLastError();
-	});
-}
-
-hipError_t launch_repack(hipStream_t s, uint32_t type_size, uint64_t null_bits, const adac_segment_desc *d_src_descs,
-                         const adac_segment_desc *d_dst_descs, const TileRef *d_tiles, uint64_t ntiles,
-                         const uint64_t *d_src_words, const uint64_t *d_validity, uint64_t *d_dst_words) {
-	if (ntiles == 0) return hipSuccess;
-	return dispatch_size(type_size, [&](auto tag) {
-		using U = decltype(tag);
-		hipLaunchKernelGGL(k_repack<U>, dim3((unsigned)ntiles), dim3(kWorkgroup), 0, s, d_src_descs, d_dst_descs,
-		                   d_tiles, d_src_words, d_validity, null_bits, d_dst_words);
 		return hipGetLastError();
 	});
 }
@@ -2423,12 +2183,6 @@ hipError_t launch_unpack(hipStream_t s, uint32_t type_size, const adac_segment_d
 	if (ntiles == 0) return hipSuccess;
 	return dispatch_size(type_size, [&](auto tag) {
 		using U = decltype(tag);
-		if (g_tuning.persistent_unpack) {
-			const unsigned grid = persistent_grid(ntiles);
-			hipLaunchKernelGGL(k_unpack_p<U>, dim3(grid), dim3(kWorkgroup), 0, s, d_descs, d_tiles, (uint32_t)ntiles,
-			                   d_words, static_cast<U *>(d_out));
-			return hipGetLastError();
-		}
 		if (d_recs) {
 			hipLaunchKernelGGL((k_unpack<U, false, true>), dim3((unsigned)ntiles), dim3(kWorkgroup), 0, s, d_descs, d_tiles,
 			                   RangeArgs {}, d_words, static_cast<U *>(d_out), d_recs);
@@ -2495,11 +2249,7 @@ hipError_t launch_scan_sum(hipStream_t s, uint32_t type_size, const ScanGroupLis
 		const int tpl = g_tuning.templated_scan | (g_tuning.sel_debug == 7 ? 7 << 1 : 0);
 		uint32_t *no_bitmap = nullptr;
 		SelEdge *no_edges = nullptr;
-		if (g_tuning.scan_probe) { // diagnostic: the scan's loop and loads without the field walk (result meaningless)
-			hipLaunchKernelGGL((k_scan_agg<U, 2, false, false>), grid, dim3(kWorkgroup), 0, s, gl.d_groups, gl.d_narrow_idx,
-			                   1, d_words, RangePred {}, static_cast<const uint64_t *>(nullptr), d_sums, no_bitmap, no_edges,
-			                   gl.d_res_cells, no_bitmap, 0u, ~0ull);
-		} else if (d_validity) {
+		if (d_validity) {
 			hipLaunchKernelGGL((k_scan_agg<U, 0, true, false>), grid, dim3(kWorkgroup), 0, s, gl.d_groups, gl.d_narrow_idx,
 			                   tpl, d_words, widen, d_validity, d_sums, no_bitmap, no_edges, gl.d_res_cells, no_bitmap, 0u, ~0ull);
 		} else {

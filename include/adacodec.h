@@ -138,14 +138,16 @@ uint64_t adac_block_stride(uint64_t count, uint8_t width);
 
 /* values per device tile for a type (16 KiB of decoded output) */
 uint32_t adac_tile_values(int physical_type);
-/* Launch-shape knobs for in-process A/B measurement: "persistent_unpack", "templated_scan", "scan_probe" (0/1),
- * "scan_tiles_per_wg" (tiles per fused-scan workgroup; 0 = chosen by type), "blocks_per_cu",
- * "num_cus", "single_pass_encode" (0 = analyze + plan + pack as three kernels).  Decoded values, packed words, widths
- * and mins never depend on them.  One knob changes WHERE adac_encode puts a segment in the arena: "encode_placement" 1
- * hands out arena space in order of completion (a cursor, no ordered look-back) instead of the exclusive prefix in
- * segment order that adac_plan computes: descriptors then carry offsets that differ from run to run (disjoint,
- * 128-byte aligned, inside max_arena_words).  "encode_stamps" 1 records diagnostic time stamps.  Returns 0 if the name
- * is known. */
+/* Launch-shape knobs for in-process A/B measurement: "templated_scan" (0/1), "scan_tiles_per_wg" (tiles per fused-scan
+ * workgroup; 0 = chosen by type), "num_cus" (0 = the device's own count), "single_pass_encode" (0 = analyze + plan +
+ * pack as three kernels), "encode_big_image", "encode_publish_ahead", "scan_cells", "tile_records", "gather_compact",
+ * "group_sum_wide", "group_sum_rw", "sel_debug": the table in adac_set_tuning is the full list, Tuning in
+ * csrc/adac_internal.h says what each does.  Decoded values, packed words, widths and mins never depend on them.  One
+ * knob changes WHERE adac_encode puts a segment in the arena: "encode_placement" 1 hands out arena space in order of
+ * completion (a cursor, no ordered look-back) instead of the exclusive prefix in segment order that adac_plan computes:
+ * descriptors then carry offsets that differ from run to run (disjoint, 128-byte aligned, inside max_arena_words).
+ * "encode_stamps" 1 records diagnostic time stamps.  Returns 0 if the name is known and the value accepted
+ * ("scan_tiles_per_wg" and "num_cus" refuse negative values), 1 otherwise. */
 int adac_set_tuning(const char *name, int value);
 /* Diagnostic, not part of the drop-in boundary: the phase time stamps (8 x uint64 per segment) the single-pass encode
  * recorded while "encode_stamps" was set (tools/encode_stamps.py).  Returns 0 on success. */

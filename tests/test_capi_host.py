@@ -99,6 +99,26 @@ def test_device_entry_points_fail_loudly_without_a_gpu(adac, lib):
     assert lib.adac_analyze(None, None, None, 0) == 1
 
 
+def test_set_tuning_names_and_bounds(lib):
+    """adac_set_tuning answers 0 for every knob name the tests, bench.py, bench_configs.py and tools/ pass (and for the
+    two others its table holds, gather_compact and num_cus), 1 for the retired names, for "" and for a name nobody ever
+    had; scan_tiles_per_wg and num_cus refuse negative values.  Each knob is set to its default (Tuning in
+    csrc/adac_internal.h), so the process is left as it was."""
+    defaults = [("sel_debug", 0), ("single_pass_encode", 1), ("encode_stamps", 0), ("encode_placement", 0),
+                ("encode_big_image", 1), ("encode_publish_ahead", 1), ("scan_cells", 1), ("tile_records", 1),
+                ("gather_compact", 3), ("group_sum_wide", 0), ("group_sum_rw", 1), ("templated_scan", 1),
+                ("scan_tiles_per_wg", 0), ("num_cus", 0)]
+    for name, value in defaults:
+        assert lib.adac_set_tuning(name.encode(), value) == 0, name
+    for name in ("persistent_unpack", "blocks_per_cu", "grouped_repack", "scan_probe", "", "no_such_knob"):
+        for value in (0, 1, 8):
+            assert lib.adac_set_tuning(name.encode(), value) != 0, name
+    assert lib.adac_set_tuning(None, 0) == 1
+    for name in ("scan_tiles_per_wg", "num_cus"):
+        assert lib.adac_set_tuning(name.encode(), -1) != 0, name
+        assert lib.adac_set_tuning(name.encode(), 0) == 0, name
+
+
 def test_workload_generator(adac):
     import importlib
     wl = importlib.import_module(adac.__name__ + ".workload")

@@ -22,25 +22,21 @@ def main():
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 7
     ctx = adac.Context(0)
     rng = np.random.default_rng(1)
-    base = {"persistent_unpack": 0, "scan_probe": 0}
     variants = [
-        ("lds x1", dict(base, templated_scan=0, scan_tiles_per_wg=1)),
-        ("lds x8", dict(base, templated_scan=0, scan_tiles_per_wg=8)),
-        ("templ auto", dict(base, templated_scan=1, scan_tiles_per_wg=0)),
-        ("templ x1", dict(base, templated_scan=1, scan_tiles_per_wg=1)),
-        ("templ x2", dict(base, templated_scan=1, scan_tiles_per_wg=2)),
-        ("templ x3", dict(base, templated_scan=1, scan_tiles_per_wg=3)),
-        ("templ x4", dict(base, templated_scan=1, scan_tiles_per_wg=4)),
-        ("templ x6", dict(base, templated_scan=1, scan_tiles_per_wg=6)),
-        ("templ x7", dict(base, templated_scan=1, scan_tiles_per_wg=7)),
-        ("templ x12", dict(base, templated_scan=1, scan_tiles_per_wg=12)),
-        ("templ x15", dict(base, templated_scan=1, scan_tiles_per_wg=15)),
-        ("templ x8", dict(base, templated_scan=1, scan_tiles_per_wg=8)),
-        ("templ x16", dict(base, templated_scan=1, scan_tiles_per_wg=16)),
-        ("templ x32", dict(base, templated_scan=1, scan_tiles_per_wg=32)),
-        ("probe x8", dict(base, templated_scan=1, scan_tiles_per_wg=8, scan_probe=1)),
-        ("probe x16", dict(base, templated_scan=1, scan_tiles_per_wg=16, scan_probe=1)),
-        ("persistent-dma-8/cu", {"persistent_unpack": 1, "blocks_per_cu": 8, "templated_scan": 0}),
+        ("lds x1", dict(templated_scan=0, scan_tiles_per_wg=1)),
+        ("lds x8", dict(templated_scan=0, scan_tiles_per_wg=8)),
+        ("templ auto", dict(templated_scan=1, scan_tiles_per_wg=0)),
+        ("templ x1", dict(templated_scan=1, scan_tiles_per_wg=1)),
+        ("templ x2", dict(templated_scan=1, scan_tiles_per_wg=2)),
+        ("templ x3", dict(templated_scan=1, scan_tiles_per_wg=3)),
+        ("templ x4", dict(templated_scan=1, scan_tiles_per_wg=4)),
+        ("templ x6", dict(templated_scan=1, scan_tiles_per_wg=6)),
+        ("templ x7", dict(templated_scan=1, scan_tiles_per_wg=7)),
+        ("templ x12", dict(templated_scan=1, scan_tiles_per_wg=12)),
+        ("templ x15", dict(templated_scan=1, scan_tiles_per_wg=15)),
+        ("templ x8", dict(templated_scan=1, scan_tiles_per_wg=8)),
+        ("templ x16", dict(templated_scan=1, scan_tiles_per_wg=16)),
+        ("templ x32", dict(templated_scan=1, scan_tiles_per_wg=32)),
     ]
     out = {"rows": rows, "rounds": rounds, "cases": []}
     cases = ((np.uint64, 8), (np.uint64, 16), (np.uint64, 32), (np.uint64, 48), (np.uint32, 8), (np.uint32, 16),
@@ -101,13 +97,12 @@ def main():
             lay.scan_sum(d_words, d_sums)
             ctx.sync()
             assert np.array_equal(d_out.download(dtype, rows), vals), name
-            if not knobs.get("scan_probe"):
-                assert int(d_sums.download(np.uint64, len(counts)).sum(dtype=np.uint64)) == ref_sum, name
-                ref_cnt = int(((vals >= lo_key) & (vals <= hi_key)).sum())
-                lay.scan_count_between(d_words, lo_key, hi_key, d_sums)
-                assert int(d_sums.download(np.uint64, len(counts)).sum()) == ref_cnt, name
-                lay.scan_select_between(d_words, lo_key, hi_key, d_bm, d_sums)
-                assert int(d_sums.download(np.uint64, len(counts)).sum()) == ref_cnt, name
+            assert int(d_sums.download(np.uint64, len(counts)).sum(dtype=np.uint64)) == ref_sum, name
+            ref_cnt = int(((vals >= lo_key) & (vals <= hi_key)).sum())
+            lay.scan_count_between(d_words, lo_key, hi_key, d_sums)
+            assert int(d_sums.download(np.uint64, len(counts)).sum()) == ref_cnt, name
+            lay.scan_select_between(d_words, lo_key, hi_key, d_bm, d_sums)
+            assert int(d_sums.download(np.uint64, len(counts)).sum()) == ref_cnt, name
         case = {"dtype": "u%d" % (8 * dtype.itemsize), "width": w, "variants": {}}
         for name, _ in variants:
             mu = float(np.median(times[name]["unpack"]))
@@ -122,7 +117,6 @@ def main():
             }
         out["cases"].append(case)
         del lay, d_vals, d_words, d_out, d_sums, d_bm
-    adac.set_tuning("scan_probe", 0)
     print(json.dumps(out))
 
 
