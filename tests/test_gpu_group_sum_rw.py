@@ -32,6 +32,16 @@ def both_ways(adac, ctx, vals, keys, counts, ngroups):
 def test_every_value_width_against_every_key_width(adac, gpu_ctx, vdtype):
     vdtype = np.dtype(vdtype)
     rng = np.random.default_rng(31 + vdtype.itemsize)
+    widths, counts, vals = every_width_column(rng, vdtype)
+    for wk in range(1, 9):
+        for ngroups, kbase in ((7, 0), (min(7, 2 ** wk), 0), (7, 2)):
+            keys = (rng.integers(0, 2 ** wk, size=len(vals)) + kbase).astype(np.uint8 if wk + kbase.bit_length() < 8 else np.uint16)
+            vd, kd = both_ways(adac, gpu_ctx, vals, keys, counts, ngroups)
+            assert sorted(set(vd["width"].tolist())) == widths and set(kd["width"].tolist()) <= {wk, wk + 1}
+
+
+def every_width_column(rng, vdtype):
+    """(widths, counts, vals): one segment per value width the register walk takes, 4 .. 32 and below the type's."""
     tb = 8 * vdtype.itemsize
     widths = [w for w in range(4, 33) if w < tb]
     # one segment per value width (ragged sizes, some spanning several scan groups), all in ONE column
@@ -44,16 +54,11 @@ def test_every_value_width_against_every_key_width(adac, gpu_ctx, vdtype):
         span = rng.integers(0, 2 ** w, size=int(c), dtype=np.uint64)
         span[:2] = (0, 2 ** w - 1)
         parts.append(((span.astype(object) + base) % (2 ** tb)).astype(np.dtype("u%d" % vdtype.itemsize)).view(vdtype))
-    vals = np.concatenate(parts)
-    for wk in range(1, 9):
-        for ngroups, kbase in ((7, 0), (min(7, 2 ** wk), 0), (7, 2)):
-            keys = (rng.integers(0, 2 ** wk, size=len(vals)) + kbase).astype(np.uint8 if wk + kbase.bit_length() < 8 else np.uint16)
-            vd, kd = both_ways(adac, gpu_ctx, vals, keys, counts, ngroups)
-            assert sorted(set(vd["width"].tolist())) == widths and set(kd["width"].tolist()) <= {wk, wk + 1}
+    return widths, counts, np.concatenate(parts)
 
 
-def test_segments_the_register_walk_leaves_to_the_staged_kernel(adac, gpu_ctx):
-    rng = np.random.default_rng(5150)
+def mixed_walk_column(rng):
+    """(vals, keys, counts): int64 segments the register walk takes next to ones it leaves to the staged kernel."""
     counts = np.array([20000, 4096, 33000, 2048, 50000, 7, 12345, 9000], dtype=np.uint32)
     n = int(counts.sum())
     starts = [int(x) for x in np.concatenate([[0], np.cumsum(counts)[:-1]])]
@@ -75,6 +80,11 @@ def test_segments_the_register_walk_leaves_to_the_staged_kernel(adac, gpu_ctx):
     keys[starts[2]:starts[2] + counts_i[2]] = rng.integers(0, 1000, size=counts_i[2])
     keys[starts[4]:starts[4] + counts_i[4]] += 300          # all of them overflow: the constant-byte form
     keys[starts[7]:starts[7] + counts_i[7]] = rng.integers(2, 6, size=counts_i[7])   # frame of reference 2 on the keys
+    return vals, keys, counts
+
+
+def test_segments_the_register_walk_leaves_to_the_staged_kernel(adac, gpu_ctx):
+    vals, keys, counts = mixed_walk_column(np.random.default_rng(5150))
     vd, kd = both_ways(adac, gpu_ctx, vals, keys, counts, 6)
     assert vd["width"].tolist()[:5] == [2, 40, 13, 1, 24] and kd["width"].tolist()[2] == 10
     # the rule-RECOMPACT encode of the wrapping segment is what makes it non-linear; with the append rule it stays raw

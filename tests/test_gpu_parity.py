@@ -668,6 +668,27 @@ def test_unpack_jobs_layout_free_batches(adac, oracle, gpu_ctx):
             adac.unpack_jobs(gpu_ctx, dtype, bad, d_words, base)
 
 
+def mixed_flow_column(dtype, nseg=700):
+    """Random segments of every size up to a full block, at random placements, with widths that alternate between the
+    flows of the single-pass encode: (counts, seg_vals, offs as a list, offs as the val_offs array)."""
+    dtype = np.dtype(dtype)
+    tb = 8 * dtype.itemsize
+    rng = np.random.default_rng(1234 + tb + (dtype.kind == "i"))
+    full = 262136 // dtype.itemsize
+    flow_widths = [tb // 2, 13, tb, tb // 4, 3 * tb // 4, 1, tb // 2 - 1, 7, tb // 2, 24 if tb == 32 else 48]
+    sizes = rng.choice([0, 1, 2, 3, 63, 64, 65, 1000, 2047, 2048, 4097, 16386, 22531, full - 1, full], size=nseg,
+                       p=[.03, .03, .03, .03, .04, .04, .04, .1, .1, .1, .1, .1, .1, .08, .08])
+    counts = sizes.astype(np.uint32)
+    gaps = rng.integers(0, 5, size=nseg)
+    offs, run = [], 0
+    for c, g in zip(counts, gaps):
+        run += int(g)
+        offs.append(run)
+        run += int(c)
+    seg_vals = [make_values(rng, dtype, int(c), flow_widths[int(rng.integers(0, len(flow_widths)))]) for c in counts]
+    return counts, seg_vals, offs, np.array(offs, dtype=np.uint64)
+
+
 @pytest.mark.parametrize("dtype", [np.uint64, np.int64, np.uint32, np.int32, np.uint16, np.int16, np.uint8])
 def test_single_pass_encode_mixes_its_flows(adac, oracle, gpu_ctx, dtype):
     """The single-pass encode is persistent: one workgroup works through many segments and chooses per segment between
@@ -679,22 +700,8 @@ def test_single_pass_encode_mixes_its_flows(adac, oracle, gpu_ctx, dtype):
     (Every type is forced through the single-pass kernel here, also those adac_encode sends to the three kernels by
     default: profiles/r03_encode_forms.json, r03_encode_small_types.json.)"""
     dtype = np.dtype(dtype)
-    tb = 8 * dtype.itemsize
-    rng = np.random.default_rng(1234 + tb + (dtype.kind == "i"))
-    full = 262136 // dtype.itemsize
-    flow_widths = [tb // 2, 13, tb, tb // 4, 3 * tb // 4, 1, tb // 2 - 1, 7, tb // 2, 24 if tb == 32 else 48]
     nseg = 700
-    sizes = rng.choice([0, 1, 2, 3, 63, 64, 65, 1000, 2047, 2048, 4097, 16386, 22531, full - 1, full], size=nseg,
-                       p=[.03, .03, .03, .03, .04, .04, .04, .1, .1, .1, .1, .1, .1, .08, .08])
-    counts = sizes.astype(np.uint32)
-    gaps = rng.integers(0, 5, size=nseg)
-    offs, run = [], 0
-    for c, g in zip(counts, gaps):
-        run += int(g)
-        offs.append(run)
-        run += int(c)
-    seg_vals = [make_values(rng, dtype, int(c), flow_widths[int(rng.integers(0, len(flow_widths)))]) for c in counts]
-    val_offs = np.array(offs, dtype=np.uint64)
+    counts, seg_vals, offs, val_offs = mixed_flow_column(dtype, nseg)
     # knob 2 = the single-pass kernel whatever the type (by default adac_encode takes it for the 8-byte types only, and
     # for the 4-byte ones under first-come placement: profiles/r03_encode_forms.json)
     adac.set_tuning("single_pass_encode", 2)

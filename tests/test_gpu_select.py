@@ -159,21 +159,8 @@ def test_unpack_selected_materialises_only_the_selected_rows(adac, oracle, gpu_c
     """adac_unpack_selected: values + element ids of the rows a bitmap keeps, dense and in row order, for ragged
     segments at unaligned offsets, every width class, empty and full selections."""
     dtype = np.dtype(dtype)
-    tb = 8 * dtype.itemsize
-    rng = np.random.default_rng(70 + tb)
-    tile = adac.tile_values(dtype)
-    widths = sorted({1, 3, 5, 8, 13, 16, 27, 33, 50, tb} & set(range(1, tb + 1)))
-    counts = [int(rng.integers(1, 3 * tile)) if i % 2 else 2 * tile for i in range(len(widths))] + [1, 0, tile + 7]
-    segs = [make_values(rng, dtype, c, w) for c, w in zip(counts, widths + [2, 2, 4])]
-    counts = np.array(counts, dtype=np.uint32)
-    offs, run = [], 0
-    for i, c in enumerate(counts):
-        run += (0, 5, 64, 1)[i % 4]
-        offs.append(run)
-        run += int(c)
-    span = run
-    lay, d_words, _, _, _ = run_encode_decode(adac, oracle, gpu_ctx, dtype, counts, segs,
-                                              val_offs=np.array(offs, dtype=np.uint64))
+    rng = np.random.default_rng(70 + 8 * dtype.itemsize)
+    lay, d_words, counts, segs, offs, span = ragged_gather_column(adac, oracle, gpu_ctx, rng, dtype)
     total_rows = int(counts.sum())
     d_out = gpu_ctx.alloc(total_rows * dtype.itemsize + 64)
     d_ids = gpu_ctx.alloc(total_rows * 8 + 64)
@@ -192,6 +179,26 @@ def test_unpack_selected_materialises_only_the_selected_rows(adac, oracle, gpu_c
         assert np.array_equal(d_ids.download(np.uint64, max(n, 1))[:n], exp_ids), (dtype, density)
         n2 = lay.unpack_selected(d_words, d_bm, d_out)              # without ids
         assert n2 == n and np.array_equal(d_out.download(dtype, max(n, 1))[:n], exp_vals)
+
+
+def ragged_gather_column(adac, oracle, gpu_ctx, rng, dtype):
+    """Encoded (and oracle-checked) ragged segments at unaligned offsets, every width class:
+    (lay, d_words, counts, segs, offs, span)."""
+    tb = 8 * dtype.itemsize
+    tile = adac.tile_values(dtype)
+    widths = sorted({1, 3, 5, 8, 13, 16, 27, 33, 50, tb} & set(range(1, tb + 1)))
+    counts = [int(rng.integers(1, 3 * tile)) if i % 2 else 2 * tile for i in range(len(widths))] + [1, 0, tile + 7]
+    segs = [make_values(rng, dtype, c, w) for c, w in zip(counts, widths + [2, 2, 4])]
+    counts = np.array(counts, dtype=np.uint32)
+    offs, run = [], 0
+    for i, c in enumerate(counts):
+        run += (0, 5, 64, 1)[i % 4]
+        offs.append(run)
+        run += int(c)
+    span = run
+    lay, d_words, _, _, _ = run_encode_decode(adac, oracle, gpu_ctx, dtype, counts, segs,
+                                              val_offs=np.array(offs, dtype=np.uint64))
+    return lay, d_words, counts, segs, offs, span
 
 
 def test_filter_then_project_pipeline(adac, oracle, gpu_ctx):
@@ -234,6 +241,18 @@ def test_select_bitmap_words_shared_by_many_groups(adac, oracle, gpu_ctx, dtype)
     the last word may be the odd half of a 64-bit word."""
     dtype = np.dtype(dtype)
     rng = np.random.default_rng(4242 + dtype.itemsize)
+    lay, d_words, counts, segs, offs, span = many_groups_column(adac, oracle, gpu_ctx, rng, dtype)
+    info = np.iinfo(dtype)
+    big = segs[int(np.argmax(counts))]
+    probes = [(int(info.min), int(info.max)), (int(np.median(big)), int(info.max)), (int(info.min), int(np.median(big))),
+              (int(big[0]), int(big[0]))]
+    check_select(adac, gpu_ctx, lay, d_words, dtype, segs, offs, span, probes)
+    valid = rng.random(span) > 0.3
+    check_select(adac, gpu_ctx, lay, d_words, dtype, segs, offs, span, probes[:2], valid)
+
+
+def many_groups_column(adac, oracle, gpu_ctx, rng, dtype):
+    """Encoded (and oracle-checked) dense column with runs of tiny segments: (lay, d_words, counts, segs, offs, span)."""
     tile = adac.tile_values(dtype)
     counts = ([1] * 70 + [32, 32, 64, 1, 31, 33, 2, 30, 5] + [int(x) for x in rng.integers(1, 40, size=150)] +
               [2 * tile, 3, tile + 17, 1, 1, 1, 64, 5 * tile + 31, 7] + [int(x) for x in rng.integers(1, 6, size=200)] + [29])
@@ -243,13 +262,7 @@ def test_select_bitmap_words_shared_by_many_groups(adac, oracle, gpu_ctx, dtype)
     offs = np.concatenate([[0], np.cumsum(counts[:-1])]).astype(np.int64).tolist()
     span = int(counts.sum())
     assert lay.value_span == span
-    info = np.iinfo(dtype)
-    big = segs[int(np.argmax(counts))]
-    probes = [(int(info.min), int(info.max)), (int(np.median(big)), int(info.max)), (int(info.min), int(np.median(big))),
-              (int(big[0]), int(big[0]))]
-    check_select(adac, gpu_ctx, lay, d_words, dtype, segs, offs, span, probes)
-    valid = rng.random(span) > 0.3
-    check_select(adac, gpu_ctx, lay, d_words, dtype, segs, offs, span, probes[:2], valid)
+    return lay, d_words, counts, segs, offs, span
 
 
 @pytest.mark.parametrize("dtype", [np.uint64, np.int32, np.uint16, np.int8])
