@@ -183,8 +183,8 @@ def q6_packed(adac, n=59_986_052):
     """C3's Q6 shape on packed columns: WHERE l_shipdate in a year AND l_discount BETWEEN
     5 AND 7 AND l_quantity < 24 -> SUM(l_extendedprice), on four int32 columns of TPC-H SF10 size that share
     their segment layout.  Three filter scans chain their selection bitmaps, the fourth scan aggregates under the
-    final bitmap; nothing is decoded to HBM.  (Q6 proper sums price * discount — a two-column product is outside
-    this codec's single-column scans.)  Beside it: the materialising plan (decode the four columns, then filter)
+    final bitmap; nothing is decoded to HBM.  (Q6 proper sums price * discount: that is q6_product_packed below, on
+    adac_scan_sum_product.)  Beside it: the materialising plan (decode the four columns, then filter)
     counted at its decode cost alone."""
     ctx = adac.Context(0)
     rng = np.random.default_rng(1994)
@@ -356,6 +356,120 @@ def q1_packed(adac, n=59_986_052):
     return out
 
 
+def product_form_groups(descs_a, descs_b, type_size=4, signed=True):
+    """Which form of k_scan_product takes how many scan groups of `a` — product_fast_eligible (adac_sum_product.inl)
+    evaluated on the host descriptors, with the default grouping of ensure_scan_groups."""
+    tb = 8 * type_size
+    tmask, sbit = (1 << tb) - 1, (1 << (tb - 1)) if signed else 0
+    tile, per = 16384 // type_size, {8: 12, 4: 6, 2: 8, 1: 4}[type_size]
+
+    def frame_ok(d):
+        if (int(d["flags"]) & 1) and int(d["min"]) != 0xFFFFFFFFFFFFFFFF:
+            bmin = (int(d["min"]) & tmask) ^ sbit
+            return bmin + (1 << int(d["width"])) - 1 <= tmask
+        return sbit == 0
+
+    out = {"fast": 0, "generic": 0}
+    for da, db in zip(descs_a, descs_b):
+        ntiles = (int(da["count"]) + tile - 1) // tile
+        if ntiles == 0:
+            continue
+        wa, wb = int(da["width"]), int(db["width"])
+        fast = (4 <= wa <= 32 and 1 <= wb <= 32 and int(da["count"]) * wa < 2 ** 31 and int(db["count"]) * wb < 2 ** 31
+                and frame_ok(da) and frame_ok(db))
+        out["fast" if fast else "generic"] += (ntiles + per - 1) // per
+    return out
+
+
+def q6_product_packed(adac, n=59_986_052):
+    """TPC-H Q6 proper on packed columns: the four int32 columns and the three chained selects of q6_packed, then
+    SUM(l_extendedprice * l_discount) under the final bitmap with adac_scan_sum_product — no value is materialised.
+    Beside it, in the same process: what a caller paid before (adac_unpack of the two columns, after which the
+    multiplication is still to do) and the two masked single-column SUMs, a lower bound for any walk of both columns."""
+    ctx = adac.Context(0)
+    rng = np.random.default_rng(1994)
+    cols = {"l_shipdate": rng.integers(8036, 10562, size=n).astype(np.int32),
+            "l_discount": rng.integers(0, 11, size=n).astype(np.int32),
+            "l_quantity": rng.integers(1, 51, size=n).astype(np.int32),
+            "l_extendedprice": rng.integers(90_000, 10_495_000, size=n).astype(np.int32)}
+    counts = adac.appender_segment_counts(n, 4)
+    enc, packed_bytes = {}, {}
+    for name, v in cols.items():
+        lay = adac.Layout(ctx, np.int32, counts)
+        d_vals = ctx.upload(v)
+        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
+        lay.encode(d_vals, d_words)
+        ctx.sync()
+        descs = lay.get_descs()
+        packed_bytes[name] = int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
+        enc[name] = (lay, d_words, sorted(set(descs["width"].tolist())), descs)
+        del d_vals
+    nw = (n + 63) // 64
+    bm = [ctx.alloc(nw * 8 + 8) for _ in range(3)]
+    d_cnt = ctx.alloc(len(counts) * 8)
+    d_sum = ctx.alloc(len(counts) * 8)
+    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
+    price, disc = enc["l_extendedprice"], enc["l_discount"]
+
+    def selects():
+        lay, w = enc["l_shipdate"][:2]
+        lay.scan_select_between(w, 8766, 9130, bm[0], d_cnt)              # 1994-01-01 .. 1994-12-31
+        lay, w = enc["l_discount"][:2]
+        lay.scan_select_between(w, 5, 7, bm[1], d_cnt, bm[0])
+        lay, w = enc["l_quantity"][:2]
+        lay.scan_select_between(w, int_min, 23, bm[2], d_cnt, bm[1])
+
+    def product():
+        price[0].scan_sum_product(price[1], disc[0], disc[1], d_sum, bm[2])
+
+    def q6():
+        selects()
+        product()
+
+    q6()
+    ctx.sync()
+    m = ((cols["l_shipdate"] >= 8766) & (cols["l_shipdate"] <= 9130) & (cols["l_discount"] >= 5) &
+         (cols["l_discount"] <= 7) & (cols["l_quantity"] < 24))
+    got = int(d_sum.download(np.uint64, len(counts)).sum(dtype=np.uint64))
+    assert got == int((cols["l_extendedprice"][m].astype(np.int64) * cols["l_discount"][m]).sum()), "Q6 parity"
+    assert int(d_cnt.download(np.uint64, len(counts)).sum()) == int(m.sum())
+    reps = 20
+    d_out = ctx.alloc(n * 4 + 64)
+
+    def unpack_two():
+        price[0].unpack(price[1], d_out)
+        disc[0].unpack(disc[1], d_out)
+
+    def two_sums():
+        price[0].scan_sum(price[1], d_sum, bm[2])
+        disc[0].scan_sum(disc[1], d_sum, bm[2])
+
+    ms = {}
+    for name, fn in (("q6_product_on_packed", q6), ("select_chain", selects), ("sum_product_masked", product),
+                     ("unpack_price_and_discount", unpack_two), ("two_masked_scan_sums", two_sums),
+                     ("sum_product_unmasked", lambda: price[0].scan_sum_product(price[1], disc[0], disc[1], d_sum))):
+        fn()
+        ctx.timer_start()
+        for _ in range(reps):
+            fn()
+        ms[name] = ctx.timer_stop() / reps
+    product()  # leave the masked result behind and check it once more after the timed loops
+    got = int(d_sum.download(np.uint64, len(counts)).sum(dtype=np.uint64))
+    assert got == int((cols["l_extendedprice"][m].astype(np.int64) * cols["l_discount"][m]).sum()), "Q6 parity (after timing)"
+    two = packed_bytes["l_extendedprice"] + packed_bytes["l_discount"]
+    out = {"rows": n, "selected_rows": int(m.sum()), "widths": {k: v[2] for k, v in enc.items()},
+           "packed_bytes": packed_bytes, "step_ms": ms,
+           "sum_product_packed_read_GBps": (two + n / 8) / (ms["sum_product_masked"] * 1e-3) / 1e9,
+           "unpack_two_columns_total_GBps": (two + 2 * n * 4) / (ms["unpack_price_and_discount"] * 1e-3) / 1e9,
+           "product_faster_than_unpack": ms["sum_product_masked"] < ms["unpack_price_and_discount"],
+           "groups_by_form": product_form_groups(price[3], disc[3]),
+           "note": "sum_product_masked = adac_scan_sum_product(l_extendedprice, l_discount) under the final bitmap of the "
+                   "three chained selects; unpack_price_and_discount is what a caller paid before it could start to "
+                   "multiply; two_masked_scan_sums is a lower bound for any walk of the two columns"}
+    ctx.close()
+    return out
+
+
 def c1_lookups(adac, wl, n=10_000_000, nlookups=10_000):
     """C1 (benchmark/micro/succinct/zipf_distribution.cpp:13-48): t1(i UINTEGER) with i = 0..N-1, compacted, then
     `SELECT i FROM t1 WHERE i == k` for Zipf(N, 1.0) keys (mt19937, seed 42).  Each look-up is one fused
@@ -400,7 +514,8 @@ def main():
     wl = importlib.import_module(PKG + ".workload")
     only = sys.argv[1:]
     jobs = {"plugin_scan": lambda: plugin_scan(host, lay), "adaptive": lambda: adaptive(host, wl),
-            "bitpacking_scan": lambda: bitpacking_scan(adac), "q6_packed": lambda: q6_packed(adac), "q1_packed": lambda: q1_packed(adac),
+            "bitpacking_scan": lambda: bitpacking_scan(adac), "q6_packed": lambda: q6_packed(adac),
+            "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "c1_lookups": lambda: c1_lookups(adac, wl)}
     res = {k: f() for k, f in jobs.items() if not only or k in only}
     print(json.dumps(res))

@@ -163,6 +163,7 @@ SIGNATURES = {
     "adac_event_destroy": (None, [_vp]),
     "adac_scan_sum": (_int, [_vp, _vp, _vp]),
     "adac_scan_group_sum": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "adac_scan_sum_product": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "adac_scan_count_eq": (_int, [_vp, _vp, _u64, _vp]),
     "adac_scan_count_between": (_int, [_vp, _vp, _u64, _u64, _vp]),
     "adac_scan_sum_valid": (_int, [_vp, _vp, _vp, _vp]),
@@ -529,6 +530,12 @@ class Layout:
         """SUM(self) and COUNT(*) GROUP BY `keys` (a Layout over the same rows); ngroups + 1 results each."""
         _check(lib().adac_scan_group_sum(self._h, _dptr(d_words), keys._h, _dptr(d_key_words), int(ngroups),
                                          _dptr(d_sums), _dptr(d_counts)), "adac_scan_group_sum")
+
+    def scan_sum_product(self, d_words, other, d_other_words, d_sums, d_validity=None):
+        """SUM(self * other) per segment (`other`: a Layout over the same rows; each value widened by its own type's
+        signedness, mod 2^64) over the rows whose bit is set in d_validity, a mask in THIS layout's element space."""
+        _check(lib().adac_scan_sum_product(self._h, _dptr(d_words), other._h, _dptr(d_other_words), _dptr(d_validity),
+                                           _dptr(d_sums)), "adac_scan_sum_product")
 
     def scan_count_between(self, d_words, lo, hi, d_counts, d_validity=None):
         """lo / hi: bit patterns of the column type (use int(np.array([v], dtype).view(unsigned)[0]) for signed)."""

@@ -1087,6 +1087,24 @@ extern "C" adac_status adac_scan_sum_valid(adac_layout *l, const uint64_t *d_wor
 	return ADAC_OK;
 }
 
+// SUM(a * b) per segment over two packed columns of one table under a selection bitmap (Q6's aggregate)
+extern "C" adac_status adac_scan_sum_product(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
+                                             const uint64_t *d_b_words, const uint64_t *d_validity, uint64_t *d_sums) {
+	if (!a || !b || a->ctx != b->ctx) return ADAC_ERR_INVALID_ARGUMENT;
+	if (a->counts != b->counts) return ADAC_ERR_INVALID_ARGUMENT; // the same rows, segment by segment
+	if (a->nseg && !d_sums) return ADAC_ERR_INVALID_ARGUMENT;
+	if (a->total_values && (!d_a_words || !d_b_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (!aligned16(d_a_words) || !aligned16(d_b_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	ADAC_HIP(hipSetDevice(a->ctx->device));
+	adac_status gst = ensure_scan_groups(a);
+	if (gst != ADAC_OK) return gst;
+	// every wave adds its part: the sums start from zero (this also writes the segments without rows)
+	if (a->nseg) ADAC_HIP(hipMemsetAsync(d_sums, 0, a->nseg * sizeof(uint64_t), a->ctx->stream));
+	ADAC_HIP(adac::launch_scan_sum_product(a->ctx->stream, a->type_size, a->is_signed, b->type_size, b->is_signed,
+	                                       a->d_groups, a->ngroups, d_a_words, b->d_descs, d_b_words, d_validity, d_sums));
+	return ADAC_OK;
+}
+
 // SUM(value), COUNT(*) GROUP BY key over two packed columns of one table (Q1's shape, TPCH_runtime.txt:2-6)
 extern "C" adac_status adac_scan_group_sum(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
                                            const uint64_t *d_key_words, uint32_t ngroups, uint64_t *d_sums,

@@ -148,6 +148,11 @@ hipError_t launch_group_sum(hipStream_t s, uint32_t v_type_size, bool v_signed, 
                             const ScanGroup *d_vgroups, uint64_t nvgroups, const uint64_t *d_vwords,
                             const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups, void *d_partial,
                             uint32_t call_parity, uint64_t *d_sums, uint64_t *d_counts);
+// SUM(a * b) over two packed columns of one table under a selection bitmap (adac_sum_product.inl)
+hipError_t launch_scan_sum_product(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
+                                   const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,
+                                   const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
+                                   const uint64_t *d_validity, uint64_t *d_sums);
 hipError_t launch_encode_1p(hipStream_t s, uint32_t type_size, bool sign_extend, uint64_t null_bits, int rule,
                             int pad_to_byte, adac_segment_desc *d_descs, uint64_t nseg, const void *d_vals,
                             const uint64_t *d_validity, uint64_t *d_minmax, void *d_scan_state, uint64_t *d_words);

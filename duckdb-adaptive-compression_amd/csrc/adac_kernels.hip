@@ -2005,6 +2005,7 @@ hipError_t dispatch_size(uint32_t type_size, F &&f) {
 #include "adac_block_image.inl"
 #include "adac_encode_1p.inl"
 #include "adac_group_sum.inl"
+#include "adac_sum_product.inl"
 
 } // namespace
 
@@ -2138,6 +2139,29 @@ hipError_t launch_group_sum(hipStream_t s, uint32_t v_type_size, bool v_signed, 
 	}
 	hipLaunchKernelGGL(k_group_final, dim3(nbins), dim3(kWorkgroup), 0, s, partial, nwg_rw, nwg, nbins, d_sums, d_counts,
 	                   static_cast<const unsigned long long *>(fallback), next_fallback, rw ? 1 : 0);
+	return hipGetLastError();
+}
+
+// SUM(a * b) per segment under a selection bitmap (adac_sum_product.inl): one workgroup per scan group of `a`; the
+// caller has cleared d_sums
+hipError_t launch_scan_sum_product(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
+                                   const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,
+                                   const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
+                                   const uint64_t *d_validity, uint64_t *d_sums) {
+	if (ngroups == 0) return hipSuccess;
+	ProductTypes ty;
+	ty.a_tmask = a_type_size >= 8 ? ~0ull : ((1ull << (8 * a_type_size)) - 1ull);
+	ty.a_sbit = a_signed ? (1ull << (8 * a_type_size - 1)) : 0ull;
+	ty.b_tmask = b_type_size >= 8 ? ~0ull : ((1ull << (8 * b_type_size)) - 1ull);
+	ty.b_sbit = b_signed ? (1ull << (8 * b_type_size - 1)) : 0ull;
+	unsigned long long *sums = reinterpret_cast<unsigned long long *>(d_sums);
+	if (d_validity) {
+		hipLaunchKernelGGL(k_scan_product<true>, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_agroups, d_awords,
+		                   d_bdescs, d_bwords, ty, d_validity, sums);
+	} else {
+		hipLaunchKernelGGL(k_scan_product<false>, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_agroups, d_awords,
+		                   d_bdescs, d_bwords, ty, d_validity, sums);
+	}
 	return hipGetLastError();
 }
 

@@ -341,6 +341,18 @@ adac_status adac_scan_count_between(adac_layout *l, const uint64_t *d_words, uin
 adac_status adac_scan_group_sum(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
                                 const uint64_t *d_key_words, uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts);
 
+/* Product aggregate over TWO packed columns of one table — TPC-H Q6's `SUM(l_extendedprice * l_discount) WHERE ...`
+ * without materialising either column.  `a` and `b` are layouts on the same context with the same row count per
+ * segment (types, widths, placements and encode rules may differ; a == b with the same words gives the sum of squares).
+ * d_sums[seg] = sum over the rows of segment seg whose bit is set in d_validity (NULL = every row) of
+ * widen(a) * widen(b), mod 2^64.  Each value is widened to 64 bits by its own column's signedness
+ * (adac_scan_sum's rule).  The product and the sum are taken mod 2^64.
+ * d_validity is indexed in a's element space (a's val_off + row), so a bitmap adac_scan_select_between wrote on a
+ * layout with a's value offsets can be passed straight in; b's value offsets play no part.  A segment without rows
+ * gets 0; d_sums is fully written by the call. */
+adac_status adac_scan_sum_product(adac_layout *a, const uint64_t *d_a_words, adac_layout *b, const uint64_t *d_b_words,
+                                  const uint64_t *d_validity, uint64_t *d_sums);
+
 /* The same two scans with a DuckDB validity mask over the element index space (bit e of word e/64 set = row e
  * valid, as for adac_analyze): NULL rows take no part in the aggregate — what SUM / COUNT over a nullable
  * column mean.  d_validity == NULL is the unmasked scan. */
