@@ -375,7 +375,8 @@ def test_argument_errors(adac, gpu_ctx):
 
 def test_large_single_segments(adac, oracle, gpu_ctx):
     """Segments far larger than DuckDB's 256 KiB blocks (the C ABI does not assume them): thousands of tiles per
-    segment, bit offsets beyond 2^31 inside one segment, every kernel."""
+    segment, every kernel.  The largest is 5 000 003 rows at 47 bits, about 2.35e8 bits: every bit offset stays below
+    2^31.  Segments at and past 2^31 and 2^32 bits are in tests/test_gpu_big_segments.py."""
     rng = np.random.default_rng(31)
     for dtype, n, bits in ((np.uint32, 9_000_001, 21), (np.uint64, 5_000_003, 47), (np.uint8, 20_000_000, 5)):
         dtype = np.dtype(dtype)
