@@ -720,9 +720,8 @@ extern "C" adac_status adac_zonemap(adac_layout *l, const void *d_vals, const ui
 	if (!l || (!d_vals && l->total_values) || (l->nseg && !zonemap)) return ADAC_ERR_INVALID_ARGUMENT;
 	if (!aligned16(d_vals)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
-	const uint32_t bits = 8 * l->type_size;
-	const uint64_t umask = bits >= 64 ? ~0ull : ((1ull << bits) - 1ull);
-	const uint64_t sbit = l->is_signed ? (1ull << (bits - 1)) : 0ull;
+	const uint64_t umask = adac::type_mask(l->type_size);
+	const uint64_t sbit = adac::type_sign_bit(l->type_size, l->is_signed);
 	ADAC_HIP(adac::launch_minmax_init(l->ctx->stream, l->d_minmax, l->nseg));
 	// the kernel's `null_bits` argument carries the sign bit: min/max are taken over bits(v) ^ signbit
 	ADAC_HIP(adac::launch_analyze(l->ctx->stream, l->type_size, false, sbit, ADAC_RULE_ZONEMAP, l->d_descs, l->d_tiles,
@@ -1074,7 +1073,7 @@ extern "C" adac_status adac_scan_sum_valid(adac_layout *l, const uint64_t *d_wor
 	if (!l || (l->nseg && !d_sums) || (l->total_values && !d_words)) return ADAC_ERR_INVALID_ARGUMENT;
 	if (!aligned16(d_words)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
-	const uint64_t sbit = l->is_signed ? (1ull << (8 * l->type_size - 1)) : 0ull;
+	const uint64_t sbit = adac::type_sign_bit(l->type_size, l->is_signed);
 	adac::ScanGroupList gl;
 	adac_status gst = scan_group_list(l, &gl);
 	if (gst != ADAC_OK) return gst;
@@ -1143,9 +1142,8 @@ static adac_status scan_range(adac_layout *l, const uint64_t *d_words, const uin
 	if (!aligned16(d_words)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	// order-preserving map of T onto unsigned numbers: flip the sign bit of the signed types
-	const uint32_t bits = 8 * l->type_size;
-	const uint64_t umask = bits >= 64 ? ~0ull : ((1ull << bits) - 1ull);
-	const uint64_t sbit = l->is_signed ? (1ull << (bits - 1)) : 0ull;
+	const uint64_t umask = adac::type_mask(l->type_size);
+	const uint64_t sbit = adac::type_sign_bit(l->type_size, l->is_signed);
 	const uint64_t blo = (lo & umask) ^ sbit, bhi = (hi & umask) ^ sbit;
 	// The scan writes every bitmap word that lies inside a group whole (zero words included).  With the segments back
 	// to back in the value space the words two groups share are all that is left: every group leaves its bits of

@@ -88,16 +88,10 @@ __device__ __forceinline__ GroupRwPlan group_rw_eligible(const adac_segment_desc
 	if (ngroups + 1u > kGroupPrivateBins || ty.wide_only) return p;
 	const uint32_t wv = vd.width, wk = kd.width;
 	if (wv < 4u || wv > 32u || wk > 8u || (uint64_t)vd.count * wv >= (1ull << 31)) return p;
-	// value column: value64 = field + vadd without leaving T's range (seg_kind's SEG_LINEAR), or the field itself
+	// value column: value64 = field + vadd without leaving T's range (seg_kind's SEG_LINEAR: an unsigned T's stored
+	// values cannot wrap, whatever the largest field would give, so it takes vadd and goes on), or the field itself
 	if ((vd.flags & ADAC_SEG_PACKED) && vd.min != ADAC_NO_MIN) {
-		const uint64_t tmin = vd.min & ty.v_tmask;
-		if (ty.v_sbit) {
-			const uint64_t bmin = tmin ^ ty.v_sbit, top = bmin + ((1ull << wv) - 1ull);
-			if (top < bmin || top > ty.v_tmask) return p; // wraps T's sign boundary
-			p.vadd = (tmin ^ ty.v_sbit) - ty.v_sbit;
-		} else {
-			p.vadd = tmin;
-		}
+		if (!frame_fits_type(vd, ty.v_tmask, ty.v_sbit, p.vadd) && ty.v_sbit) return p; // wraps T's sign boundary
 	} else if (ty.v_sbit) {
 		return p; // raw slots of a signed type: the field is not the widened value
 	}
@@ -325,7 +319,7 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 // k_group_sum above reads every field of both columns out of a staged LDS image: four dword reads and two LDS adds per
 // row, each stage a chain of global -> LDS -> register round trips; 62 % of its wave cycles wait and it reaches 10 - 20 %
 // of the HBM roofline (profiles/r02_q1_packed.json).  Here
-//   * a lane owns whole 16-byte chunks of the VALUE stream (scan_run_w's form: one coalesced global_load_dwordx4 + the
+//   * a lane owns whole 16-byte chunks of the VALUE stream (adac_chunk_walk.inl: one coalesced global_load_dwordx4 + the
 //     next dword, the next chunk prefetched before this one is decoded, every field at a compile-time position);
 //   * the KEYS of the rows a round of chunks covers (at most 4096 rows) are decoded once, by the lanes together, into
 //     a BYTE per row in LDS: a lane takes a block of 32 rows = exactly WK dwords of the key stream (key widths 1..8),
@@ -419,36 +413,34 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
                                               uint32_t wk, const uint4 *__restrict__ seg16,
                                               const uint32_t *__restrict__ kw32, uint32_t k_last_dword, uint32_t ngroups,
                                               uint8_t *keys, unsigned long long *wbins) {
-	constexpr int MAXV = (128 + W - 1) / W;
+	constexpr int MAXV = ChunkWindow<W>::MAXV;
 	constexpr int KD = (MAXV + 3 + 3) / 4;                         // dwords holding MAXV bytes from any byte offset
 	constexpr uint32_t LANES = (kGroupRwWaveRows * W / 128) < 64u ? (kGroupRwWaveRows * W / 128) : 64u; // chunks per round
 	constexpr uint32_t PASSES = ((LANES * 128u / W + 8u + 7u) / 8u + 63u) / 64u; // staged: 8-row blocks per round / 64 lanes
 	// r0 is a multiple of 128 rows: its bits start a chunk
-	const uint32_t c0 = (uint32_t)(((uint64_t)r0 * W) >> 7);
-	const uint32_t c1 = (uint32_t)(((uint64_t)r1 * W + 127) >> 7);
-	const uint32_t clast = (uint32_t)(((uint64_t)count * W + 127) >> 7) - 1;
+	const ChunkRange<W> run(r0, r1, count);
+	const uint32_t c0 = run.c0, c1 = run.c1;
 	const uint32_t lane = threadIdx.x & 63u;
 	const bool walker = lane < LANES;
 	const uint32_t kadd4 = plan.keys_overflow ? 0u : plan.kadd_byte * 0x01010101u;
 	unsigned char *const my_bins = reinterpret_cast<unsigned char *>(wbins + (lane & (kGroupRwCopies - 1u)));
 	unsigned char *const my_bins32 = reinterpret_cast<unsigned char *>(reinterpret_cast<uint32_t *>(wbins) + (lane & (kGroupRwCopies - 1u)));
 	uint32_t L = c0 + lane;
-	const uint32_t Lc = L < clast ? L : clast;
-	uint4 q = seg16[Lc];
-	uint32_t e = reinterpret_cast<const uint32_t *>(seg16 + (Lc < clast ? Lc + 1 : clast))[0];
+	uint4 q;
+	uint32_t e;
+	run.load(seg16, L, q, e);
 	// DIRECT: the two dwords of the key stream holding the keys of the rows that start in chunk Lx
 	auto direct_keys = [&](uint32_t Lx) {
-		const uint32_t i0 = (128u * Lx + (W - 1)) / W;
-		uint32_t dw = (i0 * wk) >> 5;
+		uint32_t dw = (chunk_first_row<W>(Lx) * wk) >> 5;
 		dw = dw < k_last_dword ? dw : k_last_dword; // (chunks past the run: any data will do)
 		return make_uint2(kw32[dw], kw32[dw + 1]);   // dw + 1 <= last data dword + 1: inside the padding word
 	};
 	// staged: the key rows of the round that starts at chunk `rc` = [first row starting in chunk rc, first row starting
 	// in chunk rc + LANES), from the 8-row block the round starts in
 	auto round_keys = [&](uint32_t rc, uint32_t &kb0, uint32_t &nblocks) {
-		const uint32_t rows_lo = (128u * rc + (W - 1)) / W;
+		const uint32_t rows_lo = chunk_first_row<W>(rc);
 		kb0 = rows_lo & ~7u;
-		uint32_t rows_hi = (128u * (rc + LANES) + (W - 1)) / W;
+		uint32_t rows_hi = chunk_first_row<W>(rc + LANES);
 		rows_hi = rows_hi < r1 ? rows_hi : r1;
 		nblocks = rows_hi > kb0 ? (rows_hi - kb0 + 7u) >> 3 : 0u;
 	};
@@ -456,7 +448,7 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 	uint32_t kb0 = 0, nblocks = 0;
 	uint32_t kd[PASSES][3], ksh[PASSES];
 	if (DIRECT) {
-		kq = direct_keys(Lc);
+		kq = direct_keys(run.clamp(L));
 	} else { // prologue: the first round's key bytes
 		round_keys(c0, kb0, nblocks);
 #pragma unroll
@@ -470,38 +462,31 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 	}
 	for (uint32_t round0 = c0; round0 < c1; round0 += LANES, L += LANES) { // uniform trip count
 		// requested before this round is walked: the next chunk of the value stream and its keys
-		const uint32_t Lp = L + LANES < clast ? L + LANES : clast;
-		const uint4 qn = seg16[Lp];
-		const uint32_t en = reinterpret_cast<const uint32_t *>(seg16 + (Lp < clast ? Lp + 1 : clast))[0];
+		uint4 qn;
+		uint32_t en;
+		run.load(seg16, L + LANES, qn, en);
 		uint2 kqn = make_uint2(0u, 0u);
 		uint32_t kb0n = 0, nblocksn = 0;
 		if (DIRECT) {
-			kqn = direct_keys(Lp);
+			kqn = direct_keys(run.clamp(L + LANES));
 		} else {
 			round_keys(round0 + LANES, kb0n, nblocksn);
 #pragma unroll
 			for (uint32_t p = 0; p < PASSES; p++) group_rw_key_load(kw32, (kb0n >> 3) + lane + 64u * p, wk, k_last_dword, kd[p], ksh[p]);
 		}
 		if (walker && L < c1) {
-			const uint32_t i0 = (128u * L + (W - 1)) / W; // first row starting in this chunk
-			const uint32_t o0 = i0 * W - 128u * L;
-			uint32_t nrm[5];
-			nrm[0] = __builtin_amdgcn_alignbit(q.y, q.x, o0);
-			nrm[1] = __builtin_amdgcn_alignbit(q.z, q.y, o0);
-			nrm[2] = __builtin_amdgcn_alignbit(q.w, q.z, o0);
-			nrm[3] = __builtin_amdgcn_alignbit(e, q.w, o0);
-			nrm[4] = e >> o0;
-			// MAXV - 1 rows start in every chunk, the MAXV-th one if its first bit still lies inside
-			const bool last_starts = 128 % W == 0 || o0 + (uint32_t)(MAXV - 1) * W < 128u;
+			const ChunkWindow<W> cw(q, e, L, r1);
+			// MAXV - 1 rows start in every chunk, the MAXV-th one if its first bit still lies inside.  (cw.last_starts() /
+			// cw.starting say the same; spelled from them this kernel came out with 8 bytes of scratch per lane.)
+			const bool last_starts = 128 % W == 0 || cw.o0 + (uint32_t)(MAXV - 1) * W < 128u;
 			const uint32_t starting = (uint32_t)(MAXV - 1) + (last_starts ? 1u : 0u);
-			const uint32_t lim = r1 > i0 ? r1 - i0 : 0u;
 			uint32_t kwin = 0;       // DIRECT: the keys of rows i0 .. from bit 0
 			uint32_t kn[KD];         // staged: their bytes
 			if (DIRECT) {
-				kwin = __builtin_amdgcn_alignbit(kq.y, kq.x, (i0 * wk) & 31u);
+				kwin = __builtin_amdgcn_alignbit(kq.y, kq.x, (cw.i0 * wk) & 31u);
 			} else {
 				// the key bytes of rows [i0, i0 + MAXV): dword reads from the byte offset rounded down, one v_alignbyte each
-				const uint32_t kofs = i0 - kb0;
+				const uint32_t kofs = cw.i0 - kb0;
 				const uint32_t *k32 = reinterpret_cast<const uint32_t *>(keys) + (kofs >> 2);
 				uint32_t raw[KD + 1];
 #pragma unroll
@@ -519,20 +504,20 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 				const uint32_t bin = key < ngroups ? key : ngroups;
 				if (kGroupRwNarrow<W>) { // fields of at most 8 bits: rows << 20 | sum fits 32 bits, a ds_add_u32 is half the LDS work
 					uint32_t *slot = reinterpret_cast<uint32_t *>(my_bins32 + bin * (kGroupRwCopies * 4u));
-					atomicAdd(slot, (1u << kGroupRwNarrowShift) | field_of<W>(nrm, j));
+					atomicAdd(slot, (1u << kGroupRwNarrowShift) | field_of<W>(cw.nrm, j));
 				} else {
 					unsigned long long *slot = reinterpret_cast<unsigned long long *>(my_bins + bin * (kGroupRwCopies * 8u));
-					atomicAdd(slot, (1ull << kGroupRwCountShift) | (unsigned long long)field_of<W>(nrm, j)); // ds_add_u64, no return
+					atomicAdd(slot, (1ull << kGroupRwCountShift) | (unsigned long long)field_of<W>(cw.nrm, j)); // ds_add_u64, no return
 				}
 			};
-			if (starting <= lim) { // every row that starts in the chunk belongs to the quarter: no per-row test
+			if (starting <= cw.lim) { // every row that starts in the chunk belongs to the quarter: no per-row test
 #pragma unroll
 				for (int j = 0; j < MAXV - 1; j++) add_row(j);
 				if (last_starts) add_row(MAXV - 1);
 			} else { // the quarter ends inside this chunk
 #pragma unroll
 				for (int j = 0; j < MAXV; j++) {
-					if ((uint32_t)j < lim) add_row(j);
+					if ((uint32_t)j < cw.lim) add_row(j);
 				}
 			}
 		}
@@ -614,23 +599,13 @@ __global__ __launch_bounds__(kWorkgroup, 7) void k_group_sum_rw(const ScanGroup 
 		const uint32_t k_last = (uint32_t)(((uint64_t)kd.count * wk + 31) >> 5) - 1u;
 		const uint32_t maxv = (128u + g.d.width - 1u) / g.d.width;
 		if (maxv * wk <= 32u) { // uniform: the keys of a chunk's rows fit one dword
-			switch (g.d.width) {
-#define ADAC_W(N) case N: group_rw_walk<N, true>(r0, r1, g.d.count, plan, wk, seg16, kw32, k_last, ngroups, keys[wave], bins[wave]); break;
-				ADAC_W(4) ADAC_W(5) ADAC_W(6) ADAC_W(7) ADAC_W(8) ADAC_W(9) ADAC_W(10) ADAC_W(11) ADAC_W(12) ADAC_W(13)
-				ADAC_W(14) ADAC_W(15) ADAC_W(16) ADAC_W(17) ADAC_W(18) ADAC_W(19) ADAC_W(20) ADAC_W(21) ADAC_W(22)
-				ADAC_W(23) ADAC_W(24) ADAC_W(25) ADAC_W(26) ADAC_W(27) ADAC_W(28) ADAC_W(29) ADAC_W(30) ADAC_W(31) ADAC_W(32)
-#undef ADAC_W
-			default: break;
-			}
+			dispatch_width_4_32(g.d.width, [&](auto wc) __attribute__((always_inline)) {
+				group_rw_walk<decltype(wc)::value, true>(r0, r1, g.d.count, plan, wk, seg16, kw32, k_last, ngroups, keys[wave], bins[wave]);
+			});
 		} else {
-			switch (g.d.width) {
-#define ADAC_W(N) case N: group_rw_walk<N, false>(r0, r1, g.d.count, plan, wk, seg16, kw32, k_last, ngroups, keys[wave], bins[wave]); break;
-				ADAC_W(4) ADAC_W(5) ADAC_W(6) ADAC_W(7) ADAC_W(8) ADAC_W(9) ADAC_W(10) ADAC_W(11) ADAC_W(12) ADAC_W(13)
-				ADAC_W(14) ADAC_W(15) ADAC_W(16) ADAC_W(17) ADAC_W(18) ADAC_W(19) ADAC_W(20) ADAC_W(21) ADAC_W(22)
-				ADAC_W(23) ADAC_W(24) ADAC_W(25) ADAC_W(26) ADAC_W(27) ADAC_W(28) ADAC_W(29) ADAC_W(30) ADAC_W(31) ADAC_W(32)
-#undef ADAC_W
-			default: break;
-			}
+			dispatch_width_4_32(g.d.width, [&](auto wc) __attribute__((always_inline)) {
+				group_rw_walk<decltype(wc)::value, false>(r0, r1, g.d.count, plan, wk, seg16, kw32, k_last, ngroups, keys[wave], bins[wave]);
+			});
 		}
 		group_rw_fold(bins[wave], tot[wave], plan.vadd, g.d.width <= 8u);
 	}

@@ -117,6 +117,13 @@ extern Tuning g_tuning;
 inline uint32_t tile_values(uint32_t type_size) {
 	return kTileBytes / type_size;
 }
+// all-ones mask of a type's width, and its sign bit (0 for the unsigned types)
+inline uint64_t type_mask(uint32_t type_size) {
+	return type_size >= 8 ? ~0ull : (1ull << (8 * type_size)) - 1ull;
+}
+inline uint64_t type_sign_bit(uint32_t type_size, bool is_signed) {
+	return is_signed ? 1ull << (8 * type_size - 1) : 0ull;
+}
 
 // type_size in {1,2,4,8}; every launcher returns the hipError_t of the launch.
 hipError_t launch_analyze(hipStream_t s, uint32_t type_size, bool sign_extend, uint64_t null_bits, int rule,

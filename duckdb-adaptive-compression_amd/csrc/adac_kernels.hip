@@ -488,6 +488,8 @@ __device__ __forceinline__ uint32_t field_of(const uint32_t (&nrm)[5], int j) {
 	return __builtin_amdgcn_alignbit(nrm[d + 1], nrm[d], sh) & mask;
 }
 
+#include "adac_chunk_walk.inl"
+
 __device__ __forceinline__ bool scan_width_is_narrow(uint32_t w) { return w == 2u || w == 3u; }
 
 // A workgroup's 64-byte work item through the scalar unit (see load_desc; measured: the vector loads of width / flags
@@ -725,6 +727,16 @@ __device__ __forceinline__ SegKind seg_kind(const adac_segment_desc &d, uint64_t
 	return (top >= bmin && top <= (uint64_t)(U)~(U)0) ? SEG_LINEAR : SEG_WRAPS;
 }
 
+// seg_kind's range test with the type at run time (its all-ones mask and sign bit instead of U), made for the unsigned
+// types too: does min + f stay inside T's range for EVERY width-bit field f of a segment packed with a frame of
+// reference?  `add`: min widened to 64 bits by T's signedness; written whatever the answer (group_rw_eligible keeps it
+// for an unsigned T whose largest field would leave the range).
+__device__ __forceinline__ bool frame_fits_type(const adac_segment_desc &d, uint64_t tmask, uint64_t sbit, uint64_t &add) {
+	const uint64_t bmin = (d.min & tmask) ^ sbit, top = bmin + mask64(d.width);
+	add = bmin - sbit;
+	return top >= bmin && top <= tmask;
+}
+
 // min widened to 64 bits according to T's signedness: with it, value64 = f + add64 on a linear segment
 template <typename U>
 __device__ __forceinline__ uint64_t widened_min(const adac_segment_desc &d, uint64_t sbit) {
@@ -757,7 +769,7 @@ __device__ __forceinline__ FieldRange field_range(const RangePred &p, const adac
 
 template <int W>
 struct ChunkSum {
-	static constexpr int MAXV = (128 + W - 1) / W;
+	static constexpr int MAXV = ChunkWindow<W>::MAXV;
 	static constexpr bool kFields32 = ((uint64_t)MAXV << W) <= 0xffffffffull; // MAXV fields fit a u32 sum
 	uint32_t p32 = 0;
 	uint64_t p64 = 0;
@@ -814,13 +826,11 @@ __device__ __forceinline__ void scan_run_w(const uint4 *__restrict__ seg16, uint
                                            const adac_segment_desc &d, const RangePred &pred, bool linear,
                                            const uint64_t *__restrict__ validity, const SelOut &sel_out,
                                            uint64_t &acc) {
-	constexpr int MAXV = (128 + W - 1) / W;
+	constexpr int MAXV = ChunkWindow<W>::MAXV;
 	constexpr uint32_t mask = W >= 32 ? 0xffffffffu : ((1u << W) - 1u);
 	constexpr bool PRED = OP == 1 || OP == 3;
 	constexpr uint32_t STRIDE = (uint32_t)kWorkgroup;
-	const uint32_t c0 = (uint32_t)(((uint64_t)r0 * W) >> 7);       // r0 is a multiple of 128 rows
-	const uint32_t c1 = (uint32_t)(((uint64_t)r1 * W + 127) >> 7);
-	const uint32_t clast = (uint32_t)(((uint64_t)d.count * W + 127) >> 7) - 1; // last chunk holding data bits
+	const ChunkRange<W> run(r0, r1, d.count);
 	const uint64_t add = linear ? widened_min<U>(d, pred.sbit) : 0ull;
 	FieldRange fr {0u, 0u, true};
 	if (PRED) {
@@ -828,86 +838,61 @@ __device__ __forceinline__ void scan_run_w(const uint4 *__restrict__ seg16, uint
 		if (!fr.any) return; // zonemap-style skip: no row of this segment can satisfy the predicate
 	}
 	// lane -> chunk map: the workgroup strides over the run together
-	uint32_t L = c0 + threadIdx.x;
-	const uint32_t lend = c1;
-	if (L >= lend) return;
+	uint32_t L = run.c0 + threadIdx.x;
+	if (L >= run.c1) return;
 	const uint32_t sh0 = (uint32_t)(d.val_off & 31u); // selection: bit position of row 0 inside its bitmap word
-	// software pipeline: the next chunk's loads are issued (unconditionally, index clamped into the segment)
-	// before the current chunk is decoded, so a wave always has a load in flight
-	const uint32_t Lc = L < clast ? L : clast;
-	uint4 q = seg16[Lc];
-	uint32_t e = reinterpret_cast<const uint32_t *>(seg16 + (Lc < clast ? Lc + 1 : clast))[0];
-	// V: the two mask words that hold a chunk's rows travel with the chunk — requested a round ahead, unconditionally,
-	// word indices (relative to the segment's first word, 32 bits) clamped to the word of the run's last row.  Looked
-	// up inside the loop after the walk, the mask cost the masked scans 15 - 40 % (u64 w 8: SUM 5.07 -> 3.16 TB/s).
-	const uint64_t *__restrict__ vseg = V ? validity + (d.val_off >> 6) : nullptr;
-	const uint32_t vsh0 = (uint32_t)(d.val_off & 63u);
-	const uint32_t vend = (vsh0 + r1 - 1u) >> 6;
-	auto mask_words = [&](uint32_t Lx, uint64_t &m0, uint64_t &m1) {
-		const uint32_t ix0 = (128u * Lx + (W - 1)) / W;
-		const uint32_t wi = (vsh0 + (ix0 < r1 ? ix0 : r1)) >> 6;
-		m0 = vseg[wi < vend ? wi : vend];
-		m1 = vseg[wi + 1u < vend ? wi + 1u : vend];
-	};
-	// the 64 mask bits from row `at` on (bits past the run's last row are unspecified)
-	auto mask_window = [&](uint64_t m0, uint64_t m1, uint32_t at) -> uint64_t {
-		const uint32_t sh = (vsh0 + at) & 63u;
-		return (m0 >> sh) | ((m1 << 1) << (63u - sh));
-	};
+	// software pipeline: the next chunk's loads (and its mask words) are issued before the current chunk is decoded,
+	// so a wave always has a load in flight
+	uint4 q;
+	uint32_t e;
+	run.load(seg16, L, q, e);
+	const ChunkMask<W, V> vmask(validity, d.val_off, r1);
 	uint64_t vm0 = 0, vm1 = 0;
-	if (V) mask_words(Lc, vm0, vm1);
-	constexpr uint32_t adv = STRIDE;
+	if (V) vmask.words(run.clamp(L), vm0, vm1);
 	uint32_t wave_count = 0; // wave-uniform (scalar) COUNT accumulator; lane 0 of the wave leaves the loop last
-	for (; L < lend; L += adv) {
-		const uint32_t Lp = L + adv < clast ? L + adv : clast;
-		const uint4 qn = seg16[Lp];
-		const uint32_t en = reinterpret_cast<const uint32_t *>(seg16 + (Lp < clast ? Lp + 1 : clast))[0];
+	for (; L < run.c1; L += STRIDE) {
+		uint4 qn;
+		uint32_t en;
+		run.load(seg16, L + STRIDE, qn, en);
 		uint64_t vn0 = 0, vn1 = 0;
-		if (V) mask_words(Lp, vn0, vn1);
-		const uint64_t vwnd = V ? mask_window(vm0, vm1, ((128u * L + (W - 1)) / W) < r1 ? ((128u * L + (W - 1)) / W) : r1) : 0ull;
+		if (V) vmask.words(run.clamp(L + STRIDE), vn0, vn1);
+		// (the mask window is taken before the chunk is normalised: the other order costs the masked COUNT waits)
+		const uint32_t i0 = chunk_first_row<W>(L);
+		const uint32_t at = i0 < r1 ? i0 : r1; // keeps a lane's element range inside this run
+		const uint64_t vwnd = V ? vmask.window(vm0, vm1, at) : 0ull;
 		vm0 = vn0;
 		vm1 = vn1;
-		const uint32_t i0 = (128u * L + (W - 1)) / W; // first row starting in this chunk
-		const uint32_t o0 = i0 * W - 128u * L;        // its bit offset, < W <= 32
-		uint32_t nrm[5];
-		nrm[0] = __builtin_amdgcn_alignbit(q.y, q.x, o0);
-		nrm[1] = __builtin_amdgcn_alignbit(q.z, q.y, o0);
-		nrm[2] = __builtin_amdgcn_alignbit(q.w, q.z, o0);
-		nrm[3] = __builtin_amdgcn_alignbit(e, q.w, o0);
-		nrm[4] = e >> o0;
+		const ChunkWindow<W> cw(q, e, L, r1);
 		q = qn;
 		e = en;
-		const uint32_t starting = (128u - o0 + (W - 1)) / W; // rows starting in the chunk: MAXV-1 or MAXV
-		const uint32_t lim = r1 > i0 ? r1 - i0 : 0u;
 		if (OP == 1 && !V) {
 			// COUNT through the scalar unit: when every active lane's chunk is interior, each field's compare
 			// lands in an SGPR pair and s_bcnt1 adds its population to a wave-uniform counter — three vector
 			// instructions per field (extract, subtract, compare) instead of five for the per-lane hit mask
-			if (__builtin_amdgcn_ballot_w64(starting > lim) == 0ull) {
+			if (__builtin_amdgcn_ballot_w64(cw.starting > cw.lim) == 0ull) {
 				uint32_t c = 0;
 #pragma unroll
 				for (int j = 0; j < MAXV - 1; j++) {
-					c += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((field_of<W>(nrm, j) - fr.flo) <= fr.span));
+					c += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64((field_of<W>(cw.nrm, j) - fr.flo) <= fr.span));
 				}
-				const bool last_hit = (field_of<W>(nrm, MAXV - 1) - fr.flo) <= fr.span;
+				const bool last_hit = (field_of<W>(cw.nrm, MAXV - 1) - fr.flo) <= fr.span;
 				c += (uint32_t)__popcll(
-				    __builtin_amdgcn_ballot_w64(last_hit && (128 % W == 0 || starting == (uint32_t)MAXV)));
+				    __builtin_amdgcn_ballot_w64(last_hit && cw.last_starts()));
 				wave_count += c;
 				continue;
 			}
 		}
 		if (PRED && W < 4) {
 			// widths 2 and 3 hold 64 / 43 fields per chunk: the hit mask is built as two 32-bit halves
-			const uint32_t have = starting < lim ? starting : lim; // 0 for lanes past the run
+			const uint32_t have = cw.have(); // 0 for lanes past the run
 			uint32_t lo = 0, hi = 0;
 #pragma unroll
-			for (int j = 31; j >= 0; j--) hit_shift_in(lo, field_of<W>(nrm, j) - fr.flo, fr.span);
+			for (int j = 31; j >= 0; j--) hit_shift_in(lo, field_of<W>(cw.nrm, j) - fr.flo, fr.span);
 #pragma unroll
-			for (int j = MAXV - 1; j >= 32; j--) hit_shift_in(hi, field_of<W>(nrm, j) - fr.flo, fr.span);
+			for (int j = MAXV - 1; j >= 32; j--) hit_shift_in(hi, field_of<W>(cw.nrm, j) - fr.flo, fr.span);
 			const uint32_t n_lo = have < 32u ? have : 32u, n_hi = have > 32u ? have - 32u : 0u;
 			lo &= n_lo >= 32u ? 0xffffffffu : ((1u << n_lo) - 1u);
 			hi &= n_hi >= 32u ? 0xffffffffu : ((1u << n_hi) - 1u);
-			const uint32_t at = i0 < r1 ? i0 : r1; // keeps a lane's element range inside this run
 			if (V) { // NULL rows take no part
 				lo &= (uint32_t)vwnd;
 				hi &= (uint32_t)(vwnd >> 32);
@@ -922,14 +907,13 @@ __device__ __forceinline__ void scan_run_w(const uint4 *__restrict__ seg16, uint
 		if (PRED) {
 			// bit j of `hits` = row i0 + j satisfies the predicate: built top-down so that each field costs
 			// extract, subtract, compare and one add-with-carry (hits = 2 * hits + hit)
-			const uint32_t have = starting < lim ? starting : lim; // 0 for lanes past the run
+			const uint32_t have = cw.have(); // 0 for lanes past the run
 			uint32_t hits = 0;
 #pragma unroll
 			for (int j = MAXV - 1; j >= 0; j--) {
-				hit_shift_in(hits, field_of<W>(nrm, j) - fr.flo, fr.span);
+				hit_shift_in(hits, field_of<W>(cw.nrm, j) - fr.flo, fr.span);
 			}
 			hits &= have >= 32u ? 0xffffffffu : ((1u << have) - 1u);
-			const uint32_t at = i0 < r1 ? i0 : r1; // keeps a lane's element range inside this run
 			// NULL rows (DuckDB validity mask over the element index space) take no part
 			if (V) hits &= (uint32_t)vwnd;
 			acc += (uint32_t)__popc(hits);
@@ -942,21 +926,21 @@ __device__ __forceinline__ void scan_run_w(const uint4 *__restrict__ seg16, uint
 			// rows that exist AND are valid, as one mask: a field then costs its extract, ONE signed bit-field extract
 			// (0 / -1 from the row's bit), an AND and an add; the rows are counted once per chunk (v_bcnt).  (Until round
 			// 3: a row test, the bit, its negation, a count and the masked add per field — six to eight instructions.)
-			const uint32_t have = starting < lim ? starting : lim;
+			const uint32_t have = cw.have();
 			const uint32_t vb = (uint32_t)vwnd & (have >= 32u ? 0xffffffffu : ((1u << have) - 1u));
 #pragma unroll
-			for (int j = 0; j < MAXV; j++) agg.add_masked(field_of<W>(nrm, j), (uint32_t)__builtin_amdgcn_sbfe((int)vb, j, 1));
+			for (int j = 0; j < MAXV; j++) agg.add_masked(field_of<W>(cw.nrm, j), (uint32_t)__builtin_amdgcn_sbfe((int)vb, j, 1));
 			agg.nvalid = (uint32_t)__popc(vb);
-		} else if (starting <= lim) { // interior chunk: only the last slot may be absent
-			nv = starting;
+		} else if (cw.starting <= cw.lim) { // interior chunk: only the last slot may be absent
+			nv = cw.starting;
 #pragma unroll
-			for (int j = 0; j < MAXV - 1; j++) agg.add(field_of<W>(nrm, j));
-			if (128 % W == 0 || starting == (uint32_t)MAXV) agg.add(field_of<W>(nrm, MAXV - 1));
+			for (int j = 0; j < MAXV - 1; j++) agg.add(field_of<W>(cw.nrm, j));
+			if (cw.last_starts()) agg.add(field_of<W>(cw.nrm, MAXV - 1));
 		} else { // the run ends inside this chunk
-			nv = lim;
+			nv = cw.lim;
 #pragma unroll
 			for (int j = 0; j < MAXV; j++) {
-				if ((uint32_t)j < nv) agg.add(field_of<W>(nrm, j));
+				if ((uint32_t)j < nv) agg.add(field_of<W>(cw.nrm, j));
 			}
 		}
 		acc += agg.total(nv, add);
@@ -981,14 +965,9 @@ __device__ __forceinline__ void scan_run_dispatch(uint32_t w, const uint4 *__res
 			scan_run_w<3, U, OP, V>(seg16, r0, r1, d, pred, linear, validity, sel_out, acc);
 		}
 	} else {
-		switch (w) {
-#define ADAC_W(N) case N: scan_run_w<N, U, OP, V>(seg16, r0, r1, d, pred, linear, validity, sel_out, acc); break;
-			ADAC_W(4) ADAC_W(5) ADAC_W(6) ADAC_W(7) ADAC_W(8) ADAC_W(9) ADAC_W(10) ADAC_W(11) ADAC_W(12) ADAC_W(13)
-			ADAC_W(14) ADAC_W(15) ADAC_W(16) ADAC_W(17) ADAC_W(18) ADAC_W(19) ADAC_W(20) ADAC_W(21) ADAC_W(22)
-			ADAC_W(23) ADAC_W(24) ADAC_W(25) ADAC_W(26) ADAC_W(27) ADAC_W(28) ADAC_W(29) ADAC_W(30) ADAC_W(31) ADAC_W(32)
-#undef ADAC_W
-		default: break;
-		}
+		dispatch_width_4_32(w, [&](auto wc) __attribute__((always_inline)) {
+			scan_run_w<decltype(wc)::value, U, OP, V>(seg16, r0, r1, d, pred, linear, validity, sel_out, acc);
+		});
 	}
 }
 
@@ -1630,36 +1609,25 @@ __device__ __forceinline__ uint32_t stage_tiles(uint32_t w_a, uint32_t w_b) {
 template <int W>
 __device__ __forceinline__ void repack_run_w(const uint4 *__restrict__ seg16, uint32_t r0, uint32_t r1, uint32_t count,
                                              uint32_t delta, uint32_t w_new, uint32_t *img32) {
-	constexpr int MAXV = (128 + W - 1) / W;
+	constexpr int MAXV = ChunkWindow<W>::MAXV;
 	const uint32_t mask_new = w_new >= 32u ? 0xffffffffu : ((1u << w_new) - 1u);
-	const uint32_t c0 = (uint32_t)(((uint64_t)r0 * W) >> 7); // r0 is a multiple of 128 rows
-	const uint32_t c1 = (uint32_t)(((uint64_t)r1 * W + 127) >> 7);
-	const uint32_t clast = (uint32_t)(((uint64_t)count * W + 127) >> 7) - 1; // last chunk holding data bits
-	uint32_t L = c0 + threadIdx.x;
-	if (L >= c1) return;
-	const uint32_t Lc = L < clast ? L : clast;
-	uint4 q = seg16[Lc];
-	uint32_t e = reinterpret_cast<const uint32_t *>(seg16 + (Lc < clast ? Lc + 1 : clast))[0];
-	for (; L < c1; L += kWorkgroup) {
-		const uint32_t Lp = L + kWorkgroup < clast ? L + kWorkgroup : clast;
-		const uint4 qn = seg16[Lp];
-		const uint32_t en = reinterpret_cast<const uint32_t *>(seg16 + (Lp < clast ? Lp + 1 : clast))[0];
-		const uint32_t i0 = (128u * L + (W - 1)) / W; // first row starting in this chunk
-		const uint32_t o0 = i0 * W - 128u * L;        // its bit offset, < W <= 32
-		uint32_t nrm[5];
-		nrm[0] = __builtin_amdgcn_alignbit(q.y, q.x, o0);
-		nrm[1] = __builtin_amdgcn_alignbit(q.z, q.y, o0);
-		nrm[2] = __builtin_amdgcn_alignbit(q.w, q.z, o0);
-		nrm[3] = __builtin_amdgcn_alignbit(e, q.w, o0);
-		nrm[4] = e >> o0;
+	const ChunkRange<W> run(r0, r1, count);
+	uint32_t L = run.c0 + threadIdx.x;
+	if (L >= run.c1) return;
+	uint4 q;
+	uint32_t e;
+	run.load(seg16, L, q, e);
+	for (; L < run.c1; L += kWorkgroup) {
+		uint4 qn;
+		uint32_t en;
+		run.load(seg16, L + kWorkgroup, qn, en);
+		const ChunkWindow<W> cw(q, e, L, r1);
 		q = qn;
 		e = en;
-		const uint32_t starting = (128u - o0 + (W - 1)) / W; // rows starting in the chunk: MAXV-1 or MAXV
-		const uint32_t lim = r1 > i0 ? r1 - i0 : 0u;
-		const uint32_t have = starting < lim ? starting : lim;
+		const uint32_t have = cw.have();
 		if (have == 0u) continue;
 		// the string starts at bit p of the stage image; dwords leave through a funnel by p's offset in its dword
-		const uint32_t p = (i0 - r0) * w_new;
+		const uint32_t p = (cw.i0 - r0) * w_new;
 		uint32_t *out = img32 + (p >> 5);
 		const uint32_t sh = p & 31u, rs = 32u - sh;
 		const bool z = sh == 0u;
@@ -1668,7 +1636,7 @@ __device__ __forceinline__ void repack_run_w(const uint4 *__restrict__ seg16, ui
 		uint32_t t = 0, nd = 0; // wave-uniform: bits in acc, dwords emitted
 #pragma unroll
 		for (int j = 0; j < MAXV; j++) {
-			const uint32_t g = (uint32_t)j < have ? ((field_of<W>(nrm, j) + delta) & mask_new) : 0u;
+			const uint32_t g = (uint32_t)j < have ? ((field_of<W>(cw.nrm, j) + delta) & mask_new) : 0u;
 			acc |= (uint64_t)g << t;
 			t += w_new;
 			if (t >= 32u) { // uniform
@@ -1694,37 +1662,26 @@ __device__ __forceinline__ void repack_run_w(const uint4 *__restrict__ seg16, ui
 template <int W, int TBITS>
 __device__ __forceinline__ void analyze_run_w(const uint4 *__restrict__ seg16, uint32_t r0, uint32_t r1, uint32_t count,
                                               uint32_t add32, uint32_t &mn32, uint32_t &mx32) {
-	constexpr int MAXV = (128 + W - 1) / W;
+	constexpr int MAXV = ChunkWindow<W>::MAXV;
 	constexpr uint32_t tmask = TBITS >= 32 ? 0xffffffffu : ((1u << (TBITS & 31)) - 1u);
-	const uint32_t c0 = (uint32_t)(((uint64_t)r0 * W) >> 7);
-	const uint32_t c1 = (uint32_t)(((uint64_t)r1 * W + 127) >> 7);
-	const uint32_t clast = (uint32_t)(((uint64_t)count * W + 127) >> 7) - 1;
-	uint32_t L = c0 + threadIdx.x;
-	if (L >= c1) return;
-	const uint32_t Lc = L < clast ? L : clast;
-	uint4 q = seg16[Lc];
-	uint32_t e = reinterpret_cast<const uint32_t *>(seg16 + (Lc < clast ? Lc + 1 : clast))[0];
-	for (; L < c1; L += kWorkgroup) {
-		const uint32_t Lp = L + kWorkgroup < clast ? L + kWorkgroup : clast;
-		const uint4 qn = seg16[Lp];
-		const uint32_t en = reinterpret_cast<const uint32_t *>(seg16 + (Lp < clast ? Lp + 1 : clast))[0];
-		const uint32_t i0 = (128u * L + (W - 1)) / W;
-		const uint32_t o0 = i0 * W - 128u * L;
-		uint32_t nrm[5];
-		nrm[0] = __builtin_amdgcn_alignbit(q.y, q.x, o0);
-		nrm[1] = __builtin_amdgcn_alignbit(q.z, q.y, o0);
-		nrm[2] = __builtin_amdgcn_alignbit(q.w, q.z, o0);
-		nrm[3] = __builtin_amdgcn_alignbit(e, q.w, o0);
-		nrm[4] = e >> o0;
+	const ChunkRange<W> run(r0, r1, count);
+	uint32_t L = run.c0 + threadIdx.x;
+	if (L >= run.c1) return;
+	uint4 q;
+	uint32_t e;
+	run.load(seg16, L, q, e);
+	for (; L < run.c1; L += kWorkgroup) {
+		uint4 qn;
+		uint32_t en;
+		run.load(seg16, L + kWorkgroup, qn, en);
+		const ChunkWindow<W> cw(q, e, L, r1);
 		q = qn;
 		e = en;
-		const uint32_t starting = (128u - o0 + (W - 1)) / W;
-		const uint32_t lim = r1 > i0 ? r1 - i0 : 0u;
-		const uint32_t have = starting < lim ? starting : lim;
+		const uint32_t have = cw.have();
 #pragma unroll
 		for (int j = 0; j < MAXV; j++) {
 			if ((uint32_t)j < have) {
-				const uint32_t x = TBITS == 64 ? field_of<W>(nrm, j) : ((field_of<W>(nrm, j) + add32) & tmask);
+				const uint32_t x = TBITS == 64 ? field_of<W>(cw.nrm, j) : ((field_of<W>(cw.nrm, j) + add32) & tmask);
 				mn32 = x < mn32 ? x : mn32;
 				mx32 = x > mx32 ? x : mx32;
 			}
@@ -1736,28 +1693,16 @@ template <typename U>
 __device__ __forceinline__ void analyze_run_dispatch(uint32_t w_old, const uint4 *__restrict__ seg16, uint32_t r0,
                                                      uint32_t r1, uint32_t count, uint32_t add32, uint32_t &mn32,
                                                      uint32_t &mx32) {
-	switch (w_old) {
-#define ADAC_W(N) case N: analyze_run_w<N, 8 * (int)sizeof(U)>(seg16, r0, r1, count, add32, mn32, mx32); break;
-		ADAC_W(4) ADAC_W(5) ADAC_W(6) ADAC_W(7) ADAC_W(8) ADAC_W(9) ADAC_W(10) ADAC_W(11) ADAC_W(12) ADAC_W(13)
-		ADAC_W(14) ADAC_W(15) ADAC_W(16) ADAC_W(17) ADAC_W(18) ADAC_W(19) ADAC_W(20) ADAC_W(21) ADAC_W(22)
-		ADAC_W(23) ADAC_W(24) ADAC_W(25) ADAC_W(26) ADAC_W(27) ADAC_W(28) ADAC_W(29) ADAC_W(30) ADAC_W(31) ADAC_W(32)
-#undef ADAC_W
-	default: break;
-	}
+	dispatch_width_4_32(w_old, [&](auto wc) __attribute__((always_inline)) {
+		analyze_run_w<decltype(wc)::value, 8 * (int)sizeof(U)>(seg16, r0, r1, count, add32, mn32, mx32);
+	});
 }
 
 template <typename U>
 __device__ __forceinline__ void repack_run_dispatch(uint32_t w_old, const uint4 *__restrict__ seg16, uint32_t r0,
                                                     uint32_t r1, uint32_t count, uint32_t delta, uint32_t w_new,
                                                     uint32_t *img32) {
-	switch (w_old) {
-#define ADAC_W(N) case N: repack_run_w<N>(seg16, r0, r1, count, delta, w_new, img32); break;
-		ADAC_W(4) ADAC_W(5) ADAC_W(6) ADAC_W(7) ADAC_W(8) ADAC_W(9) ADAC_W(10) ADAC_W(11) ADAC_W(12) ADAC_W(13)
-		ADAC_W(14) ADAC_W(15) ADAC_W(16) ADAC_W(17) ADAC_W(18) ADAC_W(19) ADAC_W(20) ADAC_W(21) ADAC_W(22)
-		ADAC_W(23) ADAC_W(24) ADAC_W(25) ADAC_W(26) ADAC_W(27) ADAC_W(28) ADAC_W(29) ADAC_W(30) ADAC_W(31) ADAC_W(32)
-#undef ADAC_W
-	default: break;
-	}
+	dispatch_width_4_32(w_old, [&](auto wc) __attribute__((always_inline)) { repack_run_w<decltype(wc)::value>(seg16, r0, r1, count, delta, w_new, img32); });
 }
 
 template <typename U>
@@ -2102,9 +2047,9 @@ hipError_t launch_group_sum(hipStream_t s, uint32_t v_type_size, bool v_signed, 
                             const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups, void *d_partial,
                             uint32_t call_parity, uint64_t *d_sums, uint64_t *d_counts) {
 	GroupSumTypes ty;
-	ty.v_tmask = v_type_size >= 8 ? ~0ull : ((1ull << (8 * v_type_size)) - 1ull);
-	ty.v_sbit = v_signed ? (1ull << (8 * v_type_size - 1)) : 0ull;
-	ty.k_tmask = k_type_size >= 8 ? ~0ull : ((1ull << (8 * k_type_size)) - 1ull);
+	ty.v_tmask = type_mask(v_type_size);
+	ty.v_sbit = type_sign_bit(v_type_size, v_signed);
+	ty.k_tmask = type_mask(k_type_size);
 	ty.v_tile_rows = tile_values(v_type_size);
 	ty.wide_only = g_tuning.group_sum_wide ? 1u : 0u;
 	const uint32_t nbins = ngroups + 1u;
@@ -2150,10 +2095,10 @@ hipError_t launch_scan_sum_product(hipStream_t s, uint32_t a_type_size, bool a_s
                                    const uint64_t *d_validity, uint64_t *d_sums) {
 	if (ngroups == 0) return hipSuccess;
 	ProductTypes ty;
-	ty.a_tmask = a_type_size >= 8 ? ~0ull : ((1ull << (8 * a_type_size)) - 1ull);
-	ty.a_sbit = a_signed ? (1ull << (8 * a_type_size - 1)) : 0ull;
-	ty.b_tmask = b_type_size >= 8 ? ~0ull : ((1ull << (8 * b_type_size)) - 1ull);
-	ty.b_sbit = b_signed ? (1ull << (8 * b_type_size - 1)) : 0ull;
+	ty.a_tmask = type_mask(a_type_size);
+	ty.a_sbit = type_sign_bit(a_type_size, a_signed);
+	ty.b_tmask = type_mask(b_type_size);
+	ty.b_sbit = type_sign_bit(b_type_size, b_signed);
 	unsigned long long *sums = reinterpret_cast<unsigned long long *>(d_sums);
 	if (d_validity) {
 		hipLaunchKernelGGL(k_scan_product<true>, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_agroups, d_awords,

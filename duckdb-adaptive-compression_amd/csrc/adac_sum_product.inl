@@ -36,15 +36,10 @@ struct ProductPlan {
 	uint64_t ma, mb; // value64 = field + frame on either side (0 for raw segments)
 };
 
-// value64 = field + add for EVERY w-bit field without leaving T's range (seg_kind's SEG_LINEAR with the range test
-// made for unsigned types too), or the field itself (raw slots / no frame of reference, unsigned T)
+// value64 = field + add for EVERY w-bit field without leaving T's range (frame_fits_type), or the field itself (raw
+// slots / no frame of reference, unsigned T)
 __device__ __forceinline__ bool product_frame(const adac_segment_desc &d, uint64_t tmask, uint64_t sbit, uint64_t &add) {
-	if ((d.flags & ADAC_SEG_PACKED) && d.min != ADAC_NO_MIN) {
-		const uint64_t tmin = d.min & tmask, bmin = tmin ^ sbit, top = bmin + mask64(d.width);
-		if (top < bmin || top > tmask) return false;
-		add = bmin - sbit; // widened by T's signedness
-		return true;
-	}
+	if ((d.flags & ADAC_SEG_PACKED) && d.min != ADAC_NO_MIN) return frame_fits_type(d, tmask, sbit, add);
 	add = 0ull;
 	return sbit == 0ull;
 }
@@ -74,43 +69,29 @@ __device__ __forceinline__ void product_walk(uint32_t r0, uint32_t r1, const ada
                                              const adac_segment_desc &bd, const uint4 *__restrict__ aseg16,
                                              const uint4 *__restrict__ bseg16, const uint64_t *__restrict__ validity,
                                              uint4 *bstage, ProductAcc &acc) {
-	constexpr int MAXV = (128 + W - 1) / W;
+	constexpr int MAXV = ChunkWindow<W>::MAXV;
 	const uint32_t wb = bd.width, bmask = mask32(wb);
 	// as many lanes as keep the round's rows of b inside the buffer: rows <= lanes * MAXV, so bits <= 126 chunks, which
 	// from any bit offset of the first chunk lie in 128 chunks at most (64 lanes unless b is much wider than a)
 	uint32_t lanes = ((kProdWaveData - 2u) * 128u) / ((uint32_t)MAXV * wb);
 	lanes = lanes < 64u ? lanes : 64u;
-	const uint32_t c0 = (uint32_t)(((uint64_t)r0 * W) >> 7);
-	const uint32_t c1 = (uint32_t)(((uint64_t)r1 * W + 127) >> 7);
-	const uint32_t clast = (uint32_t)(((uint64_t)ad.count * W + 127) >> 7) - 1;  // last chunk holding data bits of a
-	const uint32_t bclast = (uint32_t)(((uint64_t)bd.count * wb + 127) >> 7) - 1; // ... of b
+	const ChunkRange<W> run(r0, r1, ad.count);
+	const uint32_t c0 = run.c0, c1 = run.c1;
+	const uint32_t bclast = (uint32_t)(((uint64_t)bd.count * wb + 127) >> 7) - 1; // last chunk holding data bits of b
 	const uint32_t lane = threadIdx.x & 63u;
 	const bool walker = lane < lanes;
 	uint32_t L = c0 + lane;
-	const uint32_t Lc = L < clast ? L : clast;
-	uint4 q = aseg16[Lc];
-	uint32_t e = reinterpret_cast<const uint32_t *>(aseg16 + (Lc < clast ? Lc + 1 : clast))[0];
-	// the mask words of a chunk's rows travel with the chunk (scan_run_w's form): a's element space
-	const uint64_t *__restrict__ vseg = V ? validity + (ad.val_off >> 6) : nullptr;
-	const uint32_t vsh0 = (uint32_t)(ad.val_off & 63u);
-	const uint32_t vend = (vsh0 + r1 - 1u) >> 6;
-	auto mask_words = [&](uint32_t Lx, uint64_t &m0, uint64_t &m1) {
-		const uint32_t ix0 = (128u * Lx + (W - 1)) / W;
-		const uint32_t wi = (vsh0 + (ix0 < r1 ? ix0 : r1)) >> 6;
-		m0 = vseg[wi < vend ? wi : vend];
-		m1 = vseg[wi + 1u < vend ? wi + 1u : vend];
-	};
-	auto mask_window = [&](uint64_t m0, uint64_t m1, uint32_t at) -> uint64_t {
-		const uint32_t sh = (vsh0 + at) & 63u;
-		return (m0 >> sh) | ((m1 << 1) << (63u - sh));
-	};
+	uint4 q;
+	uint32_t e;
+	run.load(aseg16, L, q, e);
+	const ChunkMask<W, V> vmask(validity, ad.val_off, r1); // a's element space
 	uint64_t vm0 = 0, vm1 = 0;
-	if (V) mask_words(Lc, vm0, vm1);
+	if (V) vmask.words(run.clamp(L), vm0, vm1);
 	// b: the round that starts at chunk rc of a covers the rows [first row starting in chunk rc, first row starting in
 	// chunk rc + lanes) below r1; bc0 = the chunk of b holding the first bit of the first of them, nb chunks in all
 	auto round_b = [&](uint32_t rc, uint32_t &bc0, uint32_t &nb) {
-		const uint32_t lo = (128u * rc + (W - 1)) / W;
-		uint32_t hi = (128u * (rc + lanes) + (W - 1)) / W;
+		const uint32_t lo = chunk_first_row<W>(rc);
+		uint32_t hi = chunk_first_row<W>(rc + lanes);
 		hi = hi < r1 ? hi : r1;
 		bc0 = (lo * wb) >> 7;
 		nb = hi > lo ? ((hi * wb + 127u) >> 7) - bc0 : 0u;
@@ -136,30 +117,21 @@ __device__ __forceinline__ void product_walk(uint32_t r0, uint32_t r1, const ada
 	store_b(bq, nb);
 	for (uint32_t round0 = c0; round0 < c1; round0 += lanes, L += lanes) { // uniform trip count
 		// requested before this round is walked: the next chunk of a, its mask words and the next round's chunks of b
-		const uint32_t Lp = L + lanes < clast ? L + lanes : clast;
-		const uint4 qn = aseg16[Lp];
-		const uint32_t en = reinterpret_cast<const uint32_t *>(aseg16 + (Lp < clast ? Lp + 1 : clast))[0];
+		uint4 qn;
+		uint32_t en;
+		run.load(aseg16, L + lanes, qn, en);
 		uint64_t vn0 = 0, vn1 = 0;
-		if (V) mask_words(Lp, vn0, vn1);
+		if (V) vmask.words(run.clamp(L + lanes), vn0, vn1);
 		uint32_t bc0n = 0, nbn = 0;
 		round_b(round0 + lanes, bc0n, nbn);
 		load_b(bc0n, bq);
 		if (walker && L < c1) {
-			const uint32_t i0 = (128u * L + (W - 1)) / W; // first row starting in this chunk
-			const uint32_t o0 = i0 * W - 128u * L;
-			uint32_t nrm[5];
-			nrm[0] = __builtin_amdgcn_alignbit(q.y, q.x, o0);
-			nrm[1] = __builtin_amdgcn_alignbit(q.z, q.y, o0);
-			nrm[2] = __builtin_amdgcn_alignbit(q.w, q.z, o0);
-			nrm[3] = __builtin_amdgcn_alignbit(e, q.w, o0);
-			nrm[4] = e >> o0;
-			const uint32_t starting = (128u - o0 + (W - 1)) / W; // rows starting in the chunk: MAXV - 1 or MAXV
-			const uint32_t lim = r1 > i0 ? r1 - i0 : 0u;
-			const uint32_t have = starting < lim ? starting : lim;
+			const ChunkWindow<W> cw(q, e, L, r1);
+			const uint32_t have = cw.have();
 			// rows that exist AND are kept, as one mask
 			uint32_t vb = have >= 32u ? 0xffffffffu : ((1u << have) - 1u);
-			if (V) vb &= (uint32_t)mask_window(vm0, vm1, i0 < r1 ? i0 : r1);
-			const uint32_t bbit = i0 * wb - 128u * bc0; // row i0 of b inside the staged chunks
+			if (V) vb &= (uint32_t)vmask.window(vm0, vm1, cw.i0 < r1 ? cw.i0 : r1);
+			const uint32_t bbit = cw.i0 * wb - 128u * bc0; // row i0 of b inside the staged chunks
 			ChunkSum<W> sa;
 			uint64_t pp = 0, sb = 0;
 			// eight rows at a time: their fields of b are read together (eight LDS round trips in flight), then consumed
@@ -174,7 +146,7 @@ __device__ __forceinline__ void product_walk(uint32_t r0, uint32_t r1, const ada
 				for (int u = 0; u < 8; u++) {
 					if (j0 + u < MAXV) {
 						const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)vb, j0 + u, 1); // 0 / -1
-						const uint32_t fa = field_of<W>(nrm, j0 + u) & m;
+						const uint32_t fa = field_of<W>(cw.nrm, j0 + u) & m;
 						sa.add(fa);
 						sb += fb[u] & m;
 						pp += (uint64_t)fa * fb[u]; // v_mad_u64_u32
@@ -201,14 +173,9 @@ __device__ __forceinline__ void product_walk_dispatch(uint32_t r0, uint32_t r1, 
                                                       const uint4 *__restrict__ bseg16,
                                                       const uint64_t *__restrict__ validity, uint4 *bstage,
                                                       ProductAcc &acc) {
-	switch (ad.width) { // uniform
-#define ADAC_W(N) case N: product_walk<N, V>(r0, r1, ad, bd, aseg16, bseg16, validity, bstage, acc); break;
-		ADAC_W(4) ADAC_W(5) ADAC_W(6) ADAC_W(7) ADAC_W(8) ADAC_W(9) ADAC_W(10) ADAC_W(11) ADAC_W(12) ADAC_W(13)
-		ADAC_W(14) ADAC_W(15) ADAC_W(16) ADAC_W(17) ADAC_W(18) ADAC_W(19) ADAC_W(20) ADAC_W(21) ADAC_W(22)
-		ADAC_W(23) ADAC_W(24) ADAC_W(25) ADAC_W(26) ADAC_W(27) ADAC_W(28) ADAC_W(29) ADAC_W(30) ADAC_W(31) ADAC_W(32)
-#undef ADAC_W
-	default: break;
-	}
+	dispatch_width_4_32(ad.width, [&](auto wc) __attribute__((always_inline)) {
+		product_walk<decltype(wc)::value, V>(r0, r1, ad, bd, aseg16, bseg16, validity, bstage, acc);
+	});
 }
 
 // one stage of the generic form: rows [row0, row0 + m) of the segment pair (all uniform)

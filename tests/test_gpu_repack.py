@@ -109,3 +109,60 @@ def test_repack_with_nulls_and_argument_errors(adac, oracle, gpu_ctx):
         src.reencode(d_src, other, d_dst)          # different segment shapes
     with pytest.raises(adac.AdacError):
         src.repack(d_src, dst, d_src)              # in place is not supported
+
+
+@pytest.mark.parametrize("dtype", [np.uint32, np.uint64])
+def test_reencode_from_every_source_width(adac, oracle, gpu_ctx, dtype):
+    """The width-templated source walk (analyze_run_w, repack_run_w) at EVERY source width 4..32: one segment per
+    width.  Each width gets ONE of four sizes, in rotation: the workgroup takes a second round over the chunks and the
+    run ends inside a chunk (2 tiles + 37), the run ends on a chunk boundary (a tile), one or two chunks with the last
+    one partial (129), less than one chunk (3: the clamp to the last data chunk governs both loads).  The rotation
+    starts two sizes later for uint64, so the two types pair every width with different sizes: uint32 has the long run
+    at widths 4, 8, ... and the 3-row run at 7, 11, ..., uint64 the long run at 6, 10, ... and the 3-row run at 5, 9,
+    ...  Every segment's rows are rewritten in place to a range 3 bits narrower, so the min/max pass has to find new
+    extrema on the packed data and the repack re-bases every field to another width.  For uint32 the generic
+    (LDS-staged) path must write the same destination words."""
+    dtype = np.dtype(dtype)
+    rng = np.random.default_rng(4100 + dtype.itemsize)
+    tile = adac.tile_values(dtype)
+    widths = list(range(4, 33))
+    sizes = [2 * tile + 37, tile, 129, 3]
+    first = 0 if dtype.itemsize == 4 else 2
+    counts = np.array([sizes[(i + first) % 4] for i in range(len(widths))], dtype=np.uint32)
+    wide = [make_values(rng, dtype, int(n), w) for n, w in zip(counts, widths)]
+    src, d_src, _, sd, _ = run_encode_decode(adac, oracle, gpu_ctx, dtype, counts, wide)
+    assert sd["width"].tolist() == widths
+    # rewrite the rows at the OLD widths and mins (what an in-place update leaves behind)
+    descs = src.get_descs()
+    host = np.zeros(src.max_arena_words, dtype=np.uint64)
+    narrow = []
+    for s, w in enumerate(widths):
+        mn, off = int(descs["min"][s]), int(descs["word_off"][s])
+        v = make_values(rng, dtype, int(counts[s]), w - 3, base=mn + 5)
+        assert int(v.min()) >= mn and int(v.max()) - mn < (1 << w)
+        ws = oracle.pack_flat(v, mn, w)
+        host[off:off + len(ws)] = ws
+        narrow.append(v)
+    d_src.upload(host)
+    total = int(counts.sum())
+
+    def reencode():
+        dst = adac.Layout(gpu_ctx, dtype, counts)
+        d_dst = gpu_ctx.alloc(dst.max_arena_words * 8 + 16).zero()
+        src.reencode(d_src, dst, d_dst)
+        check_dst(adac, oracle, dst, d_dst, narrow, adac.RULE_APPEND, False)
+        assert dst.get_descs()["width"].tolist() == [w - 3 for w in widths]
+        d_out = gpu_ctx.alloc(total * dtype.itemsize + 64)
+        dst.unpack(d_dst, d_out)
+        assert np.array_equal(d_out.download(dtype, total), np.concatenate(narrow))
+        return d_dst.download(np.uint64, dst.max_arena_words), dst.get_descs()
+
+    words, ddescs = reencode()
+    if dtype == np.uint32:
+        try:
+            adac.set_tuning("templated_scan", 0)
+            words_generic, ddescs_generic = reencode()
+        finally:
+            adac.set_tuning("templated_scan", 1)
+        assert np.array_equal(words_generic, words)
+        assert np.array_equal(ddescs_generic, ddescs)
