@@ -118,18 +118,83 @@ def adaptive(host, wl, nseg=400, rows=32767, periods=4):
     return out
 
 
+def bitpacking_columns(n):
+    rng = np.random.default_rng(11)
+    return {
+        "for_u32_w20": (5_000_000 + rng.integers(0, 1 << 20, size=n)).astype(np.uint32),
+        "delta_for_i64_sorted": (10 ** 12 + np.cumsum(rng.integers(0, 1 << 9, size=n))).astype(np.int64),
+        "for_u64_w32": (rng.integers(0, 1 << 32, size=n, dtype=np.uint64) + np.uint64(1 << 40)).astype(np.uint64),
+    }
+
+
+def bitpacking_fused_scans(adac, n=50_000_000):
+    """Fused scans on BITPACKING blocks (adac_bp_scan_*) beside the decode of the same blocks, same process: per-call
+    HIP-event times of scan_sum, scan_select_between at about 10 % selectivity and adac_bp_unpack over
+    bitpacking_scan's three columns, after the results were checked against numpy."""
+    from oracle import bitpacking as bp
+    ctx = adac.Context(0)
+    out = {"rows": n, "cases": []}
+    stride = 262144
+    reps = 20
+    for name, v in bitpacking_columns(n).items():
+        comp = bp.Compressed(v)
+        nseg = comp.nseg
+        buf = np.zeros(nseg * stride + 64, dtype=np.uint8)
+        counts = np.zeros(nseg, dtype=np.uint32)
+        used = 0
+        for i in range(nseg):
+            buf[i * stride:i * stride + bp.BLOCK_SIZE] = comp.block(i)
+            counts[i] = comp.count(i)
+            used += comp.size(i)
+        d_blocks = ctx.upload(buf)
+        lay = adac.BitpackingLayout(ctx, v.dtype, np.arange(nseg, dtype=np.uint64) * stride, counts)
+        d_out = ctx.alloc(n * v.dtype.itemsize + 64)
+        d_sum, d_cnt, d_bm = ctx.alloc(nseg * 8), ctx.alloc(nseg * 8), ctx.alloc((n + 63) // 64 * 8 + 8)
+        lo, hi = (int(x) for x in np.quantile(v, [0.45, 0.55]))
+        lay.unpack(d_blocks, d_out)
+        lay.scan_sum(d_blocks, d_sum)
+        lay.scan_select_between(d_blocks, lo, hi, d_bm, d_cnt)
+        ctx.sync()
+        assert np.array_equal(d_out.download(v.dtype, n), v)
+        bounds = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        wide = v.astype(np.int64 if v.dtype.kind == "i" else np.uint64).view(np.uint64)
+        want = np.add.reduceat(wide, bounds[:-1])
+        assert np.array_equal(d_sum.download(np.uint64, nseg), want), "SUM parity"
+        hit = (v >= lo) & (v <= hi)
+        assert np.array_equal(d_cnt.download(np.uint64, nseg), np.add.reduceat(hit.astype(np.uint64), bounds[:-1]))
+        words = np.packbits(np.concatenate([hit, np.zeros((-n) % 64, dtype=bool)]), bitorder="little").view(np.uint64)
+        assert np.array_equal(d_bm.download(np.uint64, len(words)), words), "bitmap parity"
+        ms = {}
+        for what, fn in (("decode", lambda: lay.unpack(d_blocks, d_out)), ("scan_sum", lambda: lay.scan_sum(d_blocks, d_sum)),
+                         ("select", lambda: lay.scan_select_between(d_blocks, lo, hi, d_bm, d_cnt)),
+                         ("decode_again", lambda: lay.unpack(d_blocks, d_out)),
+                         ("scan_sum_again", lambda: lay.scan_sum(d_blocks, d_sum))):
+            fn()
+            ctx.timer_start()
+            for _ in range(reps):
+                fn()
+            ms[what] = ctx.timer_stop() / reps
+        dec, ssum = min(ms["decode"], ms["decode_again"]), min(ms["scan_sum"], ms["scan_sum_again"])
+        out["cases"].append({
+            "name": name, "dtype": str(v.dtype), "segments": nseg, "groups": int(lay.ngroups), "compressed_bytes": used,
+            "modes": comp.groups_by_mode(), "selectivity": float(hit.mean()), "ms": ms,
+            "decode_ms": dec, "scan_sum_ms": ssum, "select_ms": ms["select"],
+            "scan_sum_over_decode": ssum / dec, "select_over_decode": ms["select"] / dec,
+            "scan_sum_block_TBps": used / (ssum * 1e-3) / 1e12, "select_block_TBps": used / (ms["select"] * 1e-3) / 1e12,
+            "decode_block_TBps": used / (dec * 1e-3) / 1e12,
+        })
+        del lay, d_blocks, d_out, d_sum, d_cnt, d_bm, comp
+    ctx.close()
+    return out
+
+
 def bitpacking_scan(adac, n=50_000_000):
     """Full scan of on-disk BITPACKING segments: blocks written by the oracle's restatement of the
     reference's compress (CPU, untimed), decoded on the device; rates from HIP events on the codec stream."""
     from oracle import bitpacking as bp
     ctx = adac.Context(0)
-    rng = np.random.default_rng(11)
     out = {"rows": n, "cases": []}
-    cols = {
-        "for_u32_w20": (5_000_000 + rng.integers(0, 1 << 20, size=n)).astype(np.uint32),
-        "delta_for_i64_sorted": (10 ** 12 + np.cumsum(rng.integers(0, 1 << 9, size=n))).astype(np.int64),
-        "for_u64_w32": (rng.integers(0, 1 << 32, size=n, dtype=np.uint64) + np.uint64(1 << 40)).astype(np.uint64),
-    }
+    cols = bitpacking_columns(n)
     stride = 262144
     for name, v in cols.items():
         t0 = time.perf_counter()
@@ -515,6 +580,7 @@ def main():
     only = sys.argv[1:]
     jobs = {"plugin_scan": lambda: plugin_scan(host, lay), "adaptive": lambda: adaptive(host, wl),
             "bitpacking_scan": lambda: bitpacking_scan(adac), "q6_packed": lambda: q6_packed(adac),
+            "bitpacking_fused_scans": lambda: bitpacking_fused_scans(adac),
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "c1_lookups": lambda: c1_lookups(adac, wl)}
     res = {k: f() for k, f in jobs.items() if not only or k in only}

@@ -174,6 +174,11 @@ SIGNATURES = {
     "adac_bp_layout_destroy": (None, [_vp]),
     "adac_bp_layout_ngroups": (_u64, [_vp]),
     "adac_bp_layout_total_values": (_u64, [_vp]),
+    "adac_bp_layout_value_span": (_u64, [_vp]),
+    "adac_bp_scan_sum": (_int, [_vp, _vp, _vp, _vp]),
+    "adac_bp_scan_count_between": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
+    "adac_bp_scan_select_between": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "adac_bp_scan_min_max": (_int, [_vp, _vp, _vp, _vp]),
     "adac_bp_bind": (_int, [_vp, _vp]),
     "adac_bp_unpack": (_int, [_vp, _vp, _vp]),
     "adac_bp_unpack_range": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64]),
@@ -587,6 +592,7 @@ class BitpackingLayout:
 
     ngroups = property(lambda s: lib().adac_bp_layout_ngroups(s._h))
     total_values = property(lambda s: lib().adac_bp_layout_total_values(s._h))
+    value_span = property(lambda s: lib().adac_bp_layout_value_span(s._h))
 
     def bind(self, d_blocks):
         _check(lib().adac_bp_bind(self._h, _dptr(d_blocks)), "adac_bp_bind")
@@ -601,6 +607,25 @@ class BitpackingLayout:
     def fetch_rows(self, d_blocks, d_segs, d_rows, n, d_out):
         _check(lib().adac_bp_fetch_rows(self._h, _dptr(d_blocks), _dptr(d_segs), _dptr(d_rows), n, _dptr(d_out)),
                "adac_bp_fetch_rows")
+
+    # fused scans on the block images (nothing decoded to HBM); masks and bitmaps are indexed by out_off + row
+    def scan_sum(self, d_blocks, d_sums, d_validity=None):
+        _check(lib().adac_bp_scan_sum(self._h, _dptr(d_blocks), _dptr(d_validity), _dptr(d_sums)), "adac_bp_scan_sum")
+
+    def scan_count_between(self, d_blocks, lo, hi, d_counts, d_validity=None):
+        """lo / hi: bit patterns of the column type (use int(np.array([v], dtype).view(unsigned)[0]) for signed)."""
+        _check(lib().adac_bp_scan_count_between(self._h, _dptr(d_blocks), _dptr(d_validity), lo & NO_MIN, hi & NO_MIN,
+                                                _dptr(d_counts)), "adac_bp_scan_count_between")
+
+    def scan_select_between(self, d_blocks, lo, hi, d_bitmap, d_counts, d_validity=None):
+        """Selection bitmap over the element index space (ceil(value_span / 64) words) + per-segment hit counts."""
+        _check(lib().adac_bp_scan_select_between(self._h, _dptr(d_blocks), _dptr(d_validity), lo & NO_MIN, hi & NO_MIN,
+                                                 _dptr(d_bitmap), _dptr(d_counts)), "adac_bp_scan_select_between")
+
+    def scan_min_max(self, d_blocks, d_minmax, d_validity=None):
+        """Per segment (min, max) in the column type's order as its bit patterns; no selected row: (T.max, T.min)."""
+        _check(lib().adac_bp_scan_min_max(self._h, _dptr(d_blocks), _dptr(d_validity), _dptr(d_minmax)),
+               "adac_bp_scan_min_max")
 
 
 class BitpackingPlan:

@@ -1233,10 +1233,13 @@ extern "C" adac_status adac_scan_count_eq(adac_layout *l, const uint64_t *d_word
 struct adac_bp_layout {
 	adac_ctx *ctx = nullptr;
 	uint32_t type_size = 0;
+	bool is_signed = false;
 	uint64_t nseg = 0, ngroups = 0, total_values = 0;
+	uint64_t value_span = 0; // max(out_off + count): elements an output / mask / bitmap over the layout spans
 	std::vector<uint32_t> counts;
 	std::vector<uint64_t> seg_first_group; // index of each segment's first metadata group in the group table
 	void *d_groups = nullptr;
+	uint32_t *d_group_seg = nullptr; // segment of every group (the fused scans' results are per segment)
 	uint64_t *d_block_offs = nullptr;
 	const void *bound_blocks = nullptr; // blocks buffer whose group headers are parsed into d_groups
 };
@@ -1252,9 +1255,11 @@ extern "C" adac_status adac_bp_layout_create(adac_ctx *c, int physical_type, con
 	l->ctx = c;
 	ctx_retain(c);
 	l->type_size = adac_type_size(physical_type);
+	l->is_signed = type_is_signed(physical_type);
 	l->nseg = nseg;
 	l->counts.assign(counts, counts + nseg);
 	std::vector<adac::BpGroupHost> groups;
+	std::vector<uint32_t> group_seg;
 	uint64_t run = 0;
 	for (uint64_t s = 0; s < nseg; s++) {
 		if (block_offs[s] & 15) {
@@ -1266,20 +1271,26 @@ extern "C" adac_status adac_bp_layout_create(adac_ctx *c, int physical_type, con
 		for (uint64_t r = 0; r < counts[s]; r += 2048) {
 			const uint32_t rows = (uint32_t)(counts[s] - r < 2048 ? counts[s] - r : 2048);
 			groups.push_back(adac::BpGroupHost {block_offs[s], off + r, (uint32_t)(r / 2048), rows, 0, 0, 0, 0, 0});
+			group_seg.push_back((uint32_t)s);
 		}
 		run = off + counts[s];
+		if (run > l->value_span) l->value_span = run;
 		l->total_values += counts[s];
 	}
 	l->ngroups = groups.size();
-	if (l->ngroups >= 0x7fffffffull) {
+	if (l->ngroups >= 0x7fffffffull || nseg > 0xffffffffull) {
 		adac_bp_layout_destroy(l);
 		return ADAC_ERR_INVALID_ARGUMENT;
 	}
 	hipError_t e = hipSetDevice(c->device);
 	if (e == hipSuccess) e = hipMalloc(&l->d_groups, (l->ngroups ? l->ngroups : 1) * sizeof(adac::BpGroupHost));
+	if (e == hipSuccess) e = hipMalloc((void **)&l->d_group_seg, (l->ngroups ? l->ngroups : 1) * sizeof(uint32_t));
 	if (e == hipSuccess) e = hipMalloc((void **)&l->d_block_offs, (nseg ? nseg : 1) * sizeof(uint64_t));
 	if (e == hipSuccess && l->ngroups)
 		e = hipMemcpyAsync(l->d_groups, groups.data(), l->ngroups * sizeof(adac::BpGroupHost), hipMemcpyHostToDevice,
+		                   c->stream);
+	if (e == hipSuccess && l->ngroups)
+		e = hipMemcpyAsync(l->d_group_seg, group_seg.data(), l->ngroups * sizeof(uint32_t), hipMemcpyHostToDevice,
 		                   c->stream);
 	if (e == hipSuccess && nseg)
 		e = hipMemcpyAsync(l->d_block_offs, block_offs, nseg * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
@@ -1297,6 +1308,7 @@ extern "C" void adac_bp_layout_destroy(adac_bp_layout *l) {
 	if (!l) return;
 	(void)hipSetDevice(l->ctx->device);
 	if (l->d_groups) (void)hipFree(l->d_groups);
+	if (l->d_group_seg) (void)hipFree(l->d_group_seg);
 	if (l->d_block_offs) (void)hipFree(l->d_block_offs);
 	adac_ctx *c = l->ctx;
 	delete l;
@@ -1305,6 +1317,7 @@ extern "C" void adac_bp_layout_destroy(adac_bp_layout *l) {
 
 extern "C" uint64_t adac_bp_layout_ngroups(const adac_bp_layout *l) { return l ? l->ngroups : 0; }
 extern "C" uint64_t adac_bp_layout_total_values(const adac_bp_layout *l) { return l ? l->total_values : 0; }
+extern "C" uint64_t adac_bp_layout_value_span(const adac_bp_layout *l) { return l ? l->value_span : 0; }
 
 extern "C" adac_status adac_bp_bind(adac_bp_layout *l, const void *d_blocks) {
 	if (!l || (!d_blocks && l->total_values) || !aligned16(d_blocks)) return ADAC_ERR_INVALID_ARGUMENT;
@@ -1350,6 +1363,81 @@ extern "C" adac_status adac_bp_fetch_rows(adac_bp_layout *l, const void *d_block
 	if (!d_blocks || !d_segs || !d_rows || !d_out || !aligned16(d_blocks)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	ADAC_HIP(adac::launch_bp_fetch(l->ctx->stream, l->type_size, l->d_block_offs, d_blocks, d_segs, d_rows, n, d_out));
+	return ADAC_OK;
+}
+
+// ---- fused scans on BITPACKING blocks (adac_bp_scans.inl): nothing is decoded to HBM ----
+
+// argument checks of adac_bp_unpack + the implicit bind; d_res: the per-segment result array of the call
+static adac_status bp_scan_begin(adac_bp_layout *l, const void *d_blocks, const void *d_res) {
+	if (!l || (l->nseg && !d_res) || (l->total_values && !d_blocks)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (!aligned16(d_blocks)) return ADAC_ERR_INVALID_ARGUMENT;
+	ADAC_HIP(hipSetDevice(l->ctx->device));
+	return ADAC_OK;
+}
+
+static adac_status bp_scan_bind(adac_bp_layout *l, const void *d_blocks) {
+	if (l->total_values && l->bound_blocks != d_blocks) return adac_bp_bind(l, d_blocks);
+	return ADAC_OK;
+}
+
+extern "C" adac_status adac_bp_scan_sum(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_validity,
+                                        uint64_t *d_sums) {
+	adac_status st = bp_scan_begin(l, d_blocks, d_sums);
+	if (st != ADAC_OK || l->nseg == 0) return st;
+	if ((st = bp_scan_bind(l, d_blocks)) != ADAC_OK) return st;
+	// every wave adds its part: the sums start from zero (this also writes the segments without rows)
+	ADAC_HIP(hipMemsetAsync(d_sums, 0, l->nseg * sizeof(uint64_t), l->ctx->stream));
+	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, l->type_size, l->is_signed, adac::kBpScanOpSum, l->d_groups,
+	                              l->d_group_seg, l->ngroups, d_blocks, d_validity, 0, 0, d_sums, nullptr));
+	return ADAC_OK;
+}
+
+static adac_status bp_scan_range(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_validity, uint64_t lo,
+                                 uint64_t hi, uint64_t *d_counts, uint64_t *d_bitmap, bool want_bitmap) {
+	adac_status st = bp_scan_begin(l, d_blocks, d_counts);
+	if (st != ADAC_OK) return st;
+	if (want_bitmap && ((l->value_span && !d_bitmap) || (d_bitmap && d_bitmap == d_validity))) {
+		return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	if (l->nseg == 0) return ADAC_OK;
+	// order-preserving map of T onto unsigned numbers: flip the sign bit of the signed types
+	const uint64_t umask = adac::type_mask(l->type_size);
+	const uint64_t sbit = adac::type_sign_bit(l->type_size, l->is_signed);
+	const uint64_t blo = (lo & umask) ^ sbit, bhi = (hi & umask) ^ sbit;
+	if (want_bitmap && l->value_span) {
+		ADAC_HIP(hipMemsetAsync(d_bitmap, 0, ((l->value_span + 63) / 64) * sizeof(uint64_t), l->ctx->stream));
+	}
+	ADAC_HIP(hipMemsetAsync(d_counts, 0, l->nseg * sizeof(uint64_t), l->ctx->stream));
+	if (bhi < blo) return ADAC_OK; // empty range: all counts (and bits) are zero
+	if ((st = bp_scan_bind(l, d_blocks)) != ADAC_OK) return st;
+	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, l->type_size, l->is_signed, adac::kBpScanOpRange, l->d_groups,
+	                              l->d_group_seg, l->ngroups, d_blocks, d_validity, blo, bhi - blo, d_counts,
+	                              want_bitmap ? d_bitmap : nullptr));
+	return ADAC_OK;
+}
+
+extern "C" adac_status adac_bp_scan_count_between(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_validity,
+                                                  uint64_t lo, uint64_t hi, uint64_t *d_counts) {
+	return bp_scan_range(l, d_blocks, d_validity, lo, hi, d_counts, nullptr, false);
+}
+
+extern "C" adac_status adac_bp_scan_select_between(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_validity,
+                                                   uint64_t lo, uint64_t hi, uint64_t *d_bitmap, uint64_t *d_counts) {
+	return bp_scan_range(l, d_blocks, d_validity, lo, hi, d_counts, d_bitmap, true);
+}
+
+extern "C" adac_status adac_bp_scan_min_max(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_validity,
+                                            uint64_t *d_minmax) {
+	adac_status st = bp_scan_begin(l, d_blocks, d_minmax);
+	if (st != ADAC_OK || l->nseg == 0) return st;
+	if ((st = bp_scan_bind(l, d_blocks)) != ADAC_OK) return st;
+	// the scan works in the ordered domain bits ^ signbit from the empty interval [all-ones, 0]; a kernel over the
+	// segments maps the cells back to T's bits
+	ADAC_HIP(adac::launch_minmax_init(l->ctx->stream, d_minmax, l->nseg));
+	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, l->type_size, l->is_signed, adac::kBpScanOpMinMax, l->d_groups,
+	                              l->d_group_seg, l->ngroups, d_blocks, d_validity, 0, 0, d_minmax, nullptr));
+	ADAC_HIP(adac::launch_bp_scan_minmax_finish(l->ctx->stream, l->type_size, l->is_signed, d_minmax, l->nseg));
 	return ADAC_OK;
 }
 

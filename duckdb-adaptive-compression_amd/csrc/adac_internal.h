@@ -248,5 +248,13 @@ hipError_t launch_bp_unpack_range(hipStream_t s, uint32_t type_size, const void 
                                   void *d_out);
 hipError_t launch_bp_fetch(hipStream_t s, uint32_t type_size, const uint64_t *d_block_offs, const void *d_blocks,
                            const uint32_t *d_segs, const uint32_t *d_rows, uint64_t n, void *d_out);
+// fused scans on the block images (adac_bp_scans.inl); op values match kBpScanSum / Range / MinMax there.  d_res:
+// sums | counts | min, max pairs; the caller has filled it (and the bitmap) — see the kernel's header
+enum : int { kBpScanOpSum = 0, kBpScanOpRange = 1, kBpScanOpMinMax = 2 };
+hipError_t launch_bp_scan(hipStream_t s, uint32_t type_size, bool is_signed, int op, const void *d_groups,
+                          const uint32_t *d_group_seg, uint64_t ngroups, const void *d_blocks,
+                          const uint64_t *d_validity, uint64_t blo, uint64_t bspan, uint64_t *d_res, uint64_t *d_bitmap);
+hipError_t launch_bp_scan_minmax_finish(hipStream_t s, uint32_t type_size, bool is_signed, uint64_t *d_minmax,
+                                        uint64_t nseg);
 
 } // namespace adac

@@ -1946,6 +1946,7 @@ hipError_t dispatch_size(uint32_t type_size, F &&f) {
 }
 
 #include "adac_bitpacking.inl"
+#include "adac_bp_scans.inl"
 #include "adac_select_gather.inl"
 #include "adac_block_image.inl"
 #include "adac_encode_1p.inl"
@@ -2368,6 +2369,51 @@ hipError_t launch_bp_fetch(hipStream_t s, uint32_t type_size, const uint64_t *d_
 		                   static_cast<U *>(d_out));
 		return hipGetLastError();
 	});
+}
+
+// Fused scans on BITPACKING blocks: a wave walks `per_wave` consecutive groups; the grid is sized so that a whole
+// device holds it at once (8 workgroups = 32 waves per CU) and every wave gets about the same number of groups.
+hipError_t launch_bp_scan(hipStream_t s, uint32_t type_size, bool is_signed, int op, const void *d_groups,
+                          const uint32_t *d_group_seg, uint64_t ngroups, const void *d_blocks,
+                          const uint64_t *d_validity, uint64_t blo, uint64_t bspan, uint64_t *d_res, uint64_t *d_bitmap) {
+	static_assert(kBpScanOpSum == kBpScanSum && kBpScanOpRange == kBpScanRange && kBpScanOpMinMax == kBpScanMinMax, "ops");
+	if (ngroups == 0) return hipSuccess;
+	constexpr uint64_t kWaves = kWorkgroup / 64;
+	const uint64_t cap = device_cus() * 8 * kWaves;
+	BpScanArgs a;
+	const BpGroup *groups = static_cast<const BpGroup *>(d_groups);
+	a.ngroups = (uint32_t)ngroups;
+	a.per_wave = (uint32_t)((ngroups + cap - 1) / cap);
+	a.blocks = static_cast<const uint8_t *>(d_blocks);
+	a.validity = d_validity;
+	a.sbit = type_sign_bit(type_size, is_signed);
+	a.blo = blo;
+	a.bspan = bspan;
+	a.res = reinterpret_cast<unsigned long long *>(d_res);
+	a.bitmap = reinterpret_cast<unsigned long long *>(d_bitmap);
+	const uint64_t nwaves = (ngroups + a.per_wave - 1) / a.per_wave;
+	const dim3 grid((unsigned)((nwaves + kWaves - 1) / kWaves));
+	return dispatch_size(type_size, [&](auto tag) {
+		using U = decltype(tag);
+#define ADAC_BP_SCAN(OP)                                                                                               \
+	do {                                                                                                               \
+		if (d_validity) hipLaunchKernelGGL((k_bp_scan<U, OP, true>), grid, dim3(kWorkgroup), 0, s, groups, d_group_seg, a); \
+		else hipLaunchKernelGGL((k_bp_scan<U, OP, false>), grid, dim3(kWorkgroup), 0, s, groups, d_group_seg, a);      \
+	} while (0)
+		if (op == kBpScanSum) ADAC_BP_SCAN(kBpScanSum);
+		else if (op == kBpScanRange) ADAC_BP_SCAN(kBpScanRange);
+		else ADAC_BP_SCAN(kBpScanMinMax);
+#undef ADAC_BP_SCAN
+		return hipGetLastError();
+	});
+}
+
+hipError_t launch_bp_scan_minmax_finish(hipStream_t s, uint32_t type_size, bool is_signed, uint64_t *d_minmax,
+                                        uint64_t nseg) {
+	if (nseg == 0) return hipSuccess;
+	hipLaunchKernelGGL(k_bp_scan_minmax_finish, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, s, d_minmax, nseg,
+	                   type_mask(type_size), type_sign_bit(type_size, is_signed));
+	return hipGetLastError();
 }
 
 hipError_t launch_gather_selected(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs,

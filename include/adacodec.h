@@ -399,7 +399,8 @@ adac_status adac_blocks_read(adac_ctx *ctx, int physical_type, const adac_segmen
                              const uint64_t *block_offs, uint64_t nseg, const void *d_blocks, uint64_t *d_words);
 
 /* ---------------------------------------------------------------------------------------------
- * DuckDB BITPACKING segments — the persistent counterpart of the succinct codec, decode side.
+ * DuckDB BITPACKING segments — the persistent counterpart of the succinct codec: decode, fused
+ * filter / aggregate scans (adac_bp_scan_*) and compress.
  * A segment is the block image DuckDB's checkpoint writes (src/storage/compression/bitpacking.cpp:357-538):
  * metadata groups of 2048 rows in CONSTANT / CONSTANT_DELTA / DELTA_FOR / FOR mode, packed with fastpforlib.
  * Replaces BitpackingScanPartial / BitpackingScan (:736-826) and BitpackingFetchRow (:827-870).
@@ -414,6 +415,8 @@ adac_status adac_bp_layout_create(adac_ctx *ctx, int physical_type, const uint64
 void adac_bp_layout_destroy(adac_bp_layout *l);
 uint64_t adac_bp_layout_ngroups(const adac_bp_layout *l);
 uint64_t adac_bp_layout_total_values(const adac_bp_layout *l);
+/* elements an output / validity mask / bitmap over this layout spans: max(out_off + count) */
+uint64_t adac_bp_layout_value_span(const adac_bp_layout *l);
 /* Parse every group's header (mode, width, frame of reference, payload position) out of the block images into
  * the layout's device table — the analogue of BitpackingScanState::LoadNextGroup (bitpacking.cpp:597-640) for all
  * groups at once.  adac_bp_unpack binds by itself when handed a different buffer; call this again after
@@ -430,6 +433,32 @@ adac_status adac_bp_unpack_range(adac_bp_layout *l, const void *d_blocks, uint64
 /* d_out[k] = row d_rows[k] of segment d_segs[k] */
 adac_status adac_bp_fetch_rows(adac_bp_layout *l, const void *d_blocks, const uint32_t *d_segs, const uint32_t *d_rows,
                                uint64_t n, void *d_out);
+
+/* Fused filter / aggregate scans on the block images: nothing is decoded to HBM.  The BITPACKING counterparts of
+ * adac_scan_sum_valid / adac_scan_count_between_valid / adac_scan_select_between and of adac_zonemap's typed
+ * min / max.  Every result equals the same aggregate taken over what adac_bp_unpack returns for these bytes.
+ * Element index space: bit e of d_validity / d_bitmap is element out_offs[seg] + row, where adac_bp_unpack writes
+ * that row.  d_validity == NULL: every row; a row whose bit is clear takes no part in any result.
+ * All four enqueue on the layout's stream and do not synchronise (they bind like adac_bp_unpack when handed a
+ * different buffer); d_sums / d_counts (nseg words), d_minmax (2 * nseg words) and d_bitmap
+ * (ceil(value_span / 64) words) are fully written by the call, nothing is pre-cleared by the caller.
+ * A CONSTANT or CONSTANT_DELTA group is answered from its header, a FOR group whose [frame, frame + 2^width)
+ * interval misses or lies inside [lo, hi] from its header and the mask: no payload byte is read for them. */
+/* d_sums[seg] = sum of the values widened to 64 bits by T's signedness, mod 2^64 (adac_scan_sum's rule) */
+adac_status adac_bp_scan_sum(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_validity, uint64_t *d_sums);
+/* lo / hi: bit patterns of T, zero-extended; lo <= v <= hi in T's own order (signed for the INT types), lo > hi in
+ * that order selects nothing (adac_scan_count_between's rule).  d_counts[seg] = rows selected. */
+adac_status adac_bp_scan_count_between(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_validity,
+                                       uint64_t lo, uint64_t hi, uint64_t *d_counts);
+/* + the selection bitmap: bits of elements no segment covers are zero; must not alias d_validity; usable as the
+ * d_validity of a second call on a layout with the same out_offs or of a succinct scan sharing the element space.
+ * Output ranges of different segments must not overlap. */
+adac_status adac_bp_scan_select_between(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_validity,
+                                        uint64_t lo, uint64_t hi, uint64_t *d_bitmap, uint64_t *d_counts);
+/* d_minmax[2 * seg], d_minmax[2 * seg + 1] = min, max in T's order as bit patterns of T zero-extended; a segment
+ * without a selected row reports the empty interval min = T's maximum, max = T's minimum (adac_zonemap's convention) */
+adac_status adac_bp_scan_min_max(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_validity,
+                                 uint64_t *d_minmax);
 
 /* Compress side (BitpackingCompress / BitpackingFinalizeCompress, bitpacking.cpp:514-538): per-group statistics
  * on the device, the mode decision of BitpackingState::Flush (:229-294) and the sequential placement of groups
