@@ -421,6 +421,98 @@ def q1_packed(adac, n=59_986_052):
     return out
 
 
+def q1_filtered_packed(adac, n=59_986_052):
+    """Q1 with its WHERE clause on packed columns: q1_packed's columns plus an int32 l_shipdate in days.  One
+    adac_scan_select_between (l_shipdate <= cutoff, about 98 % of the rows as in Q1) writes a selection bitmap, then one
+    adac_scan_group_sum_valid per aggregated column under that bitmap; nothing is decoded.  Checked against numpy's
+    GROUP BY over the kept rows before anything is timed.  Beside the masked time of every column: the unmasked
+    adac_scan_group_sum of the same column in the same process, an all-ones and a 50 %-random bitmap, and what a
+    bitmap costs the plain fused SUM (adac_scan_sum_valid with all ones over adac_scan_sum) on that column."""
+    ctx = adac.Context(0)
+    rng = np.random.default_rng(1992)
+    code = rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8)
+    cols = {"l_quantity": rng.integers(1, 51, size=n).astype(np.int32),
+            "l_extendedprice": rng.integers(90_000, 10_495_000, size=n).astype(np.int32),
+            "l_partkey": rng.integers(1, 2_000_001, size=n).astype(np.int32)}
+    shipdate = rng.integers(8036, 10562, size=n).astype(np.int32)       # days since 1970: 1992-01-02 .. 1998-12-01
+    cutoff = 10511                                                     # the 98th percentile of the uniform dates
+    counts = adac.appender_segment_counts(n, 4)
+
+    def enc_col(v):
+        lay = adac.Layout(ctx, v.dtype, counts)
+        d_vals = ctx.upload(v)
+        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
+        lay.encode(d_vals, d_words)
+        ctx.sync()
+        descs = lay.get_descs()
+        nbytes = int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
+        return lay, d_words, nbytes, sorted(set(descs["width"].tolist()))
+
+    reps = 20
+
+    def timed(fn):
+        fn()
+        ctx.timer_start()
+        for _ in range(reps):
+            fn()
+        return ctx.timer_stop() / reps
+
+    klay, kwords, kbytes, kwidths = enc_col(code)
+    dlay, dwords, dbytes, dwidths = enc_col(shipdate)
+    nw = (n + 63) // 64
+    d_filter = ctx.alloc(nw * 8 + 8)
+    d_selcnt = ctx.alloc(len(counts) * 8)
+    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
+    select = lambda: dlay.scan_select_between(dwords, int_min, cutoff, d_filter, d_selcnt)
+    select()
+    ctx.sync()
+    keep = shipdate <= cutoff
+    assert int(d_selcnt.download(np.uint64, len(counts)).sum()) == int(keep.sum()), "filter parity"
+    half = rng.random(n) < 0.5
+    pad = np.zeros(nw * 64 - n, dtype=bool)
+    d_half = ctx.upload(np.packbits(np.concatenate([half, pad]), bitorder="little").view(np.uint64))
+    d_ones = ctx.upload(np.full(nw, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64))
+    d_sums, d_cnts = ctx.alloc(7 * 8), ctx.alloc(7 * 8)
+    d_seg = ctx.alloc(len(counts) * 8)
+
+    def grouped(v, m):
+        bins = [(code == g) & m for g in range(6)] + [(code >= 6) & m]     # [6]: the overflow entry (empty here)
+        return [int(v[b].astype(np.int64).sum()) & 0xFFFFFFFFFFFFFFFF for b in bins], [int(b.sum()) for b in bins]
+
+    out = {"rows": n, "groups": 6, "cutoff_day": cutoff, "selected_rows": int(keep.sum()),
+           "selected_fraction": float(keep.mean()), "key_widths": kwidths, "date_widths": dwidths,
+           "filter_ms": timed(select), "filter_packed_bytes": dbytes, "columns": []}
+    total_masked = total_plain = 0.0
+    for name, v in cols.items():
+        lay, words, nbytes, widths = enc_col(v)
+        for d_mask, m in ((d_filter, keep), (d_half, half), (d_ones, np.ones(n, dtype=bool)), (None, np.ones(n, dtype=bool))):
+            lay.scan_group_sum_valid(words, klay, kwords, d_mask, 6, d_sums, d_cnts)
+            ctx.sync()
+            assert (d_sums.download(np.uint64, 7).tolist(), d_cnts.download(np.uint64, 7).tolist()) == grouped(v, m), "Q1 parity"
+        ms_plain = timed(lambda: lay.scan_group_sum(words, klay, kwords, 6, d_sums, d_cnts))
+        ms_filter = timed(lambda: lay.scan_group_sum_valid(words, klay, kwords, d_filter, 6, d_sums, d_cnts))
+        ms_ones = timed(lambda: lay.scan_group_sum_valid(words, klay, kwords, d_ones, 6, d_sums, d_cnts))
+        ms_half = timed(lambda: lay.scan_group_sum_valid(words, klay, kwords, d_half, 6, d_sums, d_cnts))
+        ms_sum = timed(lambda: lay.scan_sum(words, d_seg))
+        ms_sum_ones = timed(lambda: lay.scan_sum(words, d_seg, d_ones))
+        total_masked += ms_filter
+        total_plain += ms_plain
+        out["columns"].append({"column": name, "widths": widths, "packed_bytes": nbytes,
+                               "group_sum_ms": ms_plain, "group_sum_filtered_ms": ms_filter,
+                               "group_sum_all_ones_ms": ms_ones, "group_sum_half_random_ms": ms_half,
+                               "scan_sum_ms": ms_sum, "scan_sum_all_ones_ms": ms_sum_ones,
+                               "grouped_mask_ratio": ms_ones / ms_plain, "fused_sum_mask_ratio": ms_sum_ones / ms_sum,
+                               "ratio_gap": ms_ones / ms_plain - ms_sum_ones / ms_sum})
+        del lay, words
+    out["q1_filtered_ms"] = out["filter_ms"] + total_masked
+    out["q1_unfiltered_three_aggregates_ms"] = total_plain
+    out["note"] = ("q1_filtered = one selection scan over l_shipdate + three grouped scans under its bitmap; "
+                   "grouped_mask_ratio = all-ones bitmap over no bitmap, fused_sum_mask_ratio = the same for the plain "
+                   "fused SUM; the target is ratio_gap <= 0.10")
+    ctx.close()
+    return out
+
+
 def product_form_groups(descs_a, descs_b, type_size=4, signed=True):
     """Which form of k_scan_product takes how many scan groups of `a` — product_fast_eligible (adac_sum_product.inl)
     evaluated on the host descriptors, with the default grouping of ensure_scan_groups."""
@@ -582,6 +674,7 @@ def main():
             "bitpacking_scan": lambda: bitpacking_scan(adac), "q6_packed": lambda: q6_packed(adac),
             "bitpacking_fused_scans": lambda: bitpacking_fused_scans(adac),
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
+            "q1_filtered_packed": lambda: q1_filtered_packed(adac),
             "c1_lookups": lambda: c1_lookups(adac, wl)}
     res = {k: f() for k, f in jobs.items() if not only or k in only}
     print(json.dumps(res))

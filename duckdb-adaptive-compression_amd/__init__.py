@@ -163,6 +163,7 @@ SIGNATURES = {
     "adac_event_destroy": (None, [_vp]),
     "adac_scan_sum": (_int, [_vp, _vp, _vp]),
     "adac_scan_group_sum": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "adac_scan_group_sum_valid": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "adac_scan_sum_product": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "adac_scan_count_eq": (_int, [_vp, _vp, _u64, _vp]),
     "adac_scan_count_between": (_int, [_vp, _vp, _u64, _u64, _vp]),
@@ -535,6 +536,12 @@ class Layout:
         """SUM(self) and COUNT(*) GROUP BY `keys` (a Layout over the same rows); ngroups + 1 results each."""
         _check(lib().adac_scan_group_sum(self._h, _dptr(d_words), keys._h, _dptr(d_key_words), int(ngroups),
                                          _dptr(d_sums), _dptr(d_counts)), "adac_scan_group_sum")
+
+    def scan_group_sum_valid(self, d_words, keys, d_key_words, d_validity, ngroups, d_sums, d_counts):
+        """scan_group_sum over the rows whose bit is set in d_validity, a mask in THIS layout's element space (e.g. the
+        bitmap of scan_select_between; None = every row)."""
+        _check(lib().adac_scan_group_sum_valid(self._h, _dptr(d_words), keys._h, _dptr(d_key_words), _dptr(d_validity),
+                                               int(ngroups), _dptr(d_sums), _dptr(d_counts)), "adac_scan_group_sum_valid")
 
     def scan_sum_product(self, d_words, other, d_other_words, d_sums, d_validity=None):
         """SUM(self * other) per segment (`other`: a Layout over the same rows; each value widened by its own type's

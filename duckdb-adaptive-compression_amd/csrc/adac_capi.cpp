@@ -1105,9 +1105,19 @@ extern "C" adac_status adac_scan_sum_product(adac_layout *a, const uint64_t *d_a
 }
 
 // SUM(value), COUNT(*) GROUP BY key over two packed columns of one table (Q1's shape, TPCH_runtime.txt:2-6)
+extern "C" adac_status adac_scan_group_sum_valid(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
+                                                 const uint64_t *d_key_words, const uint64_t *d_validity, uint32_t ngroups,
+                                                 uint64_t *d_sums, uint64_t *d_counts);
 extern "C" adac_status adac_scan_group_sum(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
                                            const uint64_t *d_key_words, uint32_t ngroups, uint64_t *d_sums,
                                            uint64_t *d_counts) {
+	return adac_scan_group_sum_valid(values, d_value_words, keys, d_key_words, nullptr, ngroups, d_sums, d_counts);
+}
+
+// ... restricted to the rows whose bit is set in d_validity (the value layout's element space; NULL = every row)
+extern "C" adac_status adac_scan_group_sum_valid(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
+                                                 const uint64_t *d_key_words, const uint64_t *d_validity, uint32_t ngroups,
+                                                 uint64_t *d_sums, uint64_t *d_counts) {
 	if (!values || !keys || values->ctx != keys->ctx || !d_sums || !d_counts) return ADAC_ERR_INVALID_ARGUMENT;
 	if (ngroups == 0 || ngroups > adac::group_sum_max_groups()) return ADAC_ERR_INVALID_ARGUMENT;
 	if (values->counts != keys->counts) return ADAC_ERR_INVALID_ARGUMENT; // the same rows, segment by segment
@@ -1123,7 +1133,7 @@ extern "C" adac_status adac_scan_group_sum(adac_layout *values, const uint64_t *
 	ADAC_HIP(adac::launch_group_sum(values->ctx->stream, values->type_size, values->is_signed, keys->type_size,
 	                                values->d_descs, values->d_tiles, values->ntiles, values->d_groups, values->ngroups,
 	                                d_value_words, keys->d_descs, d_key_words, ngroups, values->d_group_partial,
-	                                values->group_calls++, d_sums, d_counts));
+	                                values->group_calls++, d_validity, d_sums, d_counts));
 	return ADAC_OK;
 }
 

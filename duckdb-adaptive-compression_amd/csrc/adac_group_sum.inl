@@ -15,12 +15,21 @@
 // partial {sum, count} per bin, and k_group_final adds the partials — no global atomics on a handful of addresses.
 // Semantics: key = the key column's value as an unsigned number of its own width; rows whose key >= ngroups land in
 // bin `ngroups`.  SUM = the values widened to 64 bits by the value type's signedness, mod 2^64 (adac_scan_sum's rule).
+// Both scan kernels have a masked form (template parameter V, adac_scan_group_sum_valid): a row whose bit is clear in
+// the selection / validity bitmap — indexed in the VALUE layout's element space, val_off + row — is added to no bin.
+// The unmasked instantiations evaluate nothing of it.
 
 constexpr uint32_t kGroupStageBytes = 3584;   // packed bytes of one column per stage
 constexpr uint32_t kGroupChunksPerThread = (kGroupStageBytes / 16 + 1 + kWorkgroup - 1) / kWorkgroup;
 constexpr uint32_t kGroupCopies = 16;         // bin sets per wave (lane & 15 picks one): 4 lanes share a set (8 sets: slower)
 constexpr uint32_t kGroupPrivateBins = 8;     // bins held per thread
 constexpr uint32_t kGroupMaxBins = 257;       // 256 groups + overflow
+// masked form of k_group_sum: a stage's mask words travel with it (one word per thread, two LDS buffers).  A stage is
+// capped at this many rows (it only binds below 4 bits: (3584 * 8 - 256) / 4 = 7104) so that the 2 KiB of mask words
+// still leave seven workgroups per CU
+constexpr uint32_t kGroupMaskStageRows = 8192;
+constexpr uint32_t kGroupMaskWords = kGroupMaskStageRows / 64 + 1; // from any bit phase of the first word
+static_assert(kGroupMaskWords <= kWorkgroup && kGroupMaskStageRows % kWorkgroup == 0, "one mask word per thread and stage");
 constexpr uint32_t kGroupMaxWorkgroups = 4096; // capacity of the partial buffer: 8 per CU of the register-walk kernel + 7 per CU of this one
 
 // the w-bit field at `bit` of a staged image, any w in 1..64: mlo / mhi = the low / high dword of the width mask.
@@ -70,6 +79,13 @@ struct GroupStage {
 	uint32_t vbit0, kbit0, vchunks, kchunks, wv, wk, m;
 };
 
+// the mask words of a stage's rows (masked form; the unmasked kernel carries the empty struct)
+struct GroupStageMask {
+	const uint64_t *src; // the word holding the bit of the stage's first row
+	uint32_t sh, words;  // that bit; words holding the bits of the m rows
+};
+struct GroupStageNoMask {};
+
 // ---- shared with k_group_sum_rw (below): who takes which segment pair
 constexpr uint32_t kGroupRwCopies = 32;                      // bin sets per wave (two lanes share a set)
 
@@ -109,13 +125,15 @@ __device__ __forceinline__ GroupRwPlan group_rw_eligible(const adac_segment_desc
 	return p;
 }
 
+template <bool V>
 __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_desc *__restrict__ vdescs,
                                                           const TileRef *__restrict__ vtiles, uint32_t ntiles,
                                                           const uint64_t *__restrict__ vwords,
                                                           const adac_segment_desc *__restrict__ kdescs,
                                                           const uint64_t *__restrict__ kwords, GroupSumTypes ty,
                                                           uint32_t ngroups, unsigned long long *__restrict__ partial,
-                                                          const unsigned long long *__restrict__ rw_fallback) {
+                                                          const unsigned long long *__restrict__ rw_fallback,
+                                                          const uint64_t *__restrict__ validity) {
 	// Runs after k_group_sum_rw (when that kernel was launched: rw_fallback != nullptr) and takes the segment pairs it
 	// left: none, almost always — then every workgroup leaves at once with zero partials.
 	if (rw_fallback != nullptr && *rw_fallback == 0ull) return; // uniform (k_group_final then leaves these partials out)
@@ -125,6 +143,9 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 	// aggregated and written to the other buffer after it, so a global round trip is always in flight
 	__shared__ uint4 vstage[2][kGroupStageBytes / 16 + 2];
 	__shared__ uint4 kstage[2][kGroupStageBytes / 16 + 2];
+	// V: the mask words of a stage's rows, fetched and parked with its chunks (a dependent global load per row inside the
+	// row loop would put a round trip into every one of its iterations)
+	__shared__ uint64_t mstage[2][V ? kGroupMaskWords + 1 : 1];
 	// bins: up to kGroupPrivateBins bins in kGroupCopies sets per wave, or one set of up to kGroupMaxBins bins
 	constexpr uint32_t kSets = (kWorkgroup / 64) * kGroupCopies;
 	constexpr uint32_t kBinSlots = kGroupPrivateBins * kSets > kGroupMaxBins ? kGroupPrivateBins * kSets : kGroupMaxBins;
@@ -170,7 +191,8 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 		rnn = fetch_ref(t + 2u * G);
 		done = 0;
 	};
-	auto next_stage = [&](GroupStage &g) -> bool {
+	using StageMask = std::conditional_t<V, GroupStageMask, GroupStageNoMask>;
+	auto next_stage = [&](GroupStage &g, StageMask &gm) -> bool {
 		if (mcur.valid) {
 			const uint32_t left = mcur.vd.count - mcur.r.first;
 			const uint32_t n = left < ty.v_tile_rows ? left : ty.v_tile_rows;
@@ -185,7 +207,16 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 		const uint32_t wmax = g.wv > g.wk ? g.wv : g.wk;
 		uint32_t per_stage = ((kGroupStageBytes * 8u - 256u) / wmax) & ~(uint32_t)(kWorkgroup - 1);
 		per_stage = per_stage < (uint32_t)kWorkgroup ? (uint32_t)kWorkgroup : per_stage;
+		if (V) per_stage = per_stage < kGroupMaskStageRows ? per_stage : kGroupMaskStageRows;
 		g.m = n - done < per_stage ? n - done : per_stage;
+		if constexpr (V) { // element index of the stage's first row, in 64 bits: val_off alone may exceed 2^32
+			const uint64_t e0 = mcur.vd.val_off + (uint64_t)(mcur.r.first + done);
+			gm.src = validity + (e0 >> 6);
+			gm.sh = (uint32_t)(e0 & 63u);
+			// a stage has g.m >= 1 rows (a tile exists only for rows: the chunk clamps `vchunks - 1u` rest on the same),
+			// so words is 1 .. kGroupMaskWords, every one of them holds the bit of a row, and `words - 1u` cannot wrap
+			gm.words = (gm.sh + g.m + 63u) >> 6;
+		}
 		const uint64_t vpos = (uint64_t)(mcur.r.first + done) * g.wv, kpos = (uint64_t)(mcur.r.first + done) * g.wk;
 		g.vsrc = reinterpret_cast<const uint4 *>(vwords + mcur.vd.word_off) + (vpos >> 7);
 		g.ksrc = reinterpret_cast<const uint4 *>(kwords + mcur.kd.word_off) + (kpos >> 7);
@@ -199,8 +230,10 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 		return true;
 	};
 	GroupStage cur, nxt;
-	bool have = next_stage(cur); // uniform
+	StageMask mk_cur, mk_nxt;
+	bool have = next_stage(cur, mk_cur); // uniform
 	uint4 vq[kGroupChunksPerThread], kq[kGroupChunksPerThread];
+	uint64_t mq = 0;
 	if (have) {
 #pragma unroll
 		for (uint32_t h = 0; h < kGroupChunksPerThread; h++) { // chunks <= kGroupStageBytes / 16 + 1: inside the buffer
@@ -208,11 +241,14 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 			if (c < cur.vchunks) vstage[0][c] = cur.vsrc[c];
 			if (c < cur.kchunks) kstage[0][c] = cur.ksrc[c];
 		}
+		if constexpr (V) {
+			if (tid < mk_cur.words) mstage[0][tid] = mk_cur.src[tid];
+		}
 	}
 	__syncthreads();
 	uint32_t buf = 0;
 	while (have) {
-		const bool more = next_stage(nxt);
+		const bool more = next_stage(nxt, mk_nxt);
 		if (more) { // in flight while this stage is aggregated.  UNCONDITIONAL loads (index clamped into the stage): a
 			// load under a per-lane condition gets a wait of its own and the round trips run one after the other
 #pragma unroll
@@ -221,9 +257,21 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 				vq[h] = nxt.vsrc[c < nxt.vchunks ? c : nxt.vchunks - 1u];
 				kq[h] = nxt.ksrc[c < nxt.kchunks ? c : nxt.kchunks - 1u];
 			}
+			if constexpr (V) mq = mk_nxt.src[tid < mk_nxt.words ? tid : mk_nxt.words - 1u]; // clamped: no word outside the stage's rows
 		}
 		const uint32_t *v32 = reinterpret_cast<const uint32_t *>(vstage[buf]);
 		const uint32_t *k32 = reinterpret_cast<const uint32_t *>(kstage[buf]);
+		const uint32_t *m32 = reinterpret_cast<const uint32_t *>(mstage[buf]);
+		// row r's bit is bit sh + r of the staged words.  (Evaluated under `if constexpr (V)` only: with a keep[] of
+		// constant ones in its row loop the unmasked kernel came out with 63 SGPR spills instead of 54.)
+		auto kept = [&](uint32_t r) -> uint32_t {
+			if constexpr (V) {
+				const uint32_t b = mk_cur.sh + r;
+				return (m32[b >> 5] >> (b & 31u)) & 1u;
+			} else {
+				return 1u;
+			}
+		};
 		// four rows per thread and round: the eight field reads are issued together, then the eight LDS adds (one row
 		// at a time the loop was a chain of LDS round trips: 0.22 ms for 60 M rows whatever the widths)
 		const uint32_t vmlo = cur.wv >= 32u ? 0xffffffffu : mask32(cur.wv), vmhi = cur.wv > 32u ? mask32(cur.wv - 32u) : 0u;
@@ -232,12 +280,14 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 		for (uint32_t row0 = tid; row0 < cur.m; row0 += 4u * kWorkgroup) {
 			if (narrow) { // uniform: both fields and both types fit 32 bits — half the arithmetic
 				uint32_t v[4], key[4];
+				[[maybe_unused]] uint32_t keep[4];
 #pragma unroll
 				for (int u = 0; u < 4; u++) {
 					const uint32_t row = row0 + (uint32_t)u * kWorkgroup;
 					const uint32_t rr = row < cur.m ? row : row0; // clamped: the read stays inside the stage
 					v[u] = staged_field32(v32, cur.vbit0 + rr * cur.wv, vmlo);
 					key[u] = staged_field32(k32, cur.kbit0 + rr * cur.wk, kmlo);
+					if constexpr (V) keep[u] = kept(rr);
 				}
 #pragma unroll
 				for (int u = 0; u < 4; u++) {
@@ -248,7 +298,7 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 					const uint32_t k = (key[u] + (uint32_t)cur.kadd) & (uint32_t)ty.k_tmask;
 					const uint32_t bin = k < ngroups ? k : ngroups;
 					const uint32_t slot = priv ? bin * kSets + my_set : bin;
-					if (row < cur.m) {
+					if (row < cur.m && (!V || keep[u])) {
 						atomicAdd(&bsum[slot], (unsigned long long)x64);
 						atomicAdd(&bcnt[slot], 1u);
 					}
@@ -256,12 +306,14 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 				continue;
 			}
 			uint64_t v[4], key[4];
+			[[maybe_unused]] uint32_t keep[4];
 #pragma unroll
 			for (int u = 0; u < 4; u++) {
 				const uint32_t row = row0 + (uint32_t)u * kWorkgroup;
 				const uint32_t rr = row < cur.m ? row : row0; // clamped: the read stays inside the stage
 				v[u] = staged_field(v32, cur.vbit0 + rr * cur.wv, vmlo, vmhi);
 				key[u] = staged_field(k32, cur.kbit0 + rr * cur.wk, kmlo, kmhi);
+				if constexpr (V) keep[u] = kept(rr);
 			}
 #pragma unroll
 			for (int u = 0; u < 4; u++) {
@@ -271,7 +323,7 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 				const uint64_t k = (key[u] + cur.kadd) & ty.k_tmask;
 				const uint32_t bin = k < (uint64_t)ngroups ? (uint32_t)k : ngroups;
 				const uint32_t slot = priv ? bin * kSets + my_set : bin;
-				if (row < cur.m) {
+				if (row < cur.m && (!V || keep[u])) {
 					atomicAdd(&bsum[slot], (unsigned long long)x); // ds_add_u64, no return: nothing waits for it
 					atomicAdd(&bcnt[slot], 1u);
 				}
@@ -284,9 +336,13 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 				if (c < nxt.vchunks) vstage[buf ^ 1u][c] = vq[h];
 				if (c < nxt.kchunks) kstage[buf ^ 1u][c] = kq[h];
 			}
+			if constexpr (V) {
+				if (tid < mk_nxt.words) mstage[buf ^ 1u][tid] = mq;
+			}
 		}
 		__syncthreads();
 		cur = nxt;
+		mk_cur = mk_nxt;
 		have = more;
 		buf ^= 1u;
 	}
@@ -408,11 +464,19 @@ constexpr uint32_t kGroupRwNarrowShift = 20;
 template <int W> constexpr bool kGroupRwNarrow = W <= 8;
 constexpr uint32_t kGroupRwWaveRows = 1008;                    // key rows a wave stages per round: two 8-row blocks per lane
 constexpr uint32_t kGroupRwWaveKeyBytes = kGroupRwWaveRows + 16 + 64; // + the block the round starts in + read slack
-template <int W, bool DIRECT>
+// V (the masked form): the two mask words of a chunk's rows travel with the chunk (ChunkMask, as in product_walk); one
+// 64-bit window from row i0 on covers the chunk (MAXV <= 32 rows).  A row whose bit is clear adds ZERO to its bin word:
+// the ds_add stays where it is and the loop stays free of branches (a test per row would put a compare, an exec-mask
+// save and restore around every one of up to 32 LDS adds).
+// Workgroups per CU (= waves per SIMD) each form is compiled for, and its grid is sized from: the unmasked walk holds
+// 72 VGPRs, the most that gives seven; the mask words (current and prefetched pair) take it past that.
+template <bool V> constexpr uint32_t kGroupRwResident = V ? 6u : 7u;
+template <int W, bool DIRECT, bool V>
 __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t count, const GroupRwPlan &plan,
                                               uint32_t wk, const uint4 *__restrict__ seg16,
                                               const uint32_t *__restrict__ kw32, uint32_t k_last_dword, uint32_t ngroups,
-                                              uint8_t *keys, unsigned long long *wbins) {
+                                              uint8_t *keys, unsigned long long *wbins,
+                                              const uint64_t *__restrict__ validity, uint64_t val_off) {
 	constexpr int MAXV = ChunkWindow<W>::MAXV;
 	constexpr int KD = (MAXV + 3 + 3) / 4;                         // dwords holding MAXV bytes from any byte offset
 	constexpr uint32_t LANES = (kGroupRwWaveRows * W / 128) < 64u ? (kGroupRwWaveRows * W / 128) : 64u; // chunks per round
@@ -429,6 +493,9 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 	uint4 q;
 	uint32_t e;
 	run.load(seg16, L, q, e);
+	const ChunkMask<W, V> vmask(validity, val_off, r1); // the value layout's element space
+	uint64_t vm0 = 0, vm1 = 0;
+	if (V) vmask.words(run.clamp(L), vm0, vm1);
 	// DIRECT: the two dwords of the key stream holding the keys of the rows that start in chunk Lx
 	auto direct_keys = [&](uint32_t Lx) {
 		uint32_t dw = (chunk_first_row<W>(Lx) * wk) >> 5;
@@ -465,6 +532,8 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 		uint4 qn;
 		uint32_t en;
 		run.load(seg16, L + LANES, qn, en);
+		uint64_t vn0 = 0, vn1 = 0;
+		if (V) vmask.words(run.clamp(L + LANES), vn0, vn1);
 		uint2 kqn = make_uint2(0u, 0u);
 		uint32_t kb0n = 0, nblocksn = 0;
 		if (DIRECT) {
@@ -494,7 +563,11 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 #pragma unroll
 				for (int i = 0; i < KD; i++) kn[i] = __builtin_amdgcn_alignbyte(raw[i + 1], raw[i], kofs & 3u);
 			}
+			// V: bit j = row i0 + j is kept (bits past the run's last row are unspecified: the boundary chunk tests cw.lim)
+			// (a chunk whose first row lies past the run has lim == 0: its window is never looked at)
+			const uint32_t vb = V ? (uint32_t)vmask.window(vm0, vm1, cw.i0) : 0xffffffffu;
 			auto add_row = [&](int j) {
+				const uint32_t m = V ? (uint32_t)__builtin_amdgcn_sbfe((int)vb, (uint32_t)j, 1u) : 0xffffffffu; // 0 / -1
 				uint32_t key;
 				if (DIRECT) {
 					key = plan.keys_overflow ? 255u : __builtin_amdgcn_ubfe(kwin, (uint32_t)j * wk, wk) + plan.kadd_byte;
@@ -504,10 +577,11 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 				const uint32_t bin = key < ngroups ? key : ngroups;
 				if (kGroupRwNarrow<W>) { // fields of at most 8 bits: rows << 20 | sum fits 32 bits, a ds_add_u32 is half the LDS work
 					uint32_t *slot = reinterpret_cast<uint32_t *>(my_bins32 + bin * (kGroupRwCopies * 4u));
-					atomicAdd(slot, (1u << kGroupRwNarrowShift) | field_of<W>(cw.nrm, j));
+					atomicAdd(slot, ((1u << kGroupRwNarrowShift) | field_of<W>(cw.nrm, j)) & m);
 				} else {
 					unsigned long long *slot = reinterpret_cast<unsigned long long *>(my_bins + bin * (kGroupRwCopies * 8u));
-					atomicAdd(slot, (1ull << kGroupRwCountShift) | (unsigned long long)field_of<W>(cw.nrm, j)); // ds_add_u64, no return
+					atomicAdd(slot, ((unsigned long long)((1u << (kGroupRwCountShift - 32u)) & m) << 32) |
+					                    (unsigned long long)(field_of<W>(cw.nrm, j) & m)); // ds_add_u64, no return
 				}
 			};
 			if (starting <= cw.lim) { // every row that starts in the chunk belongs to the quarter: no per-row test
@@ -523,6 +597,8 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 		}
 		q = qn;
 		e = en;
+		vm0 = vn0;
+		vm1 = vn1;
 		kq = kqn;
 		if (!DIRECT) { // the next round's key bytes (issued after this round's reads of the buffer)
 #pragma unroll
@@ -565,12 +641,12 @@ __device__ __forceinline__ void group_rw_fold(unsigned long long *wbins, unsigne
 	}
 }
 
-__global__ __launch_bounds__(kWorkgroup, 7) void k_group_sum_rw(const ScanGroup *__restrict__ vgroups, uint32_t ngroups_work,
-                                                                const uint64_t *__restrict__ vwords,
-                                                                const adac_segment_desc *__restrict__ kdescs,
-                                                                const uint64_t *__restrict__ kwords, GroupSumTypes ty,
-                                                                uint32_t ngroups, unsigned long long *__restrict__ partial,
-                                                                unsigned long long *__restrict__ fallback) {
+template <bool V>
+__global__ __launch_bounds__(kWorkgroup, kGroupRwResident<V>) void k_group_sum_rw(
+    const ScanGroup *__restrict__ vgroups, uint32_t ngroups_work, const uint64_t *__restrict__ vwords,
+    const adac_segment_desc *__restrict__ kdescs, const uint64_t *__restrict__ kwords, GroupSumTypes ty, uint32_t ngroups,
+    unsigned long long *__restrict__ partial, unsigned long long *__restrict__ fallback,
+    const uint64_t *__restrict__ validity) {
 	constexpr uint32_t kWaves = kWorkgroup / 64;
 	__shared__ __attribute__((aligned(16))) uint8_t keys[kWaves][kGroupRwWaveKeyBytes];
 	__shared__ unsigned long long bins[kWaves][kGroupPrivateBins * kGroupRwCopies];
@@ -600,11 +676,13 @@ __global__ __launch_bounds__(kWorkgroup, 7) void k_group_sum_rw(const ScanGroup 
 		const uint32_t maxv = (128u + g.d.width - 1u) / g.d.width;
 		if (maxv * wk <= 32u) { // uniform: the keys of a chunk's rows fit one dword
 			dispatch_width_4_32(g.d.width, [&](auto wc) __attribute__((always_inline)) {
-				group_rw_walk<decltype(wc)::value, true>(r0, r1, g.d.count, plan, wk, seg16, kw32, k_last, ngroups, keys[wave], bins[wave]);
+				group_rw_walk<decltype(wc)::value, true, V>(r0, r1, g.d.count, plan, wk, seg16, kw32, k_last, ngroups, keys[wave],
+				                                            bins[wave], validity, g.d.val_off);
 			});
 		} else {
 			dispatch_width_4_32(g.d.width, [&](auto wc) __attribute__((always_inline)) {
-				group_rw_walk<decltype(wc)::value, false>(r0, r1, g.d.count, plan, wk, seg16, kw32, k_last, ngroups, keys[wave], bins[wave]);
+				group_rw_walk<decltype(wc)::value, false, V>(r0, r1, g.d.count, plan, wk, seg16, kw32, k_last, ngroups, keys[wave],
+				                                             bins[wave], validity, g.d.val_off);
 			});
 		}
 		group_rw_fold(bins[wave], tot[wave], plan.vadd, g.d.width <= 8u);

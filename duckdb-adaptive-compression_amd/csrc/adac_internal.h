@@ -154,7 +154,7 @@ hipError_t launch_group_sum(hipStream_t s, uint32_t v_type_size, bool v_signed, 
                             const adac_segment_desc *d_vdescs, const TileRef *d_vtiles, uint64_t ntiles,
                             const ScanGroup *d_vgroups, uint64_t nvgroups, const uint64_t *d_vwords,
                             const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups, void *d_partial,
-                            uint32_t call_parity, uint64_t *d_sums, uint64_t *d_counts);
+                            uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums, uint64_t *d_counts);
 // SUM(a * b) over two packed columns of one table under a selection bitmap (adac_sum_product.inl)
 hipError_t launch_scan_sum_product(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
                                    const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,

@@ -2046,7 +2046,7 @@ hipError_t launch_group_sum(hipStream_t s, uint32_t v_type_size, bool v_signed, 
                             const adac_segment_desc *d_vdescs, const TileRef *d_vtiles, uint64_t ntiles,
                             const ScanGroup *d_vgroups, uint64_t nvgroups, const uint64_t *d_vwords,
                             const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups, void *d_partial,
-                            uint32_t call_parity, uint64_t *d_sums, uint64_t *d_counts) {
+                            uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums, uint64_t *d_counts) {
 	GroupSumTypes ty;
 	ty.v_tmask = type_mask(v_type_size);
 	ty.v_sbit = type_sign_bit(v_type_size, v_signed);
@@ -2057,16 +2057,21 @@ hipError_t launch_group_sum(hipStream_t s, uint32_t v_type_size, bool v_signed, 
 	unsigned long long *partial = static_cast<unsigned long long *>(d_partial);
 	unsigned long long *fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + (call_parity & 1u);
 	unsigned long long *next_fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + ((call_parity + 1u) & 1u);
-	// 1. the register-walk kernel over the value layout's scan groups (up to 8 bins; persistent, seven workgroups per CU);
-	//    it counts the segment pairs it cannot take in *fallback
+	// 1. the register-walk kernel over the value layout's scan groups (up to 8 bins; persistent, as many workgroups per
+	//    CU as its form is resident with: seven, six under a mask); it counts the segment pairs it cannot take in *fallback
 	uint32_t nwg_rw = 0;
 	const bool rw = nbins <= kGroupPrivateBins && !ty.wide_only && g_tuning.group_sum_rw && nvgroups > 0;
 	if (rw) {
-		const uint64_t cap = 7ull * device_cus();
+		const uint64_t cap = (uint64_t)(d_validity ? kGroupRwResident<true> : kGroupRwResident<false>) * device_cus();
 		nwg_rw = (uint32_t)(nvgroups < cap ? nvgroups : cap);
 		nwg_rw = nwg_rw < kGroupMaxWorkgroups / 2 ? nwg_rw : kGroupMaxWorkgroups / 2;
-		hipLaunchKernelGGL(k_group_sum_rw, dim3(nwg_rw), dim3(kWorkgroup), 0, s, d_vgroups, (uint32_t)nvgroups, d_vwords,
-		                   d_kdescs, d_kwords, ty, ngroups, partial, fallback);
+		if (d_validity) {
+			hipLaunchKernelGGL(k_group_sum_rw<true>, dim3(nwg_rw), dim3(kWorkgroup), 0, s, d_vgroups, (uint32_t)nvgroups,
+			                   d_vwords, d_kdescs, d_kwords, ty, ngroups, partial, fallback, d_validity);
+		} else {
+			hipLaunchKernelGGL(k_group_sum_rw<false>, dim3(nwg_rw), dim3(kWorkgroup), 0, s, d_vgroups, (uint32_t)nvgroups,
+			                   d_vwords, d_kdescs, d_kwords, ty, ngroups, partial, fallback, d_validity);
+		}
 		hipError_t e = hipGetLastError();
 		if (e != hipSuccess) return e;
 	}
@@ -2077,9 +2082,16 @@ hipError_t launch_group_sum(hipStream_t s, uint32_t v_type_size, bool v_signed, 
 	cap = cap < kGroupMaxWorkgroups / 2 ? cap : kGroupMaxWorkgroups / 2;
 	const uint32_t nwg = (uint32_t)(ntiles < cap ? ntiles : cap);
 	if (nwg) {
-		hipLaunchKernelGGL(k_group_sum, dim3(nwg), dim3(kWorkgroup), 0, s, d_vdescs, d_vtiles, (uint32_t)ntiles, d_vwords,
-		                   d_kdescs, d_kwords, ty, ngroups, partial + (uint64_t)nwg_rw * 2u * nbins,
-		                   rw ? fallback : static_cast<const unsigned long long *>(nullptr));
+		const unsigned long long *handed = rw ? fallback : static_cast<const unsigned long long *>(nullptr);
+		if (d_validity) {
+			hipLaunchKernelGGL(k_group_sum<true>, dim3(nwg), dim3(kWorkgroup), 0, s, d_vdescs, d_vtiles, (uint32_t)ntiles,
+			                   d_vwords, d_kdescs, d_kwords, ty, ngroups, partial + (uint64_t)nwg_rw * 2u * nbins, handed,
+			                   d_validity);
+		} else {
+			hipLaunchKernelGGL(k_group_sum<false>, dim3(nwg), dim3(kWorkgroup), 0, s, d_vdescs, d_vtiles, (uint32_t)ntiles,
+			                   d_vwords, d_kdescs, d_kwords, ty, ngroups, partial + (uint64_t)nwg_rw * 2u * nbins, handed,
+			                   d_validity);
+		}
 		hipError_t e = hipGetLastError();
 		if (e != hipSuccess) return e;
 	}

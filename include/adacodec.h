@@ -341,6 +341,22 @@ adac_status adac_scan_count_between(adac_layout *l, const uint64_t *d_words, uin
 adac_status adac_scan_group_sum(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
                                 const uint64_t *d_key_words, uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts);
 
+/* The same grouped aggregate restricted to the rows whose bit is set in d_validity — Q1's WHERE clause, or a nullable
+ * column: `SELECT key, SUM(value), COUNT(*) ... WHERE <filter> GROUP BY key` with the filter evaluated by
+ * adac_scan_select_between.  Bit e of word e / 64 of d_validity is element e = val_off + row of the VALUES layout
+ * (adac_scan_sum_product's convention); the key layout's value offsets play no part, so a bitmap that
+ * adac_scan_select_between wrote on any layout with the values layout's offsets can be passed straight in.
+ * A row whose bit is clear contributes to no sum and no count, the overflow entry [ngroups] included: the ngroups + 1
+ * counts add up to the number of set bits on rows that segments cover.  Bits that belong to no row (gaps between
+ * segments, bits past value_span in the last word) never influence a result, and the call reads no mask word outside
+ * the ceil(value_span / 64) words of the values layout.  d_validity == NULL: every row takes part, the result is
+ * adac_scan_group_sum's (which is this call with NULL).  Everything else is as there: the same argument checks,
+ * d_sums and d_counts (ngroups + 1 entries each) are fully written and need no clearing by the caller, the call
+ * enqueues on the context's stream and does not synchronise. */
+adac_status adac_scan_group_sum_valid(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
+                                      const uint64_t *d_key_words, const uint64_t *d_validity, uint32_t ngroups,
+                                      uint64_t *d_sums, uint64_t *d_counts);
+
 /* Product aggregate over TWO packed columns of one table — TPC-H Q6's `SUM(l_extendedprice * l_discount) WHERE ...`
  * without materialising either column.  `a` and `b` are layouts on the same context with the same row count per
  * segment (types, widths, placements and encode rules may differ; a == b with the same words gives the sum of squares).
