@@ -627,6 +627,169 @@ def q6_product_packed(adac, n=59_986_052):
     return out
 
 
+def group_product_form_groups(descs_a, descs_b, descs_k, ngroups, a_type=(4, True), b_type=(4, True), k_size=1):
+    """Which form of adac_scan_group_sum_product takes how many scan groups of `a` — group_product_rw_eligible
+    (adac_group_product.inl) evaluated on the host descriptors, with the default grouping of ensure_scan_groups.
+    a_type / b_type: (type size, signed); k_size: the key type's size."""
+    NO_MIN = 0xFFFFFFFFFFFFFFFF
+    tile, per = 16384 // a_type[0], {8: 12, 4: 6, 2: 8, 1: 4}[a_type[0]]
+
+    def frame(d, size, signed):
+        """the widened frame of reference when value = field + frame for every field (product_frame), else None"""
+        tb = 8 * size
+        tmask, sbit = (1 << tb) - 1, (1 << (tb - 1)) if signed else 0
+        if (int(d["flags"]) & 1) and int(d["min"]) != NO_MIN:
+            bmin = (int(d["min"]) & tmask) ^ sbit
+            return bmin - sbit if bmin + (1 << int(d["width"])) - 1 <= tmask else None
+        return 0 if sbit == 0 else None
+
+    def keys_ok(d):
+        wk, kmask = int(d["width"]), (1 << (8 * k_size)) - 1
+        if wk > 8:
+            return False
+        kadd = (int(d["min"]) & kmask) if (int(d["flags"]) & 1) and int(d["min"]) != NO_MIN else 0
+        top = kadd + (1 << wk) - 1
+        return top <= kmask and (top <= 255 or kadd >= ngroups)
+
+    out = {"fast": 0, "generic": 0}
+    for da, db, dk in zip(descs_a, descs_b, descs_k):
+        ntiles = (int(da["count"]) + tile - 1) // tile
+        if ntiles == 0:
+            continue
+        wa, wb = int(da["width"]), int(db["width"])
+        fast = (ngroups + 1 <= 8 and 4 <= wa <= 32 and 1 <= wb <= 32 and int(da["count"]) * wa < 2 ** 31
+                and int(db["count"]) * wb < 2 ** 31)
+        if fast:
+            ma, mb = frame(da, *a_type), frame(db, *b_type)
+            fast = (ma is not None and mb is not None and 0 <= ma and ma + (1 << wa) - 1 < 2 ** 32
+                    and 0 <= mb and mb + (1 << wb) - 1 < 2 ** 32 and keys_ok(dk))
+        out["fast" if fast else "generic"] += (ntiles + per - 1) // per
+    return out
+
+
+def q1_disc_price_packed(adac, n=59_986_052):
+    """Q1's sum_disc_price on packed columns: the columns of q1_filtered_packed that this plan reads (flag code,
+    l_extendedprice, l_shipdate; same shapes, a random stream of its own) plus an int32 l_discount in [0, 10].  One
+    adac_scan_select_between (l_shipdate <= cutoff) writes the bitmap; under it adac_scan_group_sum_valid(price) and
+    adac_scan_group_sum_product(price, disc) give SUM(price * (100 - disc)) = 100 SUM(price) - SUM(price * disc) per
+    group, checked against numpy before anything is timed.  Beside the new call, masked and unmasked, in the same
+    process: what a caller paid before (adac_unpack of the three columns, after which the multiply and the group-by are
+    still to do) and a lower bound for any walk of these columns (the grouped SUM of price + the masked SUM of disc)."""
+    ctx = adac.Context(0)
+    rng = np.random.default_rng(1993)
+    code = rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8)
+    price = rng.integers(90_000, 10_495_000, size=n).astype(np.int32)
+    shipdate = rng.integers(8036, 10562, size=n).astype(np.int32)
+    disc = rng.integers(0, 11, size=n).astype(np.int32)
+    cutoff = 10511
+    counts = adac.appender_segment_counts(n, 4)
+
+    def enc_col(v):
+        lay = adac.Layout(ctx, v.dtype, counts)
+        d_vals = ctx.upload(v)
+        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
+        lay.encode(d_vals, d_words)
+        ctx.sync()
+        descs = lay.get_descs()
+        nbytes = int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
+        return lay, d_words, nbytes, sorted(set(descs["width"].tolist())), descs
+
+    klay, kwords, kbytes, kwidths, kdescs = enc_col(code)
+    dlay, dwords, dbytes, dwidths, _ = enc_col(shipdate)
+    play, pwords, pbytes, pwidths, pdescs = enc_col(price)
+    clay, cwords, cbytes, cwidths, cdescs = enc_col(disc)
+    nw = (n + 63) // 64
+    d_filter = ctx.alloc(nw * 8 + 8)
+    d_selcnt = ctx.alloc(len(counts) * 8)
+    d_seg = ctx.alloc(len(counts) * 8)
+    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
+    select = lambda: dlay.scan_select_between(dwords, int_min, cutoff, d_filter, d_selcnt)
+    d_sp, d_cp = ctx.alloc(7 * 8), ctx.alloc(7 * 8)    # SUM(price), COUNT(*)
+    d_spd, d_cpd = ctx.alloc(7 * 8), ctx.alloc(7 * 8)  # SUM(price * disc), COUNT(*)
+    sum_price = lambda: play.scan_group_sum_valid(pwords, klay, kwords, d_filter, 6, d_sp, d_cp)
+    product = lambda: play.scan_group_sum_product(pwords, clay, cwords, klay, kwords, 6, d_spd, None, d_filter)
+
+    def plan():
+        select()
+        sum_price()
+        product()
+
+    keep = shipdate <= cutoff
+    bins = [(code == g) & keep for g in range(6)]
+    exp = [int((price[b].astype(np.int64) * (100 - disc[b])).sum()) for b in bins]
+
+    def parity(what):
+        ctx.sync()
+        sp, spd = d_sp.download(np.uint64, 7).tolist(), d_spd.download(np.uint64, 7).tolist()
+        assert [100 * sp[g] - spd[g] for g in range(6)] == exp and spd[6] == 0, what
+        assert d_cp.download(np.uint64, 7).tolist() == [int(b.sum()) for b in bins] + [0], what
+
+    plan()
+    parity("Q1 sum_disc_price parity")
+    play.scan_group_sum_product(pwords, clay, cwords, klay, kwords, 6, d_spd, d_cpd, d_filter)   # with counts
+    ctx.sync()
+    assert d_cpd.download(np.uint64, 7).tolist() == d_cp.download(np.uint64, 7).tolist(), "count parity"
+    play.scan_group_sum_product(pwords, clay, cwords, klay, kwords, 6, d_spd, d_cpd)             # NULL mask
+    ctx.sync()
+    allrows = [code == g for g in range(6)]
+    assert d_spd.download(np.uint64, 7).tolist() == [int((price[b].astype(np.int64) * disc[b]).sum()) for b in allrows] + [0]
+    assert d_cpd.download(np.uint64, 7).tolist() == [int(b.sum()) for b in allrows] + [0], "unmasked parity"
+    # every step is timed warm: 20 back-to-back repetitions after one untimed call.  The new call's working set (packed
+    # bytes of three columns + the mask, about 240 MB) can stay in the 256 MB Infinity Cache between repetitions, the
+    # unpacks' (the same packed bytes + 540 MB of output) cannot: the comparison favours the new call to that extent
+    reps = 20
+    d_out = ctx.alloc(n * 4 + 64)
+
+    def unpack_three():
+        play.unpack(pwords, d_out)
+        clay.unpack(cwords, d_out)
+        klay.unpack(kwords, d_out)
+
+    def lower_bound():
+        sum_price()
+        clay.scan_sum(cwords, d_seg, d_filter)
+
+    def staged_only():
+        adac.set_tuning("group_product_rw", 0)
+        product()
+        adac.set_tuning("group_product_rw", 1)
+
+    ms = {}
+    for name, fn in (("q1_disc_price_on_packed", plan), ("select", select), ("group_sum_price_masked", sum_price),
+                     ("group_sum_product_masked", product),
+                     ("group_sum_product_masked_with_counts",
+                      lambda: play.scan_group_sum_product(pwords, clay, cwords, klay, kwords, 6, d_spd, d_cpd, d_filter)),
+                     ("group_sum_product_unmasked",
+                      lambda: play.scan_group_sum_product(pwords, clay, cwords, klay, kwords, 6, d_spd)),
+                     ("group_sum_product_masked_staged_kernel_only", staged_only),
+                     ("unpack_price_discount_and_code", unpack_three),
+                     ("group_sum_price_plus_masked_sum_disc", lower_bound)):
+        fn()
+        ctx.timer_start()
+        for _ in range(reps):
+            fn()
+        ms[name] = ctx.timer_stop() / reps
+    plan()  # leave the plan's results behind and check them once more after the timed loops
+    parity("Q1 sum_disc_price parity (after timing)")
+    three = pbytes + cbytes + kbytes
+    out = {"rows": n, "groups": 6, "cutoff_day": cutoff, "selected_rows": int(keep.sum()),
+           "widths": {"l_extendedprice": pwidths, "l_discount": cwidths, "code": kwidths, "l_shipdate": dwidths},
+           "packed_bytes": {"l_extendedprice": pbytes, "l_discount": cbytes, "code": kbytes, "l_shipdate": dbytes},
+           "step_ms": ms,
+           "group_sum_product_packed_read_GBps": (three + n / 8) / (ms["group_sum_product_masked"] * 1e-3) / 1e9,
+           "unpack_three_columns_total_GBps": (three + n * (4 + 4 + 1)) / (ms["unpack_price_discount_and_code"] * 1e-3) / 1e9,
+           "product_faster_than_unpack": ms["group_sum_product_masked"] < ms["unpack_price_discount_and_code"],
+           "masked_over_lower_bound": ms["group_sum_product_masked"] / ms["group_sum_price_plus_masked_sum_disc"],
+           "groups_by_form": group_product_form_groups(pdescs, cdescs, kdescs, 6),
+           "note": "group_sum_product_masked = adac_scan_group_sum_product(l_extendedprice, l_discount) GROUP BY the flag "
+                   "code under the l_shipdate bitmap, without counts; unpack_price_discount_and_code is what a caller paid "
+                   "before it could start to multiply and group; group_sum_price_plus_masked_sum_disc is a lower bound for "
+                   "any walk of the three columns; all steps warm (20 back-to-back repetitions): the scans' working set of "
+                   "about 240 MB fits the 256 MB Infinity Cache, the unpacks' does not"}
+    ctx.close()
+    return out
+
+
 def c1_lookups(adac, wl, n=10_000_000, nlookups=10_000):
     """C1 (benchmark/micro/succinct/zipf_distribution.cpp:13-48): t1(i UINTEGER) with i = 0..N-1, compacted, then
     `SELECT i FROM t1 WHERE i == k` for Zipf(N, 1.0) keys (mt19937, seed 42).  Each look-up is one fused
@@ -675,6 +838,7 @@ def main():
             "bitpacking_fused_scans": lambda: bitpacking_fused_scans(adac),
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "q1_filtered_packed": lambda: q1_filtered_packed(adac),
+            "q1_disc_price_packed": lambda: q1_disc_price_packed(adac),
             "c1_lookups": lambda: c1_lookups(adac, wl)}
     res = {k: f() for k, f in jobs.items() if not only or k in only}
     print(json.dumps(res))

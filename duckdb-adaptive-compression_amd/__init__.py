@@ -165,6 +165,8 @@ SIGNATURES = {
     "adac_scan_group_sum": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "adac_scan_group_sum_valid": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "adac_scan_sum_product": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "adac_scan_group_sum_product": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "adac_debug_group_handover": (_int, [_vp, _vp]),
     "adac_scan_count_eq": (_int, [_vp, _vp, _u64, _vp]),
     "adac_scan_count_between": (_int, [_vp, _vp, _u64, _u64, _vp]),
     "adac_scan_sum_valid": (_int, [_vp, _vp, _vp, _vp]),
@@ -548,6 +550,21 @@ class Layout:
         signedness, mod 2^64) over the rows whose bit is set in d_validity, a mask in THIS layout's element space."""
         _check(lib().adac_scan_sum_product(self._h, _dptr(d_words), other._h, _dptr(d_other_words), _dptr(d_validity),
                                            _dptr(d_sums)), "adac_scan_sum_product")
+
+    def scan_group_sum_product(self, d_words, other, d_other_words, keys, d_key_words, ngroups, d_sums, d_counts=None,
+                               d_validity=None):
+        """SUM(self * other) GROUP BY `keys` (`other`, `keys`: Layouts over the same rows; each value widened by its own
+        type's signedness, mod 2^64) over the rows whose bit is set in d_validity, a mask in THIS layout's element space.
+        ngroups + 1 sums; the rows counted per group too when d_counts is given."""
+        _check(lib().adac_scan_group_sum_product(self._h, _dptr(d_words), other._h, _dptr(d_other_words), keys._h,
+                                                 _dptr(d_key_words), _dptr(d_validity), int(ngroups), _dptr(d_sums),
+                                                 _dptr(d_counts)), "adac_scan_group_sum_product")
+
+    def debug_group_handover(self):
+        """Scan groups the register-walk kernel of this layout's last grouped scan left to the staged kernel."""
+        left = C.c_uint64(0)
+        _check(lib().adac_debug_group_handover(self._h, C.byref(left)), "adac_debug_group_handover")
+        return int(left.value)
 
     def scan_count_between(self, d_words, lo, hi, d_counts, d_validity=None):
         """lo / hi: bit patterns of the column type (use int(np.array([v], dtype).view(unsigned)[0]) for signed)."""

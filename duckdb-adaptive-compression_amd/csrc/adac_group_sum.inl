@@ -699,8 +699,9 @@ __global__ __launch_bounds__(kWorkgroup, kGroupRwResident<V>) void k_group_sum_r
 	}
 }
 
-// one workgroup per bin: the partials of all workgroups -> sums[bin], counts[bin].  The partial rows of k_group_sum are
-// read only when it had something to do (no register-walk kernel, or *rw_fallback != 0).
+// one workgroup per bin: the partials of all workgroups -> sums[bin], counts[bin] (counts may be null:
+// adac_scan_group_sum_product without d_counts).  The partial rows of k_group_sum are read only when it had something to
+// do (no register-walk kernel, or *rw_fallback != 0).
 __global__ __launch_bounds__(kWorkgroup) void k_group_final(const unsigned long long *__restrict__ partial,
                                                             uint32_t nwg_rw, uint32_t nwg_staged, uint32_t nbins,
                                                             uint64_t *__restrict__ sums, uint64_t *__restrict__ counts,
@@ -733,6 +734,6 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_final(const unsigned long 
 			tc += pc[w];
 		}
 		sums[b] = ts;
-		counts[b] = tc;
+		if (counts != nullptr) counts[b] = tc;
 	}
 }

@@ -141,7 +141,7 @@ uint32_t adac_tile_values(int physical_type);
 /* Launch-shape knobs for in-process A/B measurement: "templated_scan" (0/1), "scan_tiles_per_wg" (tiles per fused-scan
  * workgroup; 0 = chosen by type), "num_cus" (0 = the device's own count), "single_pass_encode" (0 = analyze + plan +
  * pack as three kernels), "encode_big_image", "encode_publish_ahead", "scan_cells", "tile_records", "gather_compact",
- * "group_sum_wide", "group_sum_rw", "sel_debug": the table in adac_set_tuning is the full list, Tuning in
+ * "group_sum_wide", "group_sum_rw", "group_product_rw", "sel_debug": the table in adac_set_tuning is the full list, Tuning in
  * csrc/adac_internal.h says what each does.  Decoded values, packed words, widths and mins never depend on them.  One
  * knob changes WHERE adac_encode puts a segment in the arena: "encode_placement" 1 hands out arena space in order of
  * completion (a cursor, no ordered look-back) instead of the exclusive prefix in segment order that adac_plan computes:
@@ -368,6 +368,42 @@ adac_status adac_scan_group_sum_valid(adac_layout *values, const uint64_t *d_val
  * gets 0; d_sums is fully written by the call. */
 adac_status adac_scan_sum_product(adac_layout *a, const uint64_t *d_a_words, adac_layout *b, const uint64_t *d_b_words,
                                   const uint64_t *d_validity, uint64_t *d_sums);
+
+/* Grouped product aggregate over THREE packed columns of one table — TPC-H Q1's
+ * `SUM(l_extendedprice * (1 - l_discount)) ... WHERE <filter> GROUP BY l_returnflag, l_linestatus`: with integer
+ * decimals it is 100 * SUM(price) - SUM(price * disc) per group, the first term from adac_scan_group_sum_valid, the
+ * second from this call.  `a`, `b` and `keys` are layouts on the same context with the same row count per segment
+ * (types, widths, placements, encode rules and value offsets may differ; a == b with the same words gives the per-group
+ * sum of squares); nothing is materialised.
+ * d_sums[g] for g < ngroups = the sum of widen(a) * widen(b) over the rows whose key is g and whose bit is set in
+ * d_validity.  Each value is widened to 64 bits by its own column's signedness; the product and the sum are taken mod
+ * 2^64 (adac_scan_sum_product's rule).  key = the key column's value as an unsigned number of its own width; rows whose
+ * key is >= ngroups go to entry [ngroups]; 1 <= ngroups <= 256 (adac_scan_group_sum's rule).
+ * d_validity is indexed in a's element space (a's val_off + row); b's and the key layout's value offsets play no part.
+ * NULL = every row.  Bits that belong to no row never influence a result, and the call reads no mask word outside the
+ * ceil(value_span(a) / 64) words of a's layout.  A row whose bit is clear contributes to nothing, the overflow entry
+ * included.
+ * d_counts[g] = the number of contributing rows, as adac_scan_group_sum_valid counts them.  d_counts may be NULL: then
+ * no counts are written (Q1 has them from its other aggregates; the fast form then keeps none).
+ * d_sums, and d_counts when given, hold ngroups + 1 entries; they are fully written by the call and need no clearing,
+ * also when the layouts have no rows.  The call enqueues on the context's stream and synchronises no more than
+ * adac_scan_group_sum_valid does.
+ * ADAC_ERR_INVALID_ARGUMENT: a NULL layout; layouts on different contexts; per-segment counts that differ between any
+ * two of the three layouts; ngroups 0 or > 256; NULL d_sums; a NULL words pointer while there are rows; a words pointer
+ * that is not 16-byte aligned.
+ * The tuning knob "group_product_rw" (default 1) chooses between the register-walk kernel with the staged kernel for
+ * what it leaves, and (0) the staged kernel alone; results never depend on it. */
+adac_status adac_scan_group_sum_product(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
+                                        const uint64_t *d_b_words, adac_layout *keys, const uint64_t *d_key_words,
+                                        const uint64_t *d_validity, uint32_t ngroups, uint64_t *d_sums,
+                                        uint64_t *d_counts);
+
+/* Diagnostic, not part of the drop-in boundary: *left = the number of scan groups of `l` that the register-walk kernel of
+ * the layout's LAST grouped scan (adac_scan_group_sum, adac_scan_group_sum_valid or adac_scan_group_sum_product with `l`
+ * as the value / `a` layout) left to the staged kernel; 0 when the walk took every group, when it was not launched (more
+ * than 8 bins, or its knob at 0: the staged kernel then takes everything) or when no grouped scan ran.  Synchronises the
+ * context's stream.  The tests hold the kernels' choice of form against the host mirror of the rule with it. */
+adac_status adac_debug_group_handover(adac_layout *l, uint64_t *left);
 
 /* The same two scans with a DuckDB validity mask over the element index space (bit e of word e/64 set = row e
  * valid, as for adac_analyze): NULL rows take no part in the aggregate — what SUM / COUNT over a nullable
