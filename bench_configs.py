@@ -667,6 +667,40 @@ def group_product_form_groups(descs_a, descs_b, descs_k, ngroups, a_type=(4, Tru
     return out
 
 
+def group_product3_form_groups(descs_a, descs_b, descs_c, descs_k, ngroups, a_type=(4, True), b_type=(4, True),
+                               c_type=(4, True), k_size=1):
+    """Which form of adac_scan_group_sum_product3 takes how many scan groups of `a` — group_product3_rw_eligible
+    (adac_group_product3.inl) evaluated on the host descriptors: group_product_rw_eligible on (a, b, keys), and for c
+    what holds for b (1 <= wc <= 32, below 2^31 bits, value = field + frame with 0 <= frame and frame + 2^wc - 1 < 2^32).
+    a_type / b_type / c_type: (type size, signed); k_size: the key type's size."""
+    NO_MIN = 0xFFFFFFFFFFFFFFFF
+
+    def c_ok(d):
+        wc, tb = int(d["width"]), 8 * c_type[0]
+        if not (1 <= wc <= 32 and int(d["count"]) * wc < 2 ** 31):
+            return False
+        tmask, sbit = (1 << tb) - 1, (1 << (tb - 1)) if c_type[1] else 0
+        if (int(d["flags"]) & 1) and int(d["min"]) != NO_MIN:
+            bmin = (int(d["min"]) & tmask) ^ sbit
+            if bmin + (1 << wc) - 1 > tmask:
+                return False
+            mc = bmin - sbit
+        elif sbit == 0:
+            mc = 0
+        else:
+            return False
+        return 0 <= mc and mc + (1 << wc) - 1 < 2 ** 32
+
+    out = {"fast": 0, "generic": 0}
+    for da, db, dc, dk in zip(descs_a, descs_b, descs_c, descs_k):
+        one = group_product_form_groups([da], [db], [dk], ngroups, a_type, b_type, k_size)
+        if one["fast"] and not c_ok(dc):
+            one = {"fast": 0, "generic": one["fast"]}
+        out["fast"] += one["fast"]
+        out["generic"] += one["generic"]
+    return out
+
+
 def q1_disc_price_packed(adac, n=59_986_052):
     """Q1's sum_disc_price on packed columns: the columns of q1_filtered_packed that this plan reads (flag code,
     l_extendedprice, l_shipdate; same shapes, a random stream of its own) plus an int32 l_discount in [0, 10].  One
@@ -790,6 +824,180 @@ def q1_disc_price_packed(adac, n=59_986_052):
     return out
 
 
+def q1_full_packed(adac, n=59_986_052):
+    """All of Q1 on packed columns: q1_disc_price_packed's columns (same shapes, a random stream of its own) plus
+    l_quantity (1 .. 50) and an int32 l_tax in [0, 8].  One adac_scan_select_between (l_shipdate <= cutoff) writes the
+    bitmap; under it three adac_scan_group_sum_valid (quantity, price, discount), two adac_scan_group_sum_product
+    ((price, disc), (price, tax)) and one adac_scan_group_sum_product3 (price, disc, tax).  In integer decimals
+      sum_disc_price = 100 SUM(p) - SUM(p d)
+      sum_charge     = 10000 SUM(p) + 100 SUM(p t) - 100 SUM(p d) - SUM(p d t)
+    and the three averages are exact (sum, count) pairs.  Every output column is checked against numpy over the kept rows
+    before anything is timed.  Timed: every step and the whole plan, warm and INTERLEAVED (one repetition of every step
+    per round, so no step has the clock or the cache state of a run of its own), the new call masked / unmasked / with
+    its knob at 0, and what a caller paid before: adac_unpack of the four columns the new call reads."""
+    ctx = adac.Context(0)
+    rng = np.random.default_rng(1995)
+    code = rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8)
+    price = rng.integers(90_000, 10_495_000, size=n).astype(np.int32)
+    shipdate = rng.integers(8036, 10562, size=n).astype(np.int32)
+    qty = rng.integers(1, 51, size=n).astype(np.int32)
+    disc = rng.integers(0, 11, size=n).astype(np.int32)
+    tax = rng.integers(0, 9, size=n).astype(np.int32)
+    cutoff = 10511
+    counts = adac.appender_segment_counts(n, 4)
+
+    def enc_col(v):
+        lay = adac.Layout(ctx, v.dtype, counts)
+        d_vals = ctx.upload(v)
+        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
+        lay.encode(d_vals, d_words)
+        ctx.sync()
+        d_vals.free()
+        descs = lay.get_descs()
+        nbytes = int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
+        return lay, d_words, nbytes, sorted(set(descs["width"].tolist())), descs
+
+    cols = {"code": enc_col(code), "l_shipdate": enc_col(shipdate), "l_quantity": enc_col(qty),
+            "l_extendedprice": enc_col(price), "l_discount": enc_col(disc), "l_tax": enc_col(tax)}
+    klay, kwords = cols["code"][:2]
+    dlay, dwords = cols["l_shipdate"][:2]
+    qlay, qwords = cols["l_quantity"][:2]
+    play, pwords = cols["l_extendedprice"][:2]
+    clay, cwords = cols["l_discount"][:2]
+    tlay, twords = cols["l_tax"][:2]
+    d_filter = ctx.alloc((n + 63) // 64 * 8 + 8)
+    d_selcnt = ctx.alloc(len(counts) * 8)
+    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
+    res = {k: (ctx.alloc(7 * 8), ctx.alloc(7 * 8)) for k in ("q", "p", "d", "pd", "pt", "pdt")}
+    select = lambda: dlay.scan_select_between(dwords, int_min, cutoff, d_filter, d_selcnt)
+    sum_q = lambda: qlay.scan_group_sum_valid(qwords, klay, kwords, d_filter, 6, *res["q"])
+    sum_p = lambda: play.scan_group_sum_valid(pwords, klay, kwords, d_filter, 6, *res["p"])
+    sum_d = lambda: clay.scan_group_sum_valid(cwords, klay, kwords, d_filter, 6, *res["d"])
+    sum_pd = lambda: play.scan_group_sum_product(pwords, clay, cwords, klay, kwords, 6, res["pd"][0], None, d_filter)
+    sum_pt = lambda: play.scan_group_sum_product(pwords, tlay, twords, klay, kwords, 6, res["pt"][0], None, d_filter)
+
+    def sum_pdt(mask=True, with_counts=False):
+        play.scan_group_sum_product3(pwords, clay, cwords, tlay, twords, klay, kwords, 6, res["pdt"][0],
+                                     res["pdt"][1] if with_counts else None, d_filter if mask else None)
+
+    steps = (select, sum_q, sum_p, sum_d, sum_pd, sum_pt, sum_pdt)
+
+    def plan():
+        for f in steps:
+            f()
+
+    keep = shipdate <= cutoff
+    bins = [(code == g) & keep for g in range(6)]
+    p64, d64, t64 = price.astype(np.int64), disc.astype(np.int64), tax.astype(np.int64)
+    exp = {"sum_qty": [int(qty[b].sum(dtype=np.int64)) for b in bins],
+           "sum_base_price": [int(p64[b].sum()) for b in bins],
+           "sum_disc_price": [int((p64[b] * (100 - d64[b])).sum()) for b in bins],
+           "sum_charge": [int((p64[b] * (100 - d64[b]) * (100 + t64[b])).sum()) for b in bins],
+           "avg_qty": [(int(qty[b].sum(dtype=np.int64)), int(b.sum())) for b in bins],
+           "avg_price": [(int(p64[b].sum()), int(b.sum())) for b in bins],
+           "avg_disc": [(int(d64[b].sum()), int(b.sum())) for b in bins],
+           "count_order": [int(b.sum()) for b in bins]}
+
+    def outputs():
+        """Q1's eight output columns per group, as integers, from the six results"""
+        ctx.sync()
+        s = {k: v[0].download(np.uint64, 7).tolist() for k, v in res.items()}
+        c = {k: res[k][1].download(np.uint64, 7).tolist() for k in ("q", "p", "d")}
+        assert all(s[k][6] == 0 for k in s) and all(c[k][6] == 0 for k in c), "no row has a key >= 6"
+        g6 = range(6)
+        return {"sum_qty": [s["q"][g] for g in g6],
+                "sum_base_price": [s["p"][g] for g in g6],
+                "sum_disc_price": [100 * s["p"][g] - s["pd"][g] for g in g6],
+                "sum_charge": [10000 * s["p"][g] + 100 * s["pt"][g] - 100 * s["pd"][g] - s["pdt"][g] for g in g6],
+                "avg_qty": [(s["q"][g], c["q"][g]) for g in g6],
+                "avg_price": [(s["p"][g], c["p"][g]) for g in g6],
+                "avg_disc": [(s["d"][g], c["d"][g]) for g in g6],
+                "count_order": [c["p"][g] for g in g6]}
+
+    def parity(what):
+        got = outputs()
+        for name, want in exp.items():
+            assert got[name] == want, (what, name)
+
+    plan()
+    parity("Q1 parity")
+    forms = group_product3_form_groups(cols["l_extendedprice"][4], cols["l_discount"][4], cols["l_tax"][4],
+                                       cols["code"][4], 6)
+    exp_pdt = [int((p64[b] * d64[b] * t64[b]).sum()) for b in bins] + [0]
+    for knob in (0, 1):  # both forms; with counts; the hand-over against the mirror
+        adac.set_tuning("group_product3_rw", knob)
+        sum_pdt(with_counts=True)
+        ctx.sync()
+        assert res["pdt"][0].download(np.uint64, 7).tolist() == exp_pdt, ("SUM(p d t)", knob)
+        assert res["pdt"][1].download(np.uint64, 7).tolist() == exp["count_order"] + [0], ("COUNT", knob)
+        assert play.debug_group_handover() == (forms["generic"] if knob else 0), ("hand-over", knob)
+    sum_pdt(mask=False, with_counts=True)
+    ctx.sync()
+    allrows = [code == g for g in range(6)]
+    assert res["pdt"][0].download(np.uint64, 7).tolist() == [int((p64[b] * d64[b] * t64[b]).sum()) for b in allrows] + [0]
+    assert res["pdt"][1].download(np.uint64, 7).tolist() == [int(b.sum()) for b in allrows] + [0], "unmasked parity"
+    d_out = ctx.alloc(n * 4 + 64)
+
+    def unpack_four():
+        play.unpack(pwords, d_out)
+        clay.unpack(cwords, d_out)
+        tlay.unpack(twords, d_out)
+        klay.unpack(kwords, d_out)
+
+    def staged_only():
+        adac.set_tuning("group_product3_rw", 0)
+        sum_pdt()
+        adac.set_tuning("group_product3_rw", 1)
+
+    timed = (("q1_full_on_packed", plan), ("select", select), ("group_sum_quantity_masked", sum_q),
+             ("group_sum_price_masked", sum_p), ("group_sum_discount_masked", sum_d),
+             ("group_sum_product_price_disc_masked", sum_pd), ("group_sum_product_price_tax_masked", sum_pt),
+             ("group_sum_product3_masked", sum_pdt),
+             ("group_sum_product3_masked_with_counts", lambda: sum_pdt(with_counts=True)),
+             ("group_sum_product3_unmasked", lambda: sum_pdt(mask=False)),
+             ("group_sum_product3_masked_staged_kernel_only", staged_only),
+             ("unpack_price_discount_tax_and_code", unpack_four))
+    # warm and interleaved: an untimed round, then `rounds` rounds in which every entry runs `inner` times back to back
+    # between two events of its own (one call alone, 0.1 ms, would be timed together with its launch gap); the figure is
+    # the median over the rounds of the time per call.  The scans' working sets (the new call's: packed bytes of four
+    # columns + the mask, about 270 MB) are near the 256 MB Infinity Cache, the unpacks' (the same packed bytes + 780 MB
+    # of output) are far above it: with every entry following a different one, none starts on a cache it warmed alone
+    rounds, inner = 8, 5
+    samples = {name: [] for name, _ in timed}
+    for r in range(rounds + 1):
+        for name, fn in timed:
+            ctx.timer_start()
+            for _ in range(inner):
+                fn()
+            t = ctx.timer_stop() / inner
+            if r:
+                samples[name].append(t)
+    ms = {name: float(np.median(v)) for name, v in samples.items()}
+    plan()  # leave the plan's results behind and check them once more after the timed loops
+    parity("Q1 parity (after timing)")
+    four = sum(cols[k][2] for k in ("l_extendedprice", "l_discount", "l_tax", "code"))
+    out = {"rows": n, "groups": 6, "cutoff_day": cutoff, "selected_rows": int(keep.sum()),
+           "widths": {k: v[3] for k, v in cols.items()}, "packed_bytes": {k: v[2] for k, v in cols.items()},
+           "rounds": rounds, "calls_per_round": inner, "step_ms": ms,
+           "step_ms_min": {name: float(min(v)) for name, v in samples.items()},
+           "sum_of_steps_ms": sum(ms[name] for name, _ in timed[1:8]),
+           "group_sum_product3_packed_read_GBps": (four + n / 8) / (ms["group_sum_product3_masked"] * 1e-3) / 1e9,
+           "unpack_four_columns_total_GBps": (four + n * (4 + 4 + 4 + 1)) / (ms["unpack_price_discount_tax_and_code"] * 1e-3) / 1e9,
+           "product3_faster_than_unpack": ms["group_sum_product3_masked"] < ms["unpack_price_discount_tax_and_code"],
+           "product3_over_product": ms["group_sum_product3_masked"] / ms["group_sum_product_price_disc_masked"],
+           "register_walk_faster_than_staged_only": ms["group_sum_product3_masked"] < ms["group_sum_product3_masked_staged_kernel_only"],
+           "groups_by_form": forms,
+           "q1_output": {k: [list(x) if isinstance(x, tuple) else x for x in v] for k, v in outputs().items()},
+           "note": "group_sum_product3_masked = adac_scan_group_sum_product3(l_extendedprice, l_discount, l_tax) GROUP BY "
+                   "the flag code under the l_shipdate bitmap, without counts; unpack_price_discount_tax_and_code is what a "
+                   "caller paid before it could start to multiply and group; q1_full_on_packed = the select + three "
+                   "grouped SUMs + two grouped products + the triple product, seven calls; all figures are medians over 8 "
+                   "interleaved rounds of the time per call, 5 calls back to back per entry and round, warm, one process "
+                   "(step_ms_min: the fastest round)"}
+    ctx.close()
+    return out
+
+
 def c1_lookups(adac, wl, n=10_000_000, nlookups=10_000):
     """C1 (benchmark/micro/succinct/zipf_distribution.cpp:13-48): t1(i UINTEGER) with i = 0..N-1, compacted, then
     `SELECT i FROM t1 WHERE i == k` for Zipf(N, 1.0) keys (mt19937, seed 42).  Each look-up is one fused
@@ -839,6 +1047,7 @@ def main():
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "q1_filtered_packed": lambda: q1_filtered_packed(adac),
             "q1_disc_price_packed": lambda: q1_disc_price_packed(adac),
+            "q1_full_packed": lambda: q1_full_packed(adac),
             "c1_lookups": lambda: c1_lookups(adac, wl)}
     res = {k: f() for k, f in jobs.items() if not only or k in only}
     print(json.dumps(res))

@@ -166,6 +166,7 @@ SIGNATURES = {
     "adac_scan_group_sum_valid": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "adac_scan_sum_product": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "adac_scan_group_sum_product": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "adac_scan_group_sum_product3": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "adac_debug_group_handover": (_int, [_vp, _vp]),
     "adac_scan_count_eq": (_int, [_vp, _vp, _u64, _vp]),
     "adac_scan_count_between": (_int, [_vp, _vp, _u64, _u64, _vp]),
@@ -559,6 +560,15 @@ class Layout:
         _check(lib().adac_scan_group_sum_product(self._h, _dptr(d_words), other._h, _dptr(d_other_words), keys._h,
                                                  _dptr(d_key_words), _dptr(d_validity), int(ngroups), _dptr(d_sums),
                                                  _dptr(d_counts)), "adac_scan_group_sum_product")
+
+    def scan_group_sum_product3(self, d_words, b, d_b_words, c, d_c_words, keys, d_key_words, ngroups, d_sums,
+                                d_counts=None, d_validity=None):
+        """SUM(self * b * c) GROUP BY `keys` (`b`, `c`, `keys`: Layouts over the same rows; each value widened by its own
+        type's signedness, both products mod 2^64) over the rows whose bit is set in d_validity, a mask in THIS layout's
+        element space.  ngroups + 1 sums; the rows counted per group too when d_counts is given."""
+        _check(lib().adac_scan_group_sum_product3(self._h, _dptr(d_words), b._h, _dptr(d_b_words), c._h, _dptr(d_c_words),
+                                                  keys._h, _dptr(d_key_words), _dptr(d_validity), int(ngroups),
+                                                  _dptr(d_sums), _dptr(d_counts)), "adac_scan_group_sum_product3")
 
     def debug_group_handover(self):
         """Scan groups the register-walk kernel of this layout's last grouped scan left to the staged kernel."""

@@ -357,6 +357,7 @@ extern "C" int adac_set_tuning(const char *name, int value) {
 	    {"group_sum_wide", &adac::Tuning::group_sum_wide, INT_MIN},
 	    {"group_sum_rw", &adac::Tuning::group_sum_rw, INT_MIN},
 	    {"group_product_rw", &adac::Tuning::group_product_rw, INT_MIN},
+	    {"group_product3_rw", &adac::Tuning::group_product3_rw, INT_MIN},
 	    {"templated_scan", &adac::Tuning::templated_scan, INT_MIN},
 	    {"scan_tiles_per_wg", &adac::Tuning::scan_tiles_per_wg, 0}, // 0 = by type
 	    {"num_cus", &adac::Tuning::num_cus, 0},                     // 0 = the device's own count
@@ -1163,7 +1164,40 @@ extern "C" adac_status adac_scan_group_sum_product(adac_layout *a, const uint64_
 	return ADAC_OK;
 }
 
-// Diagnostic: the hand-over word of the layout's LAST grouped scan (either entry point) — the scan groups its
+// SUM(a * b * c) GROUP BY key under a selection bitmap over four packed columns of one table (Q1's sum_charge needs
+// SUM(price * disc * tax))
+extern "C" adac_status adac_scan_group_sum_product3(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
+                                                    const uint64_t *d_b_words, adac_layout *c, const uint64_t *d_c_words,
+                                                    adac_layout *keys, const uint64_t *d_key_words,
+                                                    const uint64_t *d_validity, uint32_t ngroups, uint64_t *d_sums,
+                                                    uint64_t *d_counts) {
+	if (!a || !b || !c || !keys || a->ctx != b->ctx || a->ctx != c->ctx || a->ctx != keys->ctx || !d_sums) {
+		return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	if (ngroups == 0 || ngroups > adac::group_sum_max_groups()) return ADAC_ERR_INVALID_ARGUMENT;
+	// the same rows, segment by segment
+	if (a->counts != b->counts || a->counts != c->counts || a->counts != keys->counts) return ADAC_ERR_INVALID_ARGUMENT;
+	if (a->total_values && (!d_a_words || !d_b_words || !d_c_words || !d_key_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (!aligned16(d_a_words) || !aligned16(d_b_words) || !aligned16(d_c_words) || !aligned16(d_key_words)) {
+		return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	ADAC_HIP(hipSetDevice(a->ctx->device));
+	// the partial buffer, the call counter and the hand-over slots are a's, shared with the other grouped scans
+	if (!a->d_group_partial) {
+		ADAC_HIP(hipMalloc(&a->d_group_partial, adac::group_sum_partial_bytes()));
+		ADAC_HIP(hipMemsetAsync(a->d_group_partial, 0, adac::group_sum_partial_bytes(), a->ctx->stream));
+	}
+	adac_status gst = ensure_scan_groups(a); // the register-walk kernel's work items
+	if (gst != ADAC_OK) return gst;
+	ADAC_HIP(adac::launch_group_product3(a->ctx->stream, a->type_size, a->is_signed, b->type_size, b->is_signed,
+	                                     c->type_size, c->is_signed, keys->type_size, a->d_descs, a->d_tiles, a->ntiles,
+	                                     a->d_groups, a->ngroups, d_a_words, b->d_descs, d_b_words, c->d_descs, d_c_words,
+	                                     keys->d_descs, d_key_words, ngroups, a->d_group_partial, a->group_calls++,
+	                                     d_validity, d_sums, d_counts));
+	return ADAC_OK;
+}
+
+// Diagnostic: the hand-over word of the layout's LAST grouped scan (any of the grouped entry points) — the scan groups its
 // register-walk kernel left to the staged kernel.  The word stays until the call after the next one clears it.
 extern "C" adac_status adac_debug_group_handover(adac_layout *l, uint64_t *left) {
 	if (!l || !left) return ADAC_ERR_INVALID_ARGUMENT;

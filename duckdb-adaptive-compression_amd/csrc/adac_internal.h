@@ -101,6 +101,7 @@ struct Tuning {
 	int group_sum_wide = 0;     // A/B: adac_scan_group_sum always in 64-bit arithmetic
 	int group_sum_rw = 1;       // A/B: 0 = adac_scan_group_sum without the register-walk kernel (k_group_sum only)
 	int group_product_rw = 1;   // A/B: 0 = adac_scan_group_sum_product without the register-walk kernel (k_group_product only)
+	int group_product3_rw = 1;  // A/B: 0 = adac_scan_group_sum_product3 without the register-walk kernel (k_group_product3 only)
 	int encode_placement = 0;   // single-pass encode: 0 = arena order is segment order (look-back), 1 = order of completion
 	int encode_big_image = 1;   // single-pass encode, ordered placement: a segment whose packed words fit the LDS pool is packed there whole and publishes the NEXT footprint before it waits (A/B: 0)
 	int encode_publish_ahead = 1; // single-pass encode, ordered placement: the parked flow publishes the NEXT footprint before it waits (A/B: 0)
@@ -166,6 +167,17 @@ hipError_t launch_group_product(hipStream_t s, uint32_t a_type_size, bool a_sign
                                 const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups,
                                 void *d_partial, uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums,
                                 uint64_t *d_counts);
+// SUM(a * b * c) GROUP BY key over four packed columns of one table under a selection bitmap
+// (adac_group_product3.inl); d_partial / call_parity: launch_group_sum's, d_counts may be null
+hipError_t launch_group_product3(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
+                                 uint32_t c_type_size, bool c_signed, uint32_t k_type_size,
+                                 const adac_segment_desc *d_adescs, const TileRef *d_atiles, uint64_t ntiles,
+                                 const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
+                                 const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
+                                 const adac_segment_desc *d_cdescs, const uint64_t *d_cwords,
+                                 const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups,
+                                 void *d_partial, uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums,
+                                 uint64_t *d_counts);
 // SUM(a * b) over two packed columns of one table under a selection bitmap (adac_sum_product.inl)
 hipError_t launch_scan_sum_product(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
                                    const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,

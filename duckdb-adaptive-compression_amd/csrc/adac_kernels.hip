@@ -1953,6 +1953,7 @@ hipError_t dispatch_size(uint32_t type_size, F &&f) {
 #include "adac_group_sum.inl"
 #include "adac_sum_product.inl"
 #include "adac_group_product.inl"
+#include "adac_group_product3.inl"
 
 } // namespace
 
@@ -2158,6 +2159,72 @@ hipError_t launch_group_product(hipStream_t s, uint32_t a_type_size, bool a_sign
 			                   d_awords, d_bdescs, d_bwords, d_kdescs, d_kwords, ty, ngroups,
 			                   partial + (uint64_t)nwg_rw * 2u * nbins, handed, d_validity);
 		}
+		hipError_t e = hipGetLastError();
+		if (e != hipSuccess) return e;
+	}
+	hipLaunchKernelGGL(k_group_final, dim3(nbins), dim3(kWorkgroup), 0, s, partial, nwg_rw, nwg, nbins, d_sums,
+	                   d_counts, static_cast<const unsigned long long *>(fallback), next_fallback, rw ? 1 : 0);
+	return hipGetLastError();
+}
+
+// SUM(a * b * c) GROUP BY key under a selection bitmap (adac_group_product3.inl).  launch_group_product's three steps
+// with a fourth column, on the same partial buffer and hand-over slots (d_partial, call_parity: the `a` layout's, shared
+// between the grouped entry points)
+hipError_t launch_group_product3(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
+                                 uint32_t c_type_size, bool c_signed, uint32_t k_type_size,
+                                 const adac_segment_desc *d_adescs, const TileRef *d_atiles, uint64_t ntiles,
+                                 const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
+                                 const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
+                                 const adac_segment_desc *d_cdescs, const uint64_t *d_cwords,
+                                 const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups,
+                                 void *d_partial, uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums,
+                                 uint64_t *d_counts) {
+	GroupProduct3Types ty;
+	ty.g.p.a_tmask = type_mask(a_type_size);
+	ty.g.p.a_sbit = type_sign_bit(a_type_size, a_signed);
+	ty.g.p.b_tmask = type_mask(b_type_size);
+	ty.g.p.b_sbit = type_sign_bit(b_type_size, b_signed);
+	ty.g.k_tmask = type_mask(k_type_size);
+	ty.g.a_tile_rows = tile_values(a_type_size);
+	ty.c_tmask = type_mask(c_type_size);
+	ty.c_sbit = type_sign_bit(c_type_size, c_signed);
+	const uint32_t nbins = ngroups + 1u;
+	unsigned long long *partial = static_cast<unsigned long long *>(d_partial);
+	unsigned long long *fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + (call_parity & 1u);
+	unsigned long long *next_fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + ((call_parity + 1u) & 1u);
+	// 1. the register-walk kernel over a's scan groups (up to 8 bins; persistent, kGroupProduct3RwResident workgroups
+	//    per CU); it counts the scan groups it cannot take in *fallback
+	uint32_t nwg_rw = 0;
+	const bool rw = nbins <= kGroupPrivateBins && g_tuning.group_product3_rw && nagroups > 0;
+	if (rw) {
+		const uint64_t cap = (uint64_t)kGroupProduct3RwResident * device_cus();
+		nwg_rw = (uint32_t)(nagroups < cap ? nagroups : cap);
+		nwg_rw = nwg_rw < kGroupMaxWorkgroups / 2 ? nwg_rw : kGroupMaxWorkgroups / 2;
+		auto launch = [&](auto kernel) {
+			hipLaunchKernelGGL(kernel, dim3(nwg_rw), dim3(kWorkgroup), 0, s, d_agroups, (uint32_t)nagroups, d_awords, d_bdescs,
+			                   d_bwords, d_cdescs, d_cwords, d_kdescs, d_kwords, ty, ngroups, partial, fallback, d_validity);
+		};
+		if (d_validity) { // without d_counts the walk keeps no row counts
+			if (d_counts) launch(k_group_product3_rw<true, true>); else launch(k_group_product3_rw<true, false>);
+		} else {
+			if (d_counts) launch(k_group_product3_rw<false, true>); else launch(k_group_product3_rw<false, false>);
+		}
+		hipError_t e = hipGetLastError();
+		if (e != hipSuccess) return e;
+	}
+	// 2. the staged-LDS kernel over a's tiles: everything when the first kernel did not run, else what it left (its
+	//    workgroups leave at once when that is nothing).  Persistent: as many workgroups as are resident at once
+	uint64_t cap = (uint64_t)kGroupProduct3Resident * device_cus();
+	cap = cap < kGroupMaxWorkgroups / 2 ? cap : kGroupMaxWorkgroups / 2;
+	const uint32_t nwg = (uint32_t)(ntiles < cap ? ntiles : cap);
+	if (nwg) {
+		const unsigned long long *handed = rw ? fallback : static_cast<const unsigned long long *>(nullptr);
+		auto launch = [&](auto kernel) {
+			hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles, d_awords,
+			                   d_bdescs, d_bwords, d_cdescs, d_cwords, d_kdescs, d_kwords, ty, ngroups,
+			                   partial + (uint64_t)nwg_rw * 2u * nbins, handed, d_validity);
+		};
+		if (d_validity) launch(k_group_product3<true>); else launch(k_group_product3<false>);
 		hipError_t e = hipGetLastError();
 		if (e != hipSuccess) return e;
 	}

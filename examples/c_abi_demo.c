@@ -2,7 +2,8 @@
  *   gcc -std=c99 -O2 -Iinclude examples/c_abi_demo.c -Lduckdb-adaptive-compression_amd -ladacodec \
  *       -Wl,-rpath,$PWD/duckdb-adaptive-compression_amd -o /tmp/c_abi_demo && /tmp/c_abi_demo
  * Packs a small uint32 column of three ragged segments, scans it back, runs a filter + masked SUM on the packed
- * bytes and materialises the selected rows.  Exits 0 only if every result is right. */
+ * bytes, materialises the selected rows and runs a grouped triple product (SUM(v * v * v) GROUP BY a small key column)
+ * under the same filter.  Exits 0 only if every result is right. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -91,6 +92,44 @@ int main(void) {
 	for (uint64_t i = 0; i < n; i++) {
 		if (vals[i] >= 1001000u && vals[i] <= 1001999u && back[k++] != vals[i]) return 7;
 	}
+
+	/* SUM(v * v * v) GROUP BY key under the same bitmap (mod 2^64): the three factors may be one layout */
+	enum { NGROUPS = 3 };
+	uint8_t *keys = (uint8_t *)malloc(n);
+	for (uint64_t i = 0; i < n; i++) keys[i] = (uint8_t)((i * 7u) % 4u); /* key 3 >= NGROUPS: the overflow entry */
+	adac_layout *kcol = NULL;
+	CHECK(adac_layout_create(ctx, ADAC_UINT8, counts, NULL, NSEG, &kcol));
+	void *d_keys = NULL, *d_kwords = NULL, *d_gsums = NULL, *d_gcounts = NULL;
+	CHECK(adac_dev_alloc(ctx, n + 16, &d_keys));
+	CHECK(adac_dev_alloc(ctx, adac_layout_max_arena_words(kcol) * 8 + 16, &d_kwords));
+	CHECK(adac_dev_alloc(ctx, (NGROUPS + 1) * 8, &d_gsums));
+	CHECK(adac_dev_alloc(ctx, (NGROUPS + 1) * 8, &d_gcounts));
+	CHECK(adac_memcpy_h2d(ctx, d_keys, keys, n));
+	CHECK(adac_encode(kcol, d_keys, NULL, ADAC_RULE_APPEND, 0, (uint64_t *)d_kwords));
+	CHECK(adac_scan_group_sum_product3(col, (const uint64_t *)d_words, col, (const uint64_t *)d_words, col,
+	                                   (const uint64_t *)d_words, kcol, (const uint64_t *)d_kwords,
+	                                   (const uint64_t *)d_bitmap, NGROUPS, (uint64_t *)d_gsums, (uint64_t *)d_gcounts));
+	uint64_t gsum[NGROUPS + 1], gcnt[NGROUPS + 1], exp_gsum[NGROUPS + 1] = {0}, exp_gcnt[NGROUPS + 1] = {0};
+	CHECK(adac_memcpy_d2h(ctx, gsum, d_gsums, sizeof gsum));
+	CHECK(adac_memcpy_d2h(ctx, gcnt, d_gcounts, sizeof gcnt));
+	for (uint64_t i = 0; i < n; i++) {
+		if (vals[i] >= 1001000u && vals[i] <= 1001999u) {
+			const unsigned g = keys[i] < NGROUPS ? keys[i] : NGROUPS;
+			exp_gsum[g] += (uint64_t)vals[i] * vals[i] * vals[i]; /* wraps mod 2^64, as the call does */
+			exp_gcnt[g]++;
+		}
+	}
+	for (int g = 0; g <= NGROUPS; g++) {
+		printf("group %d: %llu rows, sum of cubes mod 2^64 %llu\n", g, (unsigned long long)gcnt[g],
+		       (unsigned long long)gsum[g]);
+		if (gsum[g] != exp_gsum[g] || gcnt[g] != exp_gcnt[g]) return 8;
+	}
+	adac_dev_free(ctx, d_keys);
+	adac_dev_free(ctx, d_kwords);
+	adac_dev_free(ctx, d_gsums);
+	adac_dev_free(ctx, d_gcounts);
+	adac_layout_destroy(kcol);
+	free(keys);
 
 	adac_dev_free(ctx, d_vals);
 	adac_dev_free(ctx, d_words);

@@ -141,7 +141,8 @@ uint32_t adac_tile_values(int physical_type);
 /* Launch-shape knobs for in-process A/B measurement: "templated_scan" (0/1), "scan_tiles_per_wg" (tiles per fused-scan
  * workgroup; 0 = chosen by type), "num_cus" (0 = the device's own count), "single_pass_encode" (0 = analyze + plan +
  * pack as three kernels), "encode_big_image", "encode_publish_ahead", "scan_cells", "tile_records", "gather_compact",
- * "group_sum_wide", "group_sum_rw", "group_product_rw", "sel_debug": the table in adac_set_tuning is the full list, Tuning in
+ * "group_sum_wide", "group_sum_rw", "group_product_rw", "group_product3_rw", "sel_debug": the table in adac_set_tuning is the
+ * full list, Tuning in
  * csrc/adac_internal.h says what each does.  Decoded values, packed words, widths and mins never depend on them.  One
  * knob changes WHERE adac_encode puts a segment in the arena: "encode_placement" 1 hands out arena space in order of
  * completion (a cursor, no ordered look-back) instead of the exclusive prefix in segment order that adac_plan computes:
@@ -398,9 +399,40 @@ adac_status adac_scan_group_sum_product(adac_layout *a, const uint64_t *d_a_word
                                         const uint64_t *d_validity, uint32_t ngroups, uint64_t *d_sums,
                                         uint64_t *d_counts);
 
+/* Grouped TRIPLE product aggregate over FOUR packed columns of one table — the term TPC-H Q1's sum_charge adds to the
+ * calls above: with integer decimals
+ *   SUM(p * (100 - d) * (100 + t)) = 10000 * SUM(p) + 100 * SUM(p * t) - 100 * SUM(p * d) - SUM(p * d * t)   per group,
+ * the first term from adac_scan_group_sum_valid, the next two from adac_scan_group_sum_product, the last from this call.
+ * Semantics are adac_scan_group_sum_product's with one more factor.  `a`, `b`, `c` and `keys` are layouts on the same
+ * context with the same row count per segment (types, widths, placements, encode rules and value offsets may differ);
+ * any two or all three of a, b, c may be the same layout with the same words (the per-group sum of cubes, or of
+ * a^2 * c); nothing is materialised.
+ * d_sums[g] for g < ngroups = the sum of widen(a) * widen(b) * widen(c) over the rows whose key is g and whose bit is
+ * set in d_validity.  Each value is widened to 64 bits by its own column's signedness; both multiplications and the sum
+ * are taken mod 2^64.  key = the key column's value as an unsigned number of its own width; rows whose key is >= ngroups
+ * go to entry [ngroups]; 1 <= ngroups <= 256.
+ * d_validity is indexed in a's element space (a's val_off + row); the value offsets of b, c and keys play no part.
+ * NULL = every row.  Bits that belong to no row never influence a result, and the call reads no mask word outside the
+ * ceil(value_span(a) / 64) words of a's layout.  A row whose bit is clear contributes to nothing, the overflow entry
+ * included.
+ * d_counts[g] = the number of contributing rows; d_counts may be NULL: then no counts are written.
+ * d_sums, and d_counts when given, hold ngroups + 1 entries; they are fully written by the call and need no clearing,
+ * also when the layouts have no rows.  The call enqueues on the context's stream and synchronises no more than
+ * adac_scan_group_sum_product does.  The partial buffer, the call counter and the hand-over slots are a's, shared with
+ * adac_scan_group_sum[_valid] and adac_scan_group_sum_product: the entry points may be called in any order on one layout.
+ * ADAC_ERR_INVALID_ARGUMENT: a NULL layout; layouts on different contexts; per-segment counts that differ between any
+ * two of the four layouts; ngroups 0 or > 256; NULL d_sums; a NULL words pointer while there are rows; a words pointer
+ * that is not 16-byte aligned.
+ * The tuning knob "group_product3_rw" (default 1) chooses between the register-walk kernel with the staged kernel for
+ * what it leaves, and (0) the staged kernel alone; results never depend on it. */
+adac_status adac_scan_group_sum_product3(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
+                                         const uint64_t *d_b_words, adac_layout *c, const uint64_t *d_c_words,
+                                         adac_layout *keys, const uint64_t *d_key_words, const uint64_t *d_validity,
+                                         uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts);
+
 /* Diagnostic, not part of the drop-in boundary: *left = the number of scan groups of `l` that the register-walk kernel of
- * the layout's LAST grouped scan (adac_scan_group_sum, adac_scan_group_sum_valid or adac_scan_group_sum_product with `l`
- * as the value / `a` layout) left to the staged kernel; 0 when the walk took every group, when it was not launched (more
+ * the layout's LAST grouped scan (adac_scan_group_sum, adac_scan_group_sum_valid, adac_scan_group_sum_product or
+ * adac_scan_group_sum_product3 with `l` as the value / `a` layout) left to the staged kernel; 0 when the walk took every group, when it was not launched (more
  * than 8 bins, or its knob at 0: the staged kernel then takes everything) or when no grouped scan ran.  Synchronises the
  * context's stream.  The tests hold the kernels' choice of form against the host mirror of the rule with it. */
 adac_status adac_debug_group_handover(adac_layout *l, uint64_t *left);
