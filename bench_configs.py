@@ -701,6 +701,23 @@ def group_product3_form_groups(descs_a, descs_b, descs_c, descs_k, ngroups, a_ty
     return out
 
 
+def group_q1_form_groups(descs_a, descs_b, descs_c, descs_q, descs_k, ngroups, a_type=(4, True), b_type=(4, True),
+                         c_type=(4, True), q_type=(4, True), k_size=1):
+    """Which form of adac_scan_group_sum_q1 takes how many scan groups of `a` — group_q1_rw_eligible
+    (adac_group_q1.inl) evaluated on the host descriptors: group_product3_rw_eligible on (a, b, c, keys), and for q what
+    holds for c.  a_type / b_type / c_type / q_type: (type size, signed); k_size: the key type's size."""
+    out = {"fast": 0, "generic": 0}
+    for da, db, dc, dq, dk in zip(descs_a, descs_b, descs_c, descs_q, descs_k):
+        one = group_product3_form_groups([da], [db], [dc], [dk], ngroups, a_type, b_type, c_type, k_size)
+        # the condition on q is the one on c: the same rule with q in c's place, every other side already decided
+        if one["fast"] and not group_product3_form_groups([da], [db], [dq], [dk], ngroups, a_type, b_type, q_type,
+                                                          k_size)["fast"]:
+            one = {"fast": 0, "generic": one["fast"]}
+        out["fast"] += one["fast"]
+        out["generic"] += one["generic"]
+    return out
+
+
 def q1_disc_price_packed(adac, n=59_986_052):
     """Q1's sum_disc_price on packed columns: the columns of q1_filtered_packed that this plan reads (flag code,
     l_extendedprice, l_shipdate; same shapes, a random stream of its own) plus an int32 l_discount in [0, 10].  One
@@ -998,6 +1015,175 @@ def q1_full_packed(adac, n=59_986_052):
     return out
 
 
+def q1_fused_packed(adac, n=59_986_052):
+    """All of Q1's aggregates from ONE scan: q1_full_packed's data (same generator and seed), the same select, and
+    adac_scan_group_sum_q1 (price, discount, tax, quantity GROUP BY the flag code under the l_shipdate bitmap) in place of
+    the six grouped calls.  All eight Q1 output columns are built from the one call's seven terms
+      sum_disc_price = 100 SUM(p) - SUM(p d),   sum_charge = 10000 SUM(p) + 100 SUM(p t) - 100 SUM(p d) - SUM(p d t)
+    and checked against numpy before and after timing; the seven terms are also held against the six calls' results.
+    Timed warm and INTERLEAVED as in q1_full_packed (one process, medians over rounds): the select, each of the six
+    grouped calls, the fused call masked / unmasked / with its knob at 0, and adac_unpack of the five columns it reads."""
+    ctx = adac.Context(0)
+    rng = np.random.default_rng(1995)
+    code = rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8)
+    price = rng.integers(90_000, 10_495_000, size=n).astype(np.int32)
+    shipdate = rng.integers(8036, 10562, size=n).astype(np.int32)
+    qty = rng.integers(1, 51, size=n).astype(np.int32)
+    disc = rng.integers(0, 11, size=n).astype(np.int32)
+    tax = rng.integers(0, 9, size=n).astype(np.int32)
+    cutoff = 10511
+    counts = adac.appender_segment_counts(n, 4)
+
+    def enc_col(v):
+        lay = adac.Layout(ctx, v.dtype, counts)
+        d_vals = ctx.upload(v)
+        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
+        lay.encode(d_vals, d_words)
+        ctx.sync()
+        d_vals.free()
+        descs = lay.get_descs()
+        nbytes = int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
+        return lay, d_words, nbytes, sorted(set(descs["width"].tolist())), descs
+
+    cols = {"code": enc_col(code), "l_shipdate": enc_col(shipdate), "l_quantity": enc_col(qty),
+            "l_extendedprice": enc_col(price), "l_discount": enc_col(disc), "l_tax": enc_col(tax)}
+    klay, kwords = cols["code"][:2]
+    dlay, dwords = cols["l_shipdate"][:2]
+    qlay, qwords = cols["l_quantity"][:2]
+    play, pwords = cols["l_extendedprice"][:2]
+    clay, cwords = cols["l_discount"][:2]
+    tlay, twords = cols["l_tax"][:2]
+    d_filter = ctx.alloc((n + 63) // 64 * 8 + 8)
+    d_selcnt = ctx.alloc(len(counts) * 8)
+    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
+    res = {k: (ctx.alloc(7 * 8), ctx.alloc(7 * 8)) for k in ("q", "p", "d", "pd", "pt", "pdt")}
+    d_q1 = ctx.alloc(7 * 7 * 8)
+    select = lambda: dlay.scan_select_between(dwords, int_min, cutoff, d_filter, d_selcnt)
+    sum_q = lambda: qlay.scan_group_sum_valid(qwords, klay, kwords, d_filter, 6, *res["q"])
+    sum_p = lambda: play.scan_group_sum_valid(pwords, klay, kwords, d_filter, 6, *res["p"])
+    sum_d = lambda: clay.scan_group_sum_valid(cwords, klay, kwords, d_filter, 6, *res["d"])
+    sum_pd = lambda: play.scan_group_sum_product(pwords, clay, cwords, klay, kwords, 6, res["pd"][0], None, d_filter)
+    sum_pt = lambda: play.scan_group_sum_product(pwords, tlay, twords, klay, kwords, 6, res["pt"][0], None, d_filter)
+    sum_pdt = lambda: play.scan_group_sum_product3(pwords, clay, cwords, tlay, twords, klay, kwords, 6, res["pdt"][0],
+                                                   None, d_filter)
+    six = (sum_q, sum_p, sum_d, sum_pd, sum_pt, sum_pdt)
+
+    def fused(mask=True):
+        play.scan_group_sum_q1(pwords, clay, cwords, tlay, twords, qlay, qwords, klay, kwords, 6, d_q1,
+                               d_filter if mask else None)
+
+    def terms():
+        ctx.sync()
+        return d_q1.download(np.uint64, 49).reshape(7, 7).tolist()
+
+    keep = shipdate <= cutoff
+    p64, d64, t64, q64 = price.astype(np.int64), disc.astype(np.int64), tax.astype(np.int64), qty.astype(np.int64)
+
+    def expected(bins):
+        rows = [int(b.sum()) for b in bins]
+        sq, sp, sd = ([int(v[b].sum()) for b in bins] for v in (q64, p64, d64))
+        return {"sum_qty": sq, "sum_base_price": sp,
+                "sum_disc_price": [int((p64[b] * (100 - d64[b])).sum()) for b in bins],
+                "sum_charge": [int((p64[b] * (100 - d64[b]) * (100 + t64[b])).sum()) for b in bins],
+                "avg_qty": list(zip(sq, rows)), "avg_price": list(zip(sp, rows)), "avg_disc": list(zip(sd, rows)),
+                "count_order": rows}
+
+    def outputs():
+        """Q1's eight output columns per group, as integers, from the one call's seven terms"""
+        t = terms()
+        assert all(row[6] == 0 for row in t), "no row has a key >= 6"
+        cnt, sq, sp, sd, spd, spt, spdt = (t[i] for i in (adac.Q1_COUNT, adac.Q1_SUM_Q, adac.Q1_SUM_A, adac.Q1_SUM_B,
+                                                          adac.Q1_SUM_AB, adac.Q1_SUM_AC, adac.Q1_SUM_ABC))
+        g6 = range(6)
+        return {"sum_qty": [sq[g] for g in g6], "sum_base_price": [sp[g] for g in g6],
+                "sum_disc_price": [100 * sp[g] - spd[g] for g in g6],
+                "sum_charge": [10000 * sp[g] + 100 * spt[g] - 100 * spd[g] - spdt[g] for g in g6],
+                "avg_qty": [(sq[g], cnt[g]) for g in g6], "avg_price": [(sp[g], cnt[g]) for g in g6],
+                "avg_disc": [(sd[g], cnt[g]) for g in g6], "count_order": [cnt[g] for g in g6]}
+
+    def parity(what, exp):
+        got = outputs()
+        for name, want in exp.items():
+            assert got[name] == want, (what, name)
+
+    exp_masked = expected([(code == g) & keep for g in range(6)])
+    exp_all = expected([code == g for g in range(6)])
+    forms = group_q1_form_groups(cols["l_extendedprice"][4], cols["l_discount"][4], cols["l_tax"][4],
+                                 cols["l_quantity"][4], cols["code"][4], 6)
+    select()
+    for f in six:
+        f()
+    ctx.sync()
+    s6 = {k: v[0].download(np.uint64, 7).tolist() for k, v in res.items()}
+    c6 = res["p"][1].download(np.uint64, 7).tolist()
+    for knob in (0, 1):  # both forms against numpy and against the six calls; the hand-over against the mirror
+        adac.set_tuning("group_q1_rw", knob)
+        fused()
+        parity(("Q1 parity", knob), exp_masked)
+        assert terms() == [c6, s6["q"], s6["p"], s6["d"], s6["pd"], s6["pt"], s6["pdt"]], ("the six calls", knob)
+        assert play.debug_group_handover() == (forms["generic"] if knob else 0), ("hand-over", knob)
+    fused(mask=False)
+    parity("Q1 parity, unmasked", exp_all)
+    d_out = ctx.alloc(n * 4 + 64)
+
+    def unpack_five():
+        play.unpack(pwords, d_out)
+        clay.unpack(cwords, d_out)
+        tlay.unpack(twords, d_out)
+        qlay.unpack(qwords, d_out)
+        klay.unpack(kwords, d_out)
+
+    def staged_only():
+        adac.set_tuning("group_q1_rw", 0)
+        fused()
+        adac.set_tuning("group_q1_rw", 1)
+
+    six_names = ("group_sum_quantity_masked", "group_sum_price_masked", "group_sum_discount_masked",
+                 "group_sum_product_price_disc_masked", "group_sum_product_price_tax_masked", "group_sum_product3_masked")
+    timed = (("select", select),) + tuple(zip(six_names, six)) + (
+        ("group_sum_q1_masked", fused), ("group_sum_q1_unmasked", lambda: fused(mask=False)),
+        ("group_sum_q1_masked_staged_kernel_only", staged_only), ("unpack_price_discount_tax_quantity_and_code", unpack_five))
+    # warm and interleaved, as in q1_full_packed: an untimed round, then `rounds` rounds in which every entry runs `inner`
+    # times back to back between two events of its own; the figure is the median over the rounds of the time per call
+    rounds, inner = 8, 5
+    samples = {name: [] for name, _ in timed}
+    for r in range(rounds + 1):
+        for name, fn in timed:
+            ctx.timer_start()
+            for _ in range(inner):
+                fn()
+            t = ctx.timer_stop() / inner
+            if r:
+                samples[name].append(t)
+    ms = {name: float(np.median(v)) for name, v in samples.items()}
+    fused()  # leave the masked result behind and check it once more after the timed loops
+    parity("Q1 parity (after timing)", exp_masked)
+    five = sum(cols[k][2] for k in ("l_extendedprice", "l_discount", "l_tax", "l_quantity", "code"))
+    six_ms = sum(ms[name] for name in six_names)
+    out = {"rows": n, "groups": 6, "cutoff_day": cutoff, "selected_rows": int(keep.sum()),
+           "widths": {k: v[3] for k, v in cols.items()}, "packed_bytes": {k: v[2] for k, v in cols.items()},
+           "rounds": rounds, "calls_per_round": inner, "step_ms": ms,
+           "step_ms_min": {name: float(min(v)) for name, v in samples.items()},
+           "six_grouped_calls_ms": six_ms,
+           "fused_over_six_calls": ms["group_sum_q1_masked"] / six_ms,
+           "fused_faster_than_six_calls": ms["group_sum_q1_masked"] < six_ms,
+           "group_sum_q1_packed_read_GBps": (five + n / 8) / (ms["group_sum_q1_masked"] * 1e-3) / 1e9,
+           "fused_over_unpack_five_columns": ms["group_sum_q1_masked"] / ms["unpack_price_discount_tax_quantity_and_code"],
+           "register_walk_faster_than_staged_only": ms["group_sum_q1_masked"] < ms["group_sum_q1_masked_staged_kernel_only"],
+           "groups_by_form": forms,
+           "q1_output": {k: [list(x) if isinstance(x, tuple) else x for x in v] for k, v in outputs().items()},
+           "note": "group_sum_q1_masked = adac_scan_group_sum_q1(l_extendedprice, l_discount, l_tax, l_quantity) GROUP BY the "
+                   "flag code under the l_shipdate bitmap: the seven terms all eight Q1 output columns are made of; "
+                   "six_grouped_calls_ms = the sum of the medians of the six grouped calls it replaces; all figures are "
+                   "medians over 8 interleaved rounds of the time per call, 5 calls back to back per entry and round, "
+                   "warm, one process (step_ms_min: the fastest round)"}
+    ctx.close()
+    # the condition the fused call exists for: it must beat, in this one interleaved process, the six calls it replaces
+    assert out["fused_faster_than_six_calls"], "adac_scan_group_sum_q1 %.4f ms is not below the six grouped calls' %.4f ms: %s" % (
+        ms["group_sum_q1_masked"], six_ms, json.dumps(ms))
+    return out
+
+
 def c1_lookups(adac, wl, n=10_000_000, nlookups=10_000):
     """C1 (benchmark/micro/succinct/zipf_distribution.cpp:13-48): t1(i UINTEGER) with i = 0..N-1, compacted, then
     `SELECT i FROM t1 WHERE i == k` for Zipf(N, 1.0) keys (mt19937, seed 42).  Each look-up is one fused
@@ -1048,6 +1234,7 @@ def main():
             "q1_filtered_packed": lambda: q1_filtered_packed(adac),
             "q1_disc_price_packed": lambda: q1_disc_price_packed(adac),
             "q1_full_packed": lambda: q1_full_packed(adac),
+            "q1_fused_packed": lambda: q1_fused_packed(adac),
             "c1_lookups": lambda: c1_lookups(adac, wl)}
     res = {k: f() for k, f in jobs.items() if not only or k in only}
     print(json.dumps(res))

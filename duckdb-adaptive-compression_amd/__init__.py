@@ -23,6 +23,9 @@ UINT8, INT8, UINT16, INT16, UINT32, INT32, UINT64, INT64 = 2, 3, 4, 5, 6, 7, 8, 
 RULE_APPEND, RULE_RECOMPACT = 0, 1
 NO_MIN = 0xFFFFFFFFFFFFFFFF
 SEG_PACKED = 1
+# adac_scan_group_sum_q1: term t of group g is d_out[t * (ngroups + 1) + g]
+Q1_TERMS = 7
+Q1_COUNT, Q1_SUM_Q, Q1_SUM_A, Q1_SUM_B, Q1_SUM_AB, Q1_SUM_AC, Q1_SUM_ABC = range(7)
 
 _NP2TYPE = {
     np.dtype(np.uint8): UINT8, np.dtype(np.int8): INT8, np.dtype(np.uint16): UINT16, np.dtype(np.int16): INT16,
@@ -167,6 +170,7 @@ SIGNATURES = {
     "adac_scan_sum_product": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "adac_scan_group_sum_product": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "adac_scan_group_sum_product3": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "adac_scan_group_sum_q1": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "adac_debug_group_handover": (_int, [_vp, _vp]),
     "adac_scan_count_eq": (_int, [_vp, _vp, _u64, _vp]),
     "adac_scan_count_between": (_int, [_vp, _vp, _u64, _u64, _vp]),
@@ -569,6 +573,16 @@ class Layout:
         _check(lib().adac_scan_group_sum_product3(self._h, _dptr(d_words), b._h, _dptr(d_b_words), c._h, _dptr(d_c_words),
                                                   keys._h, _dptr(d_key_words), _dptr(d_validity), int(ngroups),
                                                   _dptr(d_sums), _dptr(d_counts)), "adac_scan_group_sum_product3")
+
+    def scan_group_sum_q1(self, d_words, b, d_b_words, c, d_c_words, q, d_q_words, keys, d_key_words, ngroups, d_out,
+                          d_validity=None):
+        """All of Q1's grouped sums in one scan: d_out[t * (ngroups + 1) + g] for t in Q1_COUNT, Q1_SUM_Q (q), Q1_SUM_A
+        (self), Q1_SUM_B, Q1_SUM_AB, Q1_SUM_AC, Q1_SUM_ABC GROUP BY `keys` (`b`, `c`, `q`, `keys`: Layouts over the same
+        rows; each value widened by its own type's signedness, products mod 2^64) over the rows whose bit is set in
+        d_validity, a mask in THIS layout's element space.  d_out: 7 * (ngroups + 1) words."""
+        _check(lib().adac_scan_group_sum_q1(self._h, _dptr(d_words), b._h, _dptr(d_b_words), c._h, _dptr(d_c_words), q._h,
+                                            _dptr(d_q_words), keys._h, _dptr(d_key_words), _dptr(d_validity),
+                                            int(ngroups), _dptr(d_out)), "adac_scan_group_sum_q1")
 
     def debug_group_handover(self):
         """Scan groups the register-walk kernel of this layout's last grouped scan left to the staged kernel."""

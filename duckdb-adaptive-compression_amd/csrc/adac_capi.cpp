@@ -358,6 +358,7 @@ extern "C" int adac_set_tuning(const char *name, int value) {
 	    {"group_sum_rw", &adac::Tuning::group_sum_rw, INT_MIN},
 	    {"group_product_rw", &adac::Tuning::group_product_rw, INT_MIN},
 	    {"group_product3_rw", &adac::Tuning::group_product3_rw, INT_MIN},
+	    {"group_q1_rw", &adac::Tuning::group_q1_rw, INT_MIN},
 	    {"templated_scan", &adac::Tuning::templated_scan, INT_MIN},
 	    {"scan_tiles_per_wg", &adac::Tuning::scan_tiles_per_wg, 0}, // 0 = by type
 	    {"num_cus", &adac::Tuning::num_cus, 0},                     // 0 = the device's own count
@@ -1194,6 +1195,44 @@ extern "C" adac_status adac_scan_group_sum_product3(adac_layout *a, const uint64
 	                                     a->d_groups, a->ngroups, d_a_words, b->d_descs, d_b_words, c->d_descs, d_c_words,
 	                                     keys->d_descs, d_key_words, ngroups, a->d_group_partial, a->group_calls++,
 	                                     d_validity, d_sums, d_counts));
+	return ADAC_OK;
+}
+
+// All of Q1's grouped sums in one scan over five packed columns of one table: COUNT, SUM(q), SUM(a), SUM(b), SUM(a * b),
+// SUM(a * c), SUM(a * b * c) GROUP BY key under a selection bitmap
+extern "C" adac_status adac_scan_group_sum_q1(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
+                                              const uint64_t *d_b_words, adac_layout *c, const uint64_t *d_c_words,
+                                              adac_layout *q, const uint64_t *d_q_words, adac_layout *keys,
+                                              const uint64_t *d_key_words, const uint64_t *d_validity, uint32_t ngroups,
+                                              uint64_t *d_out) {
+	if (!a || !b || !c || !q || !keys || !d_out) return ADAC_ERR_INVALID_ARGUMENT;
+	if (a->ctx != b->ctx || a->ctx != c->ctx || a->ctx != q->ctx || a->ctx != keys->ctx) return ADAC_ERR_INVALID_ARGUMENT;
+	if (ngroups == 0 || ngroups > adac::group_sum_max_groups()) return ADAC_ERR_INVALID_ARGUMENT;
+	// the same rows, segment by segment
+	if (a->counts != b->counts || a->counts != c->counts || a->counts != q->counts || a->counts != keys->counts) {
+		return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	if (a->total_values && (!d_a_words || !d_b_words || !d_c_words || !d_q_words || !d_key_words)) {
+		return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	if (!aligned16(d_a_words) || !aligned16(d_b_words) || !aligned16(d_c_words) || !aligned16(d_q_words) ||
+	    !aligned16(d_key_words)) {
+		return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	ADAC_HIP(hipSetDevice(a->ctx->device));
+	// the partial buffer, the call counter and the hand-over slots are a's, shared with the other grouped scans
+	if (!a->d_group_partial) {
+		ADAC_HIP(hipMalloc(&a->d_group_partial, adac::group_sum_partial_bytes()));
+		ADAC_HIP(hipMemsetAsync(a->d_group_partial, 0, adac::group_sum_partial_bytes(), a->ctx->stream));
+	}
+	adac_status gst = ensure_scan_groups(a); // the register-walk kernel's work items
+	if (gst != ADAC_OK) return gst;
+	const uint32_t type_size[5] = {a->type_size, b->type_size, c->type_size, q->type_size, keys->type_size};
+	const bool is_signed[5] = {a->is_signed, b->is_signed, c->is_signed, q->is_signed, keys->is_signed};
+	ADAC_HIP(adac::launch_group_q1(a->ctx->stream, type_size, is_signed, a->d_descs, a->d_tiles, a->ntiles, a->d_groups,
+	                               a->ngroups, d_a_words, b->d_descs, d_b_words, c->d_descs, d_c_words, q->d_descs,
+	                               d_q_words, keys->d_descs, d_key_words, ngroups, a->d_group_partial, a->group_calls++,
+	                               d_validity, d_out));
 	return ADAC_OK;
 }
 

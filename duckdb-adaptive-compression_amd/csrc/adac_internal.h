@@ -102,6 +102,7 @@ struct Tuning {
 	int group_sum_rw = 1;       // A/B: 0 = adac_scan_group_sum without the register-walk kernel (k_group_sum only)
 	int group_product_rw = 1;   // A/B: 0 = adac_scan_group_sum_product without the register-walk kernel (k_group_product only)
 	int group_product3_rw = 1;  // A/B: 0 = adac_scan_group_sum_product3 without the register-walk kernel (k_group_product3 only)
+	int group_q1_rw = 1;        // A/B: 0 = adac_scan_group_sum_q1 without the register-walk kernel (k_group_q1 only)
 	int encode_placement = 0;   // single-pass encode: 0 = arena order is segment order (look-back), 1 = order of completion
 	int encode_big_image = 1;   // single-pass encode, ordered placement: a segment whose packed words fit the LDS pool is packed there whole and publishes the NEXT footprint before it waits (A/B: 0)
 	int encode_publish_ahead = 1; // single-pass encode, ordered placement: the parked flow publishes the NEXT footprint before it waits (A/B: 0)
@@ -178,6 +179,17 @@ hipError_t launch_group_product3(hipStream_t s, uint32_t a_type_size, bool a_sig
                                  const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups,
                                  void *d_partial, uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums,
                                  uint64_t *d_counts);
+// COUNT and the six sums of Q1 GROUP BY key over five packed columns of one table under a selection bitmap, one scan
+// (adac_group_q1.inl); type_size / is_signed: a, b, c, q, keys; d_partial / call_parity: launch_group_sum's;
+// d_out: 7 x (ngroups + 1) words, term t of group g at [t * (ngroups + 1) + g]
+hipError_t launch_group_q1(hipStream_t s, const uint32_t (&type_size)[5], const bool (&is_signed)[5],
+                           const adac_segment_desc *d_adescs, const TileRef *d_atiles, uint64_t ntiles,
+                           const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
+                           const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
+                           const adac_segment_desc *d_cdescs, const uint64_t *d_cwords,
+                           const adac_segment_desc *d_qdescs, const uint64_t *d_qwords,
+                           const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups, void *d_partial,
+                           uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_out);
 // SUM(a * b) over two packed columns of one table under a selection bitmap (adac_sum_product.inl)
 hipError_t launch_scan_sum_product(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
                                    const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,

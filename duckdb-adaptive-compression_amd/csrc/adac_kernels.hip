@@ -1954,6 +1954,7 @@ hipError_t dispatch_size(uint32_t type_size, F &&f) {
 #include "adac_sum_product.inl"
 #include "adac_group_product.inl"
 #include "adac_group_product3.inl"
+#include "adac_group_q1.inl"
 
 } // namespace
 
@@ -2230,6 +2231,73 @@ hipError_t launch_group_product3(hipStream_t s, uint32_t a_type_size, bool a_sig
 	}
 	hipLaunchKernelGGL(k_group_final, dim3(nbins), dim3(kWorkgroup), 0, s, partial, nwg_rw, nwg, nbins, d_sums,
 	                   d_counts, static_cast<const unsigned long long *>(fallback), next_fallback, rw ? 1 : 0);
+	return hipGetLastError();
+}
+
+// COUNT, SUM(q), SUM(a), SUM(b), SUM(a * b), SUM(a * c), SUM(a * b * c) GROUP BY key under a selection bitmap in one scan
+// (adac_group_q1.inl).  launch_group_product3's three steps with a fifth column and seven terms, on the same partial
+// buffer and hand-over slots (d_partial, call_parity: the `a` layout's, shared between the grouped entry points).  A
+// workgroup's partial row is 7 x nbins words here, not 2 x nbins, so the grids are sized to what the buffer holds too.
+hipError_t launch_group_q1(hipStream_t s, const uint32_t (&type_size)[5], const bool (&is_signed)[5],
+                           const adac_segment_desc *d_adescs, const TileRef *d_atiles, uint64_t ntiles,
+                           const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
+                           const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
+                           const adac_segment_desc *d_cdescs, const uint64_t *d_cwords,
+                           const adac_segment_desc *d_qdescs, const uint64_t *d_qwords,
+                           const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups, void *d_partial,
+                           uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_out) {
+	GroupQ1Types ty; // type_size / is_signed: a, b, c, q, keys
+	ty.g.g.p.a_tmask = type_mask(type_size[0]);
+	ty.g.g.p.a_sbit = type_sign_bit(type_size[0], is_signed[0]);
+	ty.g.g.p.b_tmask = type_mask(type_size[1]);
+	ty.g.g.p.b_sbit = type_sign_bit(type_size[1], is_signed[1]);
+	ty.g.c_tmask = type_mask(type_size[2]);
+	ty.g.c_sbit = type_sign_bit(type_size[2], is_signed[2]);
+	ty.q_tmask = type_mask(type_size[3]);
+	ty.q_sbit = type_sign_bit(type_size[3], is_signed[3]);
+	ty.g.g.k_tmask = type_mask(type_size[4]);
+	ty.g.g.a_tile_rows = tile_values(type_size[0]);
+	const uint32_t nbins = ngroups + 1u;
+	unsigned long long *partial = static_cast<unsigned long long *>(d_partial);
+	unsigned long long *fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + (call_parity & 1u);
+	unsigned long long *next_fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + ((call_parity + 1u) & 1u);
+	// partial rows the buffer holds, half for either kernel (257 bins: 585 rows each; 8 bins: more than either grid asks for)
+	const uint64_t rows_cap = ((uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins) / ((uint64_t)kGroupQ1Terms * nbins) / 2u;
+	// 1. the register-walk kernel over a's scan groups (up to 8 bins; persistent, kGroupQ1RwResident workgroups per CU);
+	//    it counts the scan groups it cannot take in *fallback
+	uint32_t nwg_rw = 0;
+	const bool rw = nbins <= kGroupPrivateBins && g_tuning.group_q1_rw && nagroups > 0;
+	if (rw) {
+		uint64_t cap = (uint64_t)kGroupQ1RwResident * device_cus();
+		cap = cap < rows_cap ? cap : rows_cap;
+		nwg_rw = (uint32_t)(nagroups < cap ? nagroups : cap);
+		auto launch = [&](auto kernel) {
+			hipLaunchKernelGGL(kernel, dim3(nwg_rw), dim3(kWorkgroup), 0, s, d_agroups, (uint32_t)nagroups, d_awords, d_bdescs,
+			                   d_bwords, d_cdescs, d_cwords, d_qdescs, d_qwords, d_kdescs, d_kwords, ty, ngroups, partial,
+			                   fallback, d_validity);
+		};
+		if (d_validity) launch(k_group_q1_rw<true>); else launch(k_group_q1_rw<false>);
+		hipError_t e = hipGetLastError();
+		if (e != hipSuccess) return e;
+	}
+	// 2. the staged-LDS kernel over a's tiles: everything when the first kernel did not run, else what it left (its
+	//    workgroups leave at once when that is nothing).  Persistent: as many workgroups as are resident at once
+	uint64_t cap = (uint64_t)kGroupQ1Resident * device_cus();
+	cap = cap < rows_cap ? cap : rows_cap;
+	const uint32_t nwg = (uint32_t)(ntiles < cap ? ntiles : cap);
+	if (nwg) {
+		const unsigned long long *handed = rw ? fallback : static_cast<const unsigned long long *>(nullptr);
+		auto launch = [&](auto kernel) {
+			hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles, d_awords,
+			                   d_bdescs, d_bwords, d_cdescs, d_cwords, d_qdescs, d_qwords, d_kdescs, d_kwords, ty, ngroups,
+			                   partial + (uint64_t)nwg_rw * kGroupQ1Terms * nbins, handed, d_validity);
+		};
+		if (d_validity) launch(k_group_q1<true>); else launch(k_group_q1<false>);
+		hipError_t e = hipGetLastError();
+		if (e != hipSuccess) return e;
+	}
+	hipLaunchKernelGGL(k_group_q1_final, dim3(nbins), dim3(kWorkgroup), 0, s, partial, nwg_rw, nwg, nbins, d_out,
+	                   static_cast<const unsigned long long *>(fallback), next_fallback, rw ? 1 : 0);
 	return hipGetLastError();
 }
 

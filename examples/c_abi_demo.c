@@ -3,7 +3,7 @@
  *       -Wl,-rpath,$PWD/duckdb-adaptive-compression_amd -o /tmp/c_abi_demo && /tmp/c_abi_demo
  * Packs a small uint32 column of three ragged segments, scans it back, runs a filter + masked SUM on the packed
  * bytes, materialises the selected rows and runs a grouped triple product (SUM(v * v * v) GROUP BY a small key column)
- * under the same filter.  Exits 0 only if every result is right. */
+ * under the same filter, then all seven grouped terms of Q1 in one fused call.  Exits 0 only if every result is right. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -124,6 +124,30 @@ int main(void) {
 		       (unsigned long long)gsum[g]);
 		if (gsum[g] != exp_gsum[g] || gcnt[g] != exp_gcnt[g]) return 8;
 	}
+
+	/* the same scan as ONE fused call with v in all four value roles: COUNT, three times SUM(v), twice SUM(v * v) and
+	 * SUM(v * v * v) per group — held against the triple product above and against the host */
+	void *d_q1 = NULL;
+	CHECK(adac_dev_alloc(ctx, ADAC_Q1_TERMS * (NGROUPS + 1) * 8, &d_q1));
+	CHECK(adac_scan_group_sum_q1(col, (const uint64_t *)d_words, col, (const uint64_t *)d_words, col,
+	                             (const uint64_t *)d_words, col, (const uint64_t *)d_words, kcol,
+	                             (const uint64_t *)d_kwords, (const uint64_t *)d_bitmap, NGROUPS, (uint64_t *)d_q1));
+	uint64_t q1[ADAC_Q1_TERMS][NGROUPS + 1], exp_s1[NGROUPS + 1] = {0}, exp_s2[NGROUPS + 1] = {0};
+	CHECK(adac_memcpy_d2h(ctx, q1, d_q1, sizeof q1));
+	for (uint64_t i = 0; i < n; i++) {
+		if (vals[i] >= 1001000u && vals[i] <= 1001999u) {
+			const unsigned g = keys[i] < NGROUPS ? keys[i] : NGROUPS;
+			exp_s1[g] += vals[i];
+			exp_s2[g] += (uint64_t)vals[i] * vals[i];
+		}
+	}
+	for (int g = 0; g <= NGROUPS; g++) {
+		if (q1[ADAC_Q1_COUNT][g] != gcnt[g] || q1[ADAC_Q1_SUM_ABC][g] != gsum[g]) return 9; /* the separate call */
+		if (q1[ADAC_Q1_SUM_Q][g] != exp_s1[g] || q1[ADAC_Q1_SUM_A][g] != exp_s1[g] || q1[ADAC_Q1_SUM_B][g] != exp_s1[g]) return 10;
+		if (q1[ADAC_Q1_SUM_AB][g] != exp_s2[g] || q1[ADAC_Q1_SUM_AC][g] != exp_s2[g]) return 11;
+	}
+	printf("fused call: seven terms per group agree\n");
+	adac_dev_free(ctx, d_q1);
 	adac_dev_free(ctx, d_keys);
 	adac_dev_free(ctx, d_kwords);
 	adac_dev_free(ctx, d_gsums);

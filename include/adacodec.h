@@ -141,8 +141,8 @@ uint32_t adac_tile_values(int physical_type);
 /* Launch-shape knobs for in-process A/B measurement: "templated_scan" (0/1), "scan_tiles_per_wg" (tiles per fused-scan
  * workgroup; 0 = chosen by type), "num_cus" (0 = the device's own count), "single_pass_encode" (0 = analyze + plan +
  * pack as three kernels), "encode_big_image", "encode_publish_ahead", "scan_cells", "tile_records", "gather_compact",
- * "group_sum_wide", "group_sum_rw", "group_product_rw", "group_product3_rw", "sel_debug": the table in adac_set_tuning is the
- * full list, Tuning in
+ * "group_sum_wide", "group_sum_rw", "group_product_rw", "group_product3_rw", "group_q1_rw", "sel_debug": the table in
+ * adac_set_tuning is the full list, Tuning in
  * csrc/adac_internal.h says what each does.  Decoded values, packed words, widths and mins never depend on them.  One
  * knob changes WHERE adac_encode puts a segment in the arena: "encode_placement" 1 hands out arena space in order of
  * completion (a cursor, no ordered look-back) instead of the exclusive prefix in segment order that adac_plan computes:
@@ -430,9 +430,48 @@ adac_status adac_scan_group_sum_product3(adac_layout *a, const uint64_t *d_a_wor
                                          adac_layout *keys, const uint64_t *d_key_words, const uint64_t *d_validity,
                                          uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts);
 
+/* All of TPC-H Q1's grouped sums in ONE scan over FIVE packed columns of one table — what the three
+ * adac_scan_group_sum_valid, two adac_scan_group_sum_product and one adac_scan_group_sum_product3 calls of the plan above
+ * return, with every column, the keys and the mask read once.  In Q1 a = l_extendedprice, b = l_discount, c = l_tax,
+ * q = l_quantity.  `a`, `b`, `c`, `q` and `keys` are layouts on the same context with the same row count per segment
+ * (types, widths, placements, encode rules and value offsets may differ); any of a, b, c, q may be the same layout with
+ * the same words; nothing is materialised.
+ * d_out holds ADAC_Q1_TERMS * (ngroups + 1) words: term t of group g is d_out[t * (ngroups + 1) + g], over the rows whose
+ * key is g and whose bit is set in d_validity:
+ *   ADAC_Q1_COUNT    the number of those rows           (adac_scan_group_sum_valid's d_counts)
+ *   ADAC_Q1_SUM_Q    the sum of widen(q)                (adac_scan_group_sum_valid on q)
+ *   ADAC_Q1_SUM_A    the sum of widen(a)                (... on a)
+ *   ADAC_Q1_SUM_B    the sum of widen(b)                (... on b)
+ *   ADAC_Q1_SUM_AB   the sum of widen(a) * widen(b)     (adac_scan_group_sum_product on a, b)
+ *   ADAC_Q1_SUM_AC   the sum of widen(a) * widen(c)     (... on a, c)
+ *   ADAC_Q1_SUM_ABC  the sum of widen(a) * widen(b) * widen(c)   (adac_scan_group_sum_product3)
+ * Each value is widened to 64 bits by its own column's signedness; products and sums are taken mod 2^64.  key = the key
+ * column's value as an unsigned number of its own width; rows whose key is >= ngroups go to entry [ngroups];
+ * 1 <= ngroups <= 256.
+ * d_validity is indexed in a's element space (a's val_off + row); the value offsets of b, c, q and keys play no part.
+ * NULL = every row.  Bits that belong to no row never influence a result, and the call reads no mask word outside the
+ * ceil(value_span(a) / 64) words of a's layout.  A row whose bit is clear contributes to no term, COUNT and the overflow
+ * entry included.
+ * d_out is fully written by the call and needs no clearing, also when the layouts have no rows.  The call enqueues on
+ * the context's stream and synchronises no more than adac_scan_group_sum_product3 does.  The partial buffer, the call
+ * counter and the hand-over slots are a's, shared with the other grouped scans: the entry points may be called in any
+ * order on one layout.
+ * ADAC_ERR_INVALID_ARGUMENT: a NULL layout; layouts on different contexts; per-segment counts that differ between any
+ * two of the five layouts; ngroups 0 or > 256; NULL d_out; a NULL words pointer while there are rows; a words pointer
+ * that is not 16-byte aligned.
+ * The tuning knob "group_q1_rw" (default 1) chooses between the register-walk kernel with the staged kernel for what it
+ * leaves, and (0) the staged kernel alone; results never depend on it. */
+#define ADAC_Q1_TERMS 7
+enum { ADAC_Q1_COUNT = 0, ADAC_Q1_SUM_Q = 1, ADAC_Q1_SUM_A = 2, ADAC_Q1_SUM_B = 3,
+       ADAC_Q1_SUM_AB = 4, ADAC_Q1_SUM_AC = 5, ADAC_Q1_SUM_ABC = 6 };
+adac_status adac_scan_group_sum_q1(adac_layout *a, const uint64_t *d_a_words, adac_layout *b, const uint64_t *d_b_words,
+                                   adac_layout *c, const uint64_t *d_c_words, adac_layout *q, const uint64_t *d_q_words,
+                                   adac_layout *keys, const uint64_t *d_key_words, const uint64_t *d_validity,
+                                   uint32_t ngroups, uint64_t *d_out);
+
 /* Diagnostic, not part of the drop-in boundary: *left = the number of scan groups of `l` that the register-walk kernel of
- * the layout's LAST grouped scan (adac_scan_group_sum, adac_scan_group_sum_valid, adac_scan_group_sum_product or
- * adac_scan_group_sum_product3 with `l` as the value / `a` layout) left to the staged kernel; 0 when the walk took every group, when it was not launched (more
+ * the layout's LAST grouped scan (adac_scan_group_sum, adac_scan_group_sum_valid, adac_scan_group_sum_product,
+ * adac_scan_group_sum_product3 or adac_scan_group_sum_q1 with `l` as the value / `a` layout) left to the staged kernel; 0 when the walk took every group, when it was not launched (more
  * than 8 bins, or its knob at 0: the staged kernel then takes everything) or when no grouped scan ran.  Synchronises the
  * context's stream.  The tests hold the kernels' choice of form against the host mirror of the rule with it. */
 adac_status adac_debug_group_handover(adac_layout *l, uint64_t *left);
