@@ -627,6 +627,124 @@ def q6_product_packed(adac, n=59_986_052):
     return out
 
 
+def q6_bitpacking(adac, n=59_986_052):
+    """TPC-H Q6 end to end on DuckDB's own BITPACKING blocks: q6_product_packed's four int32 columns compressed the way
+    bitpacking_fused_scans builds its columns, the three chained adac_bp_scan_select_between calls, then
+    adac_bp_scan_sum_product(l_extendedprice, l_discount) under the final bitmap — checked against numpy.  Beside it, in
+    the same process and interleaved: adac_bp_unpack of the two columns the product reads (what a caller paid before it
+    could start to multiply).  Second line: adac_bp_scan_group_sum of l_quantity by a 6-valued uint8 code column under
+    Q1's bitmap (l_shipdate <= cutoff), against adac_bp_unpack of those two columns."""
+    from oracle import bitpacking as bp
+    ctx = adac.Context(0)
+    rng = np.random.default_rng(1994)
+    cols = {"l_shipdate": rng.integers(8036, 10562, size=n).astype(np.int32),
+            "l_discount": rng.integers(0, 11, size=n).astype(np.int32),
+            "l_quantity": rng.integers(1, 51, size=n).astype(np.int32),
+            "l_extendedprice": rng.integers(90_000, 10_495_000, size=n).astype(np.int32),
+            "code": rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8)}
+    stride = 262144
+    enc, packed_bytes, info = {}, {}, {}
+    for name, v in cols.items():
+        comp = bp.Compressed(v)
+        nseg = comp.nseg
+        buf = np.zeros(nseg * stride + 64, dtype=np.uint8)
+        counts = np.zeros(nseg, dtype=np.uint32)
+        used = 0
+        for i in range(nseg):
+            buf[i * stride:i * stride + bp.BLOCK_SIZE] = comp.block(i)
+            counts[i] = comp.count(i)
+            used += comp.size(i)
+        lay = adac.BitpackingLayout(ctx, v.dtype, np.arange(nseg, dtype=np.uint64) * stride, counts)
+        enc[name] = (lay, ctx.upload(buf), nseg)
+        packed_bytes[name] = used
+        info[name] = {"segments": nseg, "groups": int(lay.ngroups), "modes": comp.groups_by_mode(),
+                      "width_of_group_0": comp.group_info(0, 0)[2]}
+        del comp, buf
+    nw = (n + 63) // 64
+    bm = [ctx.alloc(nw * 8 + 8) for _ in range(3)]
+    d_q1 = ctx.alloc(nw * 8 + 8)
+    price, disc, qty, ship, code = (enc[k] for k in ("l_extendedprice", "l_discount", "l_quantity", "l_shipdate", "code"))
+    d_cnt = ctx.alloc(max(e[2] for e in enc.values()) * 8)
+    d_sum = ctx.alloc(price[2] * 8)
+    d_gsum, d_gcnt = ctx.alloc(7 * 8), ctx.alloc(7 * 8)
+    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
+    cutoff = 10511
+
+    def selects():
+        ship[0].scan_select_between(ship[1], 8766, 9130, bm[0], d_cnt)              # 1994-01-01 .. 1994-12-31
+        disc[0].scan_select_between(disc[1], 5, 7, bm[1], d_cnt, bm[0])
+        qty[0].scan_select_between(qty[1], int_min, 23, bm[2], d_cnt, bm[1])
+
+    def product():
+        price[0].scan_sum_product(price[1], disc[0], disc[1], d_sum, bm[2])
+
+    def q6():
+        selects()
+        product()
+
+    def grouped():
+        qty[0].scan_group_sum(qty[1], code[0], code[1], 6, d_gsum, d_gcnt, d_q1)
+
+    q6()
+    ship[0].scan_select_between(ship[1], int_min, cutoff, d_q1, d_cnt)
+    grouped()
+    ctx.sync()
+    m = ((cols["l_shipdate"] >= 8766) & (cols["l_shipdate"] <= 9130) & (cols["l_discount"] >= 5) &
+         (cols["l_discount"] <= 7) & (cols["l_quantity"] < 24))
+    want_q6 = int((cols["l_extendedprice"][m].astype(np.int64) * cols["l_discount"][m]).sum())
+    assert int(d_sum.download(np.uint64, price[2]).sum(dtype=np.uint64)) == want_q6, "Q6 parity"
+    keep = cols["l_shipdate"] <= cutoff
+    want_gs = np.bincount(cols["code"][keep], weights=None, minlength=7).astype(np.uint64)
+    want_sum = np.zeros(7, dtype=np.int64)
+    np.add.at(want_sum, cols["code"][keep], cols["l_quantity"][keep].astype(np.int64))
+    assert np.array_equal(d_gcnt.download(np.uint64, 7), want_gs), "grouped COUNT parity"
+    assert np.array_equal(d_gsum.download(np.uint64, 7), want_sum.view(np.uint64)), "grouped SUM parity"
+    reps = 20
+    d_out = ctx.alloc(n * 4 + 64)
+
+    def unpack_price_disc():
+        price[0].unpack(price[1], d_out)
+        disc[0].unpack(disc[1], d_out)
+
+    def unpack_qty_code():
+        qty[0].unpack(qty[1], d_out)
+        code[0].unpack(code[1], d_out)
+
+    ms = {}
+    for name, fn in (("q6_on_bitpacking", q6), ("select_chain", selects), ("sum_product_masked", product),
+                     ("unpack_price_and_discount", unpack_price_disc),
+                     ("sum_product_unmasked", lambda: price[0].scan_sum_product(price[1], disc[0], disc[1], d_sum)),
+                     ("group_sum_masked", grouped), ("unpack_quantity_and_code", unpack_qty_code),
+                     ("sum_product_masked_again", product), ("unpack_price_and_discount_again", unpack_price_disc),
+                     ("group_sum_masked_again", grouped), ("unpack_quantity_and_code_again", unpack_qty_code)):
+        fn()
+        ctx.timer_start()
+        for _ in range(reps):
+            fn()
+        ms[name] = ctx.timer_stop() / reps
+    product()  # leave the masked results behind and check them once more after the timed loops
+    grouped()
+    assert int(d_sum.download(np.uint64, price[2]).sum(dtype=np.uint64)) == want_q6, "Q6 parity (after timing)"
+    assert np.array_equal(d_gcnt.download(np.uint64, 7), want_gs), "grouped COUNT parity (after timing)"
+    prod = min(ms["sum_product_masked"], ms["sum_product_masked_again"])
+    dec = min(ms["unpack_price_and_discount"], ms["unpack_price_and_discount_again"])
+    grp = min(ms["group_sum_masked"], ms["group_sum_masked_again"])
+    dec2 = min(ms["unpack_quantity_and_code"], ms["unpack_quantity_and_code_again"])
+    two = packed_bytes["l_extendedprice"] + packed_bytes["l_discount"]
+    out = {"rows": n, "selected_rows": int(m.sum()), "q1_selected_rows": int(keep.sum()), "columns": info,
+           "packed_bytes": packed_bytes, "step_ms": ms,
+           "sum_product_masked_ms": prod, "unpack_price_and_discount_ms": dec, "sum_product_over_decode": prod / dec,
+           "group_sum_masked_ms": grp, "unpack_quantity_and_code_ms": dec2, "group_sum_over_decode": grp / dec2,
+           "sum_product_packed_read_GBps": (two + n / 8) / (prod * 1e-3) / 1e9,
+           "unpack_two_columns_total_GBps": (two + 2 * n * 4) / (dec * 1e-3) / 1e9,
+           "note": "sum_product_masked = adac_bp_scan_sum_product(l_extendedprice, l_discount) under the final bitmap of "
+                   "the three chained adac_bp_scan_select_between calls; group_sum_masked = adac_bp_scan_group_sum("
+                   "l_quantity BY code, 6 groups) under l_shipdate <= cutoff; the decodes are adac_bp_unpack of the two "
+                   "columns each call reads; every *_over_decode takes the faster of two interleaved timings of each"}
+    ctx.close()
+    return out
+
+
 def group_product_form_groups(descs_a, descs_b, descs_k, ngroups, a_type=(4, True), b_type=(4, True), k_size=1):
     """Which form of adac_scan_group_sum_product takes how many scan groups of `a` — group_product_rw_eligible
     (adac_group_product.inl) evaluated on the host descriptors, with the default grouping of ensure_scan_groups.
@@ -1230,6 +1348,7 @@ def main():
     jobs = {"plugin_scan": lambda: plugin_scan(host, lay), "adaptive": lambda: adaptive(host, wl),
             "bitpacking_scan": lambda: bitpacking_scan(adac), "q6_packed": lambda: q6_packed(adac),
             "bitpacking_fused_scans": lambda: bitpacking_fused_scans(adac),
+            "q6_bitpacking": lambda: q6_bitpacking(adac),
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "q1_filtered_packed": lambda: q1_filtered_packed(adac),
             "q1_disc_price_packed": lambda: q1_disc_price_packed(adac),

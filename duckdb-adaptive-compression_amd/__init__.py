@@ -187,6 +187,8 @@ SIGNATURES = {
     "adac_bp_scan_count_between": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "adac_bp_scan_select_between": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "adac_bp_scan_min_max": (_int, [_vp, _vp, _vp, _vp]),
+    "adac_bp_scan_sum_product": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "adac_bp_scan_group_sum": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "adac_bp_bind": (_int, [_vp, _vp]),
     "adac_bp_unpack": (_int, [_vp, _vp, _vp]),
     "adac_bp_unpack_range": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64]),
@@ -674,6 +676,19 @@ class BitpackingLayout:
         """Per segment (min, max) in the column type's order as its bit patterns; no selected row: (T.max, T.min)."""
         _check(lib().adac_bp_scan_min_max(self._h, _dptr(d_blocks), _dptr(d_validity), _dptr(d_minmax)),
                "adac_bp_scan_min_max")
+
+    def scan_sum_product(self, d_blocks, other, d_other_blocks, d_sums, d_validity=None):
+        """SUM(self * other) per segment of THIS layout (`other`: a BitpackingLayout whose metadata groups cover the
+        same rows; each value widened by its own type's signedness, mod 2^64) over the rows whose bit is set in
+        d_validity, a mask in this layout's element space."""
+        _check(lib().adac_bp_scan_sum_product(self._h, _dptr(d_blocks), other._h, _dptr(d_other_blocks),
+                                              _dptr(d_validity), _dptr(d_sums)), "adac_bp_scan_sum_product")
+
+    def scan_group_sum(self, d_blocks, keys, d_key_blocks, ngroups, d_sums, d_counts=None, d_validity=None):
+        """SUM(self) and COUNT(*) GROUP BY `keys` (a BitpackingLayout whose metadata groups cover the same rows) over
+        the rows whose bit is set in d_validity; ngroups + 1 results each, keys >= ngroups in the last."""
+        _check(lib().adac_bp_scan_group_sum(self._h, _dptr(d_blocks), keys._h, _dptr(d_key_blocks), _dptr(d_validity),
+                                            int(ngroups), _dptr(d_sums), _dptr(d_counts)), "adac_bp_scan_group_sum")
 
 
 class BitpackingPlan:

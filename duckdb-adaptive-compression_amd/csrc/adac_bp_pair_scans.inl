@@ -1,0 +1,326 @@
+// adac_bp_pair_scans.inl — fused scans over TWO columns of DuckDB BITPACKING blocks walked in step: SUM(a * b) per
+// segment (Q6's aggregate) and SUM(v), COUNT(*) GROUP BY key (Q1's basic shape), under an optional selection bitmap,
+// nothing decoded to HBM.  Included into adac_kernels.hip after adac_bp_scans.inl: the BpGroup table, the mask window
+// of a group, BpScanAcc and the staging scheme of bp_scan_packed are k_bp_scan's.
+//
+// Work shape (k_bp_scan's): a WAVE walks a run of consecutive metadata groups on its own — no barrier anywhere.  The
+// host has checked that group i of both layouts covers the same rows at the same element offset, so the wave takes
+// group i of both columns; lane l of step k owns row 64 k + l of both, and the mask bits of a step are one 64-bit
+// window in the FIRST layout's element space.
+//
+// A column is read through a cursor (BpCursor) that yields the lane's value of step k as 64 bits masked to the type's
+// width (the prefix mod 2^64 and then mod 2^bits is the prefix mod 2^bits), so one kernel serves every pair of types:
+//   linear   CONSTANT, CONSTANT_DELTA, FOR / DELTA_FOR at width 0: first + row * step, no payload byte read
+//   FOR      field + frame
+//   DELTA    the running prefix: one DPP wave scan per step, carried in a uniform register.  EVERY step of the group
+//            must pass through the cursor in order, masked or not.
+// The kind is a template parameter of the step loop (nine pairs), the width is not: a field is read branch-free as
+// three dwords.  Each cursor stages its payload through a wave-private LDS buffer of its own, in pieces of whole
+// steps when the width is above 16; which piece is resident is decided by the STEP INDEX asked for (the pieces of a
+// 21-bit and of a 40-bit column end at different steps, and steps whose mask window is zero are skipped when neither
+// column is DELTA).
+// Results: the caller zeroes them.  SUM(a * b): a wave adds what it gathered over the groups of one segment of the
+// first layout with one 64-bit atomic.  Grouped: bins live in LDS per wave — 16 / 8 / 4 / 2 / 1 copies of the
+// ngroups + 1 bins, lane & (copies - 1) picks one, so few lanes collide on an LDS add when there are few keys — and at
+// its end the wave touches every bin with one global atomic.  A group whose key column is a constant updates its bin
+// once.
+
+constexpr uint32_t kBpPairBins = 257; // 256 groups + overflow
+enum : int { kBpCurLinear = 0, kBpCurFor = 1, kBpCurDelta = 2 };
+
+struct BpPairArgs {
+	uint32_t ngroups;  // metadata groups (the same number in both layouts)
+	uint32_t per_wave; // consecutive groups one wave walks
+	const uint8_t *a_blocks, *b_blocks;
+	const uint64_t *validity; // bit e = element out_off + row of the first layout; read only by the <V> kernels
+	uint64_t a_tmask, a_sbit, b_tmask, b_sbit; // all-ones of the type's width; its sign bit, 0 for the unsigned types
+	unsigned long long *res;    // sums per segment of the first layout | sums per key
+	unsigned long long *counts; // grouped: rows per key, or nullptr
+	uint32_t nkeys;             // grouped: keys >= nkeys land in bin nkeys
+};
+
+// Every member is wave-uniform and lives in scalar registers: only what cannot be had from the width in a few
+// scalar instructions is kept (two cursors, the mask window and the bins share ~100 of them).
+struct BpCursor {
+	const uint4 *src16; // the 16-byte chunk holding the payload's first byte
+	uint4 *stage;       // kBpScanWaveChunks chunks of LDS, this wave's and this column's
+	uint64_t frame;     // linear: the first value.  FOR / DELTA: the frame of reference
+	uint64_t base;      // linear: the step.  DELTA: what the rows before the current step contribute
+	uint64_t tmask;
+	uint32_t n, w, pbit;
+	uint32_t r0, r1, bit0; // the resident piece: rows [r0, r1), row r0's bit in the staged image
+};
+
+__device__ __forceinline__ int bp_cursor_open(BpCursor &c, const BpGroup &g, const uint8_t *blocks, uint64_t tmask,
+                                              uint4 *stage) {
+	c.tmask = tmask;
+	c.n = g.rows;
+	c.stage = stage;
+	c.w = g.width;
+	c.src16 = nullptr;
+	c.pbit = c.r0 = c.r1 = c.bit0 = 0u;
+	if ((g.mode != kBpFor && g.mode != kBpDeltaFor) || g.width == 0u) {
+		// v[i] = first + i * step (k_bp_unpack's width-0 branch); step 0: CONSTANT and FOR at width 0
+		c.frame = g.frame;
+		c.base = 0ull;
+		if (g.mode == kBpConstantDelta) c.base = g.extra & tmask;
+		if (g.mode == kBpDeltaFor) {
+			c.frame = g.extra + g.frame;
+			c.base = g.frame & tmask;
+		}
+		return kBpCurLinear;
+	}
+	const uintptr_t addr = reinterpret_cast<uintptr_t>(blocks + g.payload_off);
+	c.src16 = reinterpret_cast<const uint4 *>(addr & ~uintptr_t(15));
+	c.pbit = (uint32_t)(addr & 15) * 8u;
+	c.frame = g.frame;
+	c.base = g.extra;
+	return g.mode == kBpFor ? kBpCurFor : kBpCurDelta;
+}
+
+// Make the piece that holds step k resident (bp_scan_packed's aligned, index-clamped 16-byte loads).
+__device__ __forceinline__ void bp_cursor_stage(BpCursor &c, uint32_t k /* uniform */, uint32_t lane) {
+	const uint32_t stage_rows = c.w <= 16u ? (uint32_t)kBpGroupRows : ((kBpScanStageBytes * 8u / c.w) & ~63u);
+	const uint32_t r0 = (k * 64u / stage_rows) * stage_rows;
+	const uint32_t r1 = r0 + stage_rows < c.n ? r0 + stage_rows : c.n;
+	const uint32_t bits = c.pbit + r0 * c.w;
+	const uint4 *src = c.src16 + (bits >> 7);
+	const uint32_t bit0 = bits & 127u;
+	const uint32_t nchunks = (bit0 + (r1 - r0) * c.w + 127u) >> 7; // <= kBpScanStageBytes / 16 + 1
+	uint4 q[kBpScanStageLoads];
+#pragma unroll
+	for (uint32_t i = 0; i < kBpScanStageLoads; i++) { // all requested before the first is stored
+		const uint32_t ch = lane + 64u * i;
+		q[i] = make_uint4(0u, 0u, 0u, 0u);
+		if (64u * i < nchunks) q[i] = src[ch < nchunks ? ch : nchunks - 1u]; // uniform test, index clamped
+	}
+	// LDS operations of one wave execute in order: these stores come after the reads of the piece before
+	__builtin_amdgcn_wave_barrier();
+#pragma unroll
+	for (uint32_t i = 0; i < kBpScanStageLoads; i++) {
+		const uint32_t ch = lane + 64u * i;
+		if (ch < nchunks) c.stage[ch] = q[i];
+	}
+	__builtin_amdgcn_wave_barrier();
+	c.r0 = r0;
+	c.r1 = r1;
+	c.bit0 = bit0;
+}
+
+// The lane's value of step k, masked to the type's width.  DELTA: call for every k = 0, 1, 2 ... of the group.
+template <int KIND>
+__device__ __forceinline__ uint64_t bp_cursor_value(BpCursor &c, uint32_t k /* uniform */, uint32_t lane) {
+	const uint32_t row = k * 64u + lane;
+	if (KIND == kBpCurLinear) return (c.frame + (uint64_t)row * c.base) & c.tmask;
+	if (k * 64u < c.r0 || k * 64u >= c.r1) bp_cursor_stage(c, k, lane); // never resident at first: r0 = r1 = 0
+	// rows past the group are clamped into the stage; the third dword lies inside the stage's spare chunks
+	const uint32_t bit = row < c.r1 ? c.bit0 + (row - c.r0) * c.w : c.bit0;
+	const uint32_t *lds32 = reinterpret_cast<const uint32_t *>(c.stage);
+	const uint32_t dw = bit >> 5, sh = bit & 31u;
+	const uint32_t a0 = lds32[dw], a1 = lds32[dw + 1], a2 = lds32[dw + 2];
+	const uint32_t lo = __builtin_amdgcn_alignbit(a1, a0, sh) & mask32(c.w);
+	const uint32_t hi = __builtin_amdgcn_alignbit(a2, a1, sh) & (c.w > 32u ? mask32(c.w - 32u) : 0u);
+	uint64_t f = ((uint64_t)hi << 32) | lo;
+	if (KIND == kBpCurFor) return (f + c.frame) & c.tmask;
+	// v[i] = delta_offset + (i + 1) * frame + sum_{j <= i} field[j]
+	f = row < c.n ? f : 0ull;
+	uint64_t incl;
+	// on one dword where that is exact: a type of at most 32 bits wraps there anyway, and 64 fields of at most 26 bits
+	// sum to less than 2^32
+	if (c.tmask <= 0xffffffffull || c.w <= 26u) incl = (uint64_t)wave_inclusive_sum<uint32_t>((uint32_t)f);
+	else incl = wave_inclusive_sum<uint64_t>(f);
+	const uint64_t val = c.base + (uint64_t)(lane + 1u) * c.frame + incl;
+	c.base += 64ull * c.frame + bp_readlane64(incl, 63u);
+	return val & c.tmask;
+}
+
+// lane j: which of the rows [64 j, 64 j + 64) of the group exist and are wanted (bp_scan_group's window)
+template <bool V>
+__device__ __forceinline__ uint64_t bp_pair_window(const BpGroup &g, const uint64_t *validity, uint32_t lane) {
+	const uint32_t n = g.rows;
+	const uint32_t left = 64u * lane < n ? n - 64u * lane : 0u;
+	uint64_t win = left >= 64u ? ~0ull : ((1ull << left) - 1ull);
+	if (V) {
+		const uint32_t sh = (uint32_t)(g.out_off & 63u);
+		const uint64_t word0 = g.out_off >> 6;
+		const uint32_t nwords = (uint32_t)(((g.out_off + n - 1u) >> 6) - word0) + 1u; // <= 33
+		const uint64_t vw = lane < nwords ? validity[word0 + lane] : 0ull;
+		const uint64_t nx = __shfl_down(vw, 1, 64);
+		win &= sh ? (vw >> sh) | (nx << (64u - sh)) : vw;
+	}
+	return win;
+}
+
+__device__ __forceinline__ uint64_t bp_widen(uint64_t v, uint64_t sbit) { return (v ^ sbit) - sbit; }
+
+// ---- SUM(a * b) -----------------------------------------------------------------------------------------------
+
+template <int KA, int KB>
+__device__ __forceinline__ void bp_pair_sum_steps(const BpPairArgs &s, BpCursor &ca, BpCursor &cb, uint64_t win,
+                                                  uint32_t lane, BpScanAcc<kBpScanSum> &acc) {
+	if (KA == kBpCurLinear && KB == kBpCurLinear && ca.base == 0ull && cb.base == 0ull) { // two constants
+		acc.a += bp_widen(ca.frame & ca.tmask, s.a_sbit) * bp_widen(cb.frame & cb.tmask, s.b_sbit) *
+		         (uint64_t)__popcll(win);
+		return;
+	}
+	const uint32_t steps = (ca.n + 63u) >> 6;
+	for (uint32_t k = 0; k < steps; k++) {
+		const uint64_t wk = bp_readlane64(win, k);
+		// nothing of the step is wanted: legal to pass over only when no prefix has to advance
+		if (KA != kBpCurDelta && KB != kBpCurDelta && wk == 0ull) continue;
+		const uint64_t va = bp_cursor_value<KA>(ca, k, lane);
+		const uint64_t vb = bp_cursor_value<KB>(cb, k, lane);
+		const uint64_t p = bp_widen(va, s.a_sbit) * bp_widen(vb, s.b_sbit);
+		acc.a += ((wk >> lane) & 1ull) ? p : 0ull;
+	}
+}
+
+template <int KA>
+__device__ __forceinline__ void bp_pair_sum_b(const BpPairArgs &s, int kb, BpCursor &ca, BpCursor &cb, uint64_t win,
+                                              uint32_t lane, BpScanAcc<kBpScanSum> &acc) {
+	if (kb == kBpCurLinear) bp_pair_sum_steps<KA, kBpCurLinear>(s, ca, cb, win, lane, acc);
+	else if (kb == kBpCurFor) bp_pair_sum_steps<KA, kBpCurFor>(s, ca, cb, win, lane, acc);
+	else bp_pair_sum_steps<KA, kBpCurDelta>(s, ca, cb, win, lane, acc);
+}
+
+template <bool V>
+__global__ __launch_bounds__(kWorkgroup) void k_bp_scan_pair_sum(const BpGroup *__restrict__ a_groups,
+                                                                 const BpGroup *__restrict__ b_groups,
+                                                                 const uint32_t *__restrict__ group_seg /* of a */,
+                                                                 const BpPairArgs s) {
+	constexpr uint32_t kWaves = kWorkgroup / 64;
+	__shared__ uint4 lds[kWaves * 2 * kBpScanWaveChunks];
+	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint64_t first = ((uint64_t)blockIdx.x * kWaves + wave) * s.per_wave;
+	if (first >= s.ngroups) return; // uniform per wave; no barrier follows
+	const uint32_t g0 = (uint32_t)first;
+	const uint32_t g1 = first + s.per_wave < s.ngroups ? g0 + s.per_wave : s.ngroups;
+	uint4 *stage_a = lds + wave * 2 * kBpScanWaveChunks, *stage_b = stage_a + kBpScanWaveChunks;
+	BpScanAcc<kBpScanSum> acc;
+	uint32_t seg = group_seg[g0];
+	for (uint32_t gi = g0; gi < g1; gi++) {
+		const uint32_t gs = group_seg[gi];
+		if (gs != seg) {
+			acc.flush(s.res, seg, lane);
+			seg = gs;
+		}
+		const BpGroup ga = a_groups[gi], gb = b_groups[gi];
+		BpCursor ca, cb;
+		const int ka = bp_cursor_open(ca, ga, s.a_blocks, s.a_tmask, stage_a);
+		const int kb = bp_cursor_open(cb, gb, s.b_blocks, s.b_tmask, stage_b);
+		const uint64_t win = bp_pair_window<V>(ga, s.validity, lane);
+		if (ka == kBpCurLinear) bp_pair_sum_b<kBpCurLinear>(s, kb, ca, cb, win, lane, acc);
+		else if (ka == kBpCurFor) bp_pair_sum_b<kBpCurFor>(s, kb, ca, cb, win, lane, acc);
+		else bp_pair_sum_b<kBpCurDelta>(s, kb, ca, cb, win, lane, acc);
+	}
+	acc.flush(s.res, seg, lane);
+}
+
+// ---- SUM(v), COUNT(*) GROUP BY key ----------------------------------------------------------------------------
+
+struct BpPairBins {
+	unsigned long long *sums, *counts; // this wave's: kBpPairBins words each
+	uint32_t copies;                   // power of two; bin b's copies at [b * copies, (b + 1) * copies)
+};
+
+// the key column is a constant over the group: the lanes gather, one bin update per group
+template <int KV>
+__device__ __forceinline__ void bp_pair_gsum_one_key(const BpPairArgs &s, BpCursor &cv, uint64_t key, uint64_t win,
+                                                     uint32_t lane, const BpPairBins &bins) {
+	uint64_t sum = 0ull;
+	if (KV == kBpCurLinear && cv.base == 0ull) {
+		sum = bp_widen(cv.frame & cv.tmask, s.a_sbit) * (uint64_t)__popcll(win);
+	} else {
+		const uint32_t steps = (cv.n + 63u) >> 6;
+		for (uint32_t k = 0; k < steps; k++) {
+			const uint64_t wk = bp_readlane64(win, k);
+			if (KV != kBpCurDelta && wk == 0ull) continue;
+			const uint64_t v = bp_cursor_value<KV>(cv, k, lane);
+			sum += ((wk >> lane) & 1ull) ? bp_widen(v, s.a_sbit) : 0ull;
+		}
+	}
+	sum = wave_sum(sum);
+	const uint64_t cnt = wave_sum((uint64_t)__popcll(win));
+	const uint32_t bin = key < (uint64_t)s.nkeys ? (uint32_t)key : s.nkeys;
+	if (lane == 0 && cnt != 0ull) {
+		atomicAdd(bins.sums + bin * bins.copies, (unsigned long long)sum);
+		atomicAdd(bins.counts + bin * bins.copies, (unsigned long long)cnt);
+	}
+}
+
+template <int KV, int KK>
+__device__ __forceinline__ void bp_pair_gsum_steps(const BpPairArgs &s, BpCursor &cv, BpCursor &ck, uint64_t win,
+                                                   uint32_t lane, const BpPairBins &bins) {
+	if (KK == kBpCurLinear && ck.base == 0ull) {
+		bp_pair_gsum_one_key<KV>(s, cv, ck.frame & ck.tmask, win, lane, bins);
+		return;
+	}
+	const uint32_t steps = (cv.n + 63u) >> 6;
+	const uint32_t copy = lane & (bins.copies - 1u);
+	for (uint32_t k = 0; k < steps; k++) {
+		const uint64_t wk = bp_readlane64(win, k);
+		if (KV != kBpCurDelta && KK != kBpCurDelta && wk == 0ull) continue;
+		const uint64_t v = bp_cursor_value<KV>(cv, k, lane);
+		const uint64_t key = bp_cursor_value<KK>(ck, k, lane); // unsigned, of the key type's own width
+		const uint32_t bin = key < (uint64_t)s.nkeys ? (uint32_t)key : s.nkeys;
+		if ((wk >> lane) & 1ull) {
+			atomicAdd(bins.sums + bin * bins.copies + copy, (unsigned long long)bp_widen(v, s.a_sbit));
+			atomicAdd(bins.counts + bin * bins.copies + copy, 1ull);
+		}
+	}
+}
+
+template <int KV>
+__device__ __forceinline__ void bp_pair_gsum_k(const BpPairArgs &s, int kk, BpCursor &cv, BpCursor &ck, uint64_t win,
+                                               uint32_t lane, const BpPairBins &bins) {
+	if (kk == kBpCurLinear) bp_pair_gsum_steps<KV, kBpCurLinear>(s, cv, ck, win, lane, bins);
+	else if (kk == kBpCurFor) bp_pair_gsum_steps<KV, kBpCurFor>(s, cv, ck, win, lane, bins);
+	else bp_pair_gsum_steps<KV, kBpCurDelta>(s, cv, ck, win, lane, bins);
+}
+
+template <bool V>
+__global__ __launch_bounds__(kWorkgroup) void k_bp_scan_pair_gsum(const BpGroup *__restrict__ v_groups,
+                                                                  const BpGroup *__restrict__ k_groups,
+                                                                  const BpPairArgs s) {
+	constexpr uint32_t kWaves = kWorkgroup / 64;
+	__shared__ uint4 lds[kWaves * 2 * kBpScanWaveChunks];
+	__shared__ unsigned long long lds_bins[kWaves * 2 * kBpPairBins];
+	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint64_t first = ((uint64_t)blockIdx.x * kWaves + wave) * s.per_wave;
+	if (first >= s.ngroups) return; // uniform per wave; no barrier follows
+	const uint32_t g0 = (uint32_t)first;
+	const uint32_t g1 = first + s.per_wave < s.ngroups ? g0 + s.per_wave : s.ngroups;
+	uint4 *stage_v = lds + wave * 2 * kBpScanWaveChunks, *stage_k = stage_v + kBpScanWaveChunks;
+	const uint32_t nbins = s.nkeys + 1u; // <= kBpPairBins
+	BpPairBins bins;
+	bins.sums = lds_bins + wave * 2 * kBpPairBins;
+	bins.counts = bins.sums + kBpPairBins;
+	bins.copies = nbins <= 16u ? 16u : nbins <= 32u ? 8u : nbins <= 64u ? 4u : nbins <= 128u ? 2u : 1u; // * nbins <= 257
+	for (uint32_t i = lane; i < 2 * kBpPairBins; i += 64u) bins.sums[i] = 0ull;
+	__builtin_amdgcn_wave_barrier();
+	for (uint32_t gi = g0; gi < g1; gi++) {
+		const BpGroup gv = v_groups[gi], gk = k_groups[gi];
+		BpCursor cv, ck;
+		const int kv = bp_cursor_open(cv, gv, s.a_blocks, s.a_tmask, stage_v);
+		const int kk = bp_cursor_open(ck, gk, s.b_blocks, s.b_tmask, stage_k);
+		const uint64_t win = bp_pair_window<V>(gv, s.validity, lane);
+		if (kv == kBpCurLinear) bp_pair_gsum_k<kBpCurLinear>(s, kk, cv, ck, win, lane, bins);
+		else if (kv == kBpCurFor) bp_pair_gsum_k<kBpCurFor>(s, kk, cv, ck, win, lane, bins);
+		else bp_pair_gsum_k<kBpCurDelta>(s, kk, cv, ck, win, lane, bins);
+	}
+	// the wave's LDS adds have executed before these reads (in order); one global atomic per bin
+	__builtin_amdgcn_wave_barrier();
+	for (uint32_t b = lane; b < nbins; b += 64u) {
+		uint64_t sum = 0ull, cnt = 0ull;
+		for (uint32_t c = 0; c < bins.copies; c++) {
+			sum += bins.sums[b * bins.copies + c];
+			cnt += bins.counts[b * bins.copies + c];
+		}
+		if (cnt != 0ull) {
+			atomicAdd(s.res + b, (unsigned long long)sum);
+			if (s.counts != nullptr) atomicAdd(s.counts + b, (unsigned long long)cnt);
+		}
+	}
+}

@@ -90,6 +90,8 @@ __device__ __forceinline__ void bp_scan_row(const BpScanArgs &s, uint32_t k, uin
 }
 
 // FOR / DELTA_FOR at width >= 1: the payload in stages of whole steps through the wave's LDS buffer.
+// (bp_cursor_stage in adac_bp_pair_scans.inl stages the same way — piece size, chunk count, clamped loads — for a
+// cursor per column: a change to the staging here belongs there too.)
 // SCAN32 (DELTA_FOR of a 64-bit type at w <= 26): the fields of a step sum to less than 2^32, so the wave scan runs
 // on one dword.
 template <typename U, int OP, bool V, bool WIDE, bool DELTA, bool SCAN32 = false>

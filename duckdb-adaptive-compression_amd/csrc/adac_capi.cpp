@@ -1360,6 +1360,8 @@ struct adac_bp_layout {
 	uint64_t value_span = 0; // max(out_off + count): elements an output / mask / bitmap over the layout spans
 	std::vector<uint32_t> counts;
 	std::vector<uint64_t> seg_first_group; // index of each segment's first metadata group in the group table
+	std::vector<uint64_t> group_out_off;   // of every group: what two layouts must share for a pair scan
+	std::vector<uint32_t> group_rows;
 	void *d_groups = nullptr;
 	uint32_t *d_group_seg = nullptr; // segment of every group (the fused scans' results are per segment)
 	uint64_t *d_block_offs = nullptr;
@@ -1394,6 +1396,8 @@ extern "C" adac_status adac_bp_layout_create(adac_ctx *c, int physical_type, con
 			const uint32_t rows = (uint32_t)(counts[s] - r < 2048 ? counts[s] - r : 2048);
 			groups.push_back(adac::BpGroupHost {block_offs[s], off + r, (uint32_t)(r / 2048), rows, 0, 0, 0, 0, 0});
 			group_seg.push_back((uint32_t)s);
+			l->group_out_off.push_back(off + r);
+			l->group_rows.push_back(rows);
 		}
 		run = off + counts[s];
 		if (run > l->value_span) l->value_span = run;
@@ -1560,6 +1564,62 @@ extern "C" adac_status adac_bp_scan_min_max(adac_bp_layout *l, const void *d_blo
 	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, l->type_size, l->is_signed, adac::kBpScanOpMinMax, l->d_groups,
 	                              l->d_group_seg, l->ngroups, d_blocks, d_validity, 0, 0, d_minmax, nullptr));
 	ADAC_HIP(adac::launch_bp_scan_minmax_finish(l->ctx->stream, l->type_size, l->is_signed, d_minmax, l->nseg));
+	return ADAC_OK;
+}
+
+// ---- pair scans on BITPACKING blocks (adac_bp_pair_scans.inl): two columns walked in step ----
+
+// The checks both pair scans share, all on the host, before anything is enqueued.  Group i of both layouts must
+// cover the same rows at the same element offset; where the segments end plays no part.
+static adac_status bp_pair_begin(adac_bp_layout *a, const void *d_a_blocks, adac_bp_layout *b, const void *d_b_blocks) {
+	if (!a || !b || a->ctx != b->ctx) return ADAC_ERR_INVALID_ARGUMENT;
+	// a blocks pointer is looked at only while its layout has rows
+	if (a->total_values && (!d_a_blocks || !aligned16(d_a_blocks))) return ADAC_ERR_INVALID_ARGUMENT;
+	if (b->total_values && (!d_b_blocks || !aligned16(d_b_blocks))) return ADAC_ERR_INVALID_ARGUMENT;
+	// one layout object is bound to one buffer at a time
+	if (a == b && d_a_blocks != d_b_blocks) return ADAC_ERR_INVALID_ARGUMENT;
+	if (a != b && (a->group_out_off != b->group_out_off || a->group_rows != b->group_rows)) {
+		return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	return ADAC_OK;
+}
+
+static adac_status bp_pair_bind(adac_bp_layout *a, const void *d_a_blocks, adac_bp_layout *b, const void *d_b_blocks) {
+	adac_status st = bp_scan_bind(a, d_a_blocks);
+	if (st == ADAC_OK && b != a) st = bp_scan_bind(b, d_b_blocks);
+	return st;
+}
+
+extern "C" adac_status adac_bp_scan_sum_product(adac_bp_layout *a, const void *d_a_blocks, adac_bp_layout *b,
+                                                const void *d_b_blocks, const uint64_t *d_validity, uint64_t *d_sums) {
+	adac_status st = bp_pair_begin(a, d_a_blocks, b, d_b_blocks);
+	if (st != ADAC_OK) return st;
+	if (a->nseg && !d_sums) return ADAC_ERR_INVALID_ARGUMENT;
+	if (a->nseg == 0) return ADAC_OK;
+	ADAC_HIP(hipSetDevice(a->ctx->device));
+	if ((st = bp_pair_bind(a, d_a_blocks, b, d_b_blocks)) != ADAC_OK) return st;
+	// every wave adds its part: the sums start from zero (this also writes the segments without rows)
+	ADAC_HIP(hipMemsetAsync(d_sums, 0, a->nseg * sizeof(uint64_t), a->ctx->stream));
+	const adac::BpPairColumn ca {a->d_groups, d_a_blocks, a->type_size, a->is_signed};
+	const adac::BpPairColumn cb {b->d_groups, d_b_blocks, b->type_size, b->is_signed};
+	ADAC_HIP(adac::launch_bp_scan_pair_sum(a->ctx->stream, ca, cb, a->d_group_seg, a->ngroups, d_validity, d_sums));
+	return ADAC_OK;
+}
+
+extern "C" adac_status adac_bp_scan_group_sum(adac_bp_layout *values, const void *d_value_blocks, adac_bp_layout *keys,
+                                              const void *d_key_blocks, const uint64_t *d_validity, uint32_t ngroups,
+                                              uint64_t *d_sums, uint64_t *d_counts) {
+	adac_status st = bp_pair_begin(values, d_value_blocks, keys, d_key_blocks);
+	if (st != ADAC_OK) return st;
+	if (!d_sums || ngroups == 0 || ngroups > 256) return ADAC_ERR_INVALID_ARGUMENT;
+	ADAC_HIP(hipSetDevice(values->ctx->device));
+	if ((st = bp_pair_bind(values, d_value_blocks, keys, d_key_blocks)) != ADAC_OK) return st;
+	ADAC_HIP(hipMemsetAsync(d_sums, 0, (ngroups + 1ull) * sizeof(uint64_t), values->ctx->stream));
+	if (d_counts) ADAC_HIP(hipMemsetAsync(d_counts, 0, (ngroups + 1ull) * sizeof(uint64_t), values->ctx->stream));
+	const adac::BpPairColumn cv {values->d_groups, d_value_blocks, values->type_size, values->is_signed};
+	const adac::BpPairColumn ck {keys->d_groups, d_key_blocks, keys->type_size, keys->is_signed};
+	ADAC_HIP(adac::launch_bp_scan_pair_gsum(values->ctx->stream, cv, ck, values->ngroups, d_validity, ngroups, d_sums,
+	                                        d_counts));
 	return ADAC_OK;
 }
 

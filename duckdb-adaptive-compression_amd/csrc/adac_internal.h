@@ -291,5 +291,17 @@ hipError_t launch_bp_scan(hipStream_t s, uint32_t type_size, bool is_signed, int
                           const uint64_t *d_validity, uint64_t blo, uint64_t bspan, uint64_t *d_res, uint64_t *d_bitmap);
 hipError_t launch_bp_scan_minmax_finish(hipStream_t s, uint32_t type_size, bool is_signed, uint64_t *d_minmax,
                                         uint64_t nseg);
+// pair scans on the block images of two layouts whose group tables agree (adac_bp_pair_scans.inl).  The caller has
+// zeroed the results.  a's group_seg: SUM(a * b) is per segment of a
+struct BpPairColumn {
+	const void *d_groups, *d_blocks;
+	uint32_t type_size;
+	bool is_signed;
+};
+hipError_t launch_bp_scan_pair_sum(hipStream_t s, const BpPairColumn &a, const BpPairColumn &b,
+                                   const uint32_t *d_group_seg, uint64_t ngroups, const uint64_t *d_validity,
+                                   uint64_t *d_sums);
+hipError_t launch_bp_scan_pair_gsum(hipStream_t s, const BpPairColumn &v, const BpPairColumn &k, uint64_t ngroups,
+                                    const uint64_t *d_validity, uint32_t nkeys, uint64_t *d_sums, uint64_t *d_counts);
 
 } // namespace adac

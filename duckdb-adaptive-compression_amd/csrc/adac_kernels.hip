@@ -1947,6 +1947,7 @@ hipError_t dispatch_size(uint32_t type_size, F &&f) {
 
 #include "adac_bitpacking.inl"
 #include "adac_bp_scans.inl"
+#include "adac_bp_pair_scans.inl"
 #include "adac_select_gather.inl"
 #include "adac_block_image.inl"
 #include "adac_encode_1p.inl"
@@ -2626,6 +2627,56 @@ hipError_t launch_bp_scan_minmax_finish(hipStream_t s, uint32_t type_size, bool 
 	if (nseg == 0) return hipSuccess;
 	hipLaunchKernelGGL(k_bp_scan_minmax_finish, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, s, d_minmax, nseg,
 	                   type_mask(type_size), type_sign_bit(type_size, is_signed));
+	return hipGetLastError();
+}
+
+// Pair scans on BITPACKING blocks (adac_bp_pair_scans.inl): launch_bp_scan's shape.  Two stage buffers per wave (and
+// the grouped kernel's bins) leave room for `resident` workgroups per CU.
+static BpPairArgs bp_pair_args(const BpPairColumn &a, const BpPairColumn &b, uint64_t ngroups, uint64_t resident,
+                               const uint64_t *d_validity, uint64_t *d_res, dim3 &grid) {
+	constexpr uint64_t kWaves = kWorkgroup / 64;
+	const uint64_t cap = device_cus() * resident * kWaves;
+	BpPairArgs s;
+	s.ngroups = (uint32_t)ngroups;
+	s.per_wave = (uint32_t)((ngroups + cap - 1) / cap);
+	s.a_blocks = static_cast<const uint8_t *>(a.d_blocks);
+	s.b_blocks = static_cast<const uint8_t *>(b.d_blocks);
+	s.validity = d_validity;
+	s.a_tmask = type_mask(a.type_size);
+	s.a_sbit = type_sign_bit(a.type_size, a.is_signed);
+	s.b_tmask = type_mask(b.type_size);
+	s.b_sbit = type_sign_bit(b.type_size, b.is_signed);
+	s.res = reinterpret_cast<unsigned long long *>(d_res);
+	s.counts = nullptr;
+	s.nkeys = 0;
+	const uint64_t nwaves = (ngroups + s.per_wave - 1) / s.per_wave;
+	grid = dim3((unsigned)((nwaves + kWaves - 1) / kWaves));
+	return s;
+}
+
+hipError_t launch_bp_scan_pair_sum(hipStream_t st, const BpPairColumn &a, const BpPairColumn &b,
+                                   const uint32_t *d_group_seg, uint64_t ngroups, const uint64_t *d_validity,
+                                   uint64_t *d_sums) {
+	if (ngroups == 0) return hipSuccess;
+	dim3 grid;
+	const BpPairArgs s = bp_pair_args(a, b, ngroups, 4, d_validity, d_sums, grid);
+	const BpGroup *ga = static_cast<const BpGroup *>(a.d_groups), *gb = static_cast<const BpGroup *>(b.d_groups);
+	if (d_validity) hipLaunchKernelGGL(k_bp_scan_pair_sum<true>, grid, dim3(kWorkgroup), 0, st, ga, gb, d_group_seg, s);
+	else hipLaunchKernelGGL(k_bp_scan_pair_sum<false>, grid, dim3(kWorkgroup), 0, st, ga, gb, d_group_seg, s);
+	return hipGetLastError();
+}
+
+hipError_t launch_bp_scan_pair_gsum(hipStream_t st, const BpPairColumn &v, const BpPairColumn &k, uint64_t ngroups,
+                                    const uint64_t *d_validity, uint32_t nkeys, uint64_t *d_sums, uint64_t *d_counts) {
+	if (ngroups == 0) return hipSuccess;
+	static_assert(kBpPairBins == 257, "adac_bp_scan_group_sum admits 256 keys + the overflow entry");
+	dim3 grid;
+	BpPairArgs s = bp_pair_args(v, k, ngroups, 3, d_validity, d_sums, grid);
+	s.counts = reinterpret_cast<unsigned long long *>(d_counts);
+	s.nkeys = nkeys;
+	const BpGroup *gv = static_cast<const BpGroup *>(v.d_groups), *gk = static_cast<const BpGroup *>(k.d_groups);
+	if (d_validity) hipLaunchKernelGGL(k_bp_scan_pair_gsum<true>, grid, dim3(kWorkgroup), 0, st, gv, gk, s);
+	else hipLaunchKernelGGL(k_bp_scan_pair_gsum<false>, grid, dim3(kWorkgroup), 0, st, gv, gk, s);
 	return hipGetLastError();
 }
 

@@ -583,6 +583,31 @@ adac_status adac_bp_scan_select_between(adac_bp_layout *l, const void *d_blocks,
 adac_status adac_bp_scan_min_max(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_validity,
                                  uint64_t *d_minmax);
 
+/* Pair scans: two BITPACKING columns of the same table walked in step, nothing decoded to HBM.  Both layouts must
+ * live on one context and their metadata group tables must agree: the same number of groups, and group i of each
+ * with the same element offset and the same row count — else ADAC_ERR_INVALID_ARGUMENT, as for a NULL layout, NULL
+ * results, or a blocks pointer that is NULL or not 16-byte aligned while its layout has rows; all checked on the host
+ * before anything is enqueued.  Where the SEGMENTS end may differ (a wide column fills its block after 16 groups, a
+ * narrow one after 250).  d_validity is indexed in the FIRST layout's element space, out_offs[seg] + row; NULL:
+ * every row; no mask word outside that layout's ceil(value_span / 64) words is read.  Both calls enqueue on the
+ * context's stream, do not synchronise and bind each layout like adac_bp_unpack when handed a buffer it is not bound
+ * to (one layout object passed twice must come with one buffer).  The results are fully written by the call, nothing
+ * is pre-cleared by the caller, and equal the same aggregate over what adac_bp_unpack returns for the two buffers. */
+/* d_sums[seg], over a's segments (a's nseg words, written for segments without rows too) = sum of widen(a) * widen(b)
+ * mod 2^64 over the selected rows, each factor widened by its own type's signedness (adac_scan_sum_product's rule).
+ * b's segmentation and out_offs play no part beyond the group check; a == b gives the sum of squares. */
+adac_status adac_bp_scan_sum_product(adac_bp_layout *a, const void *d_a_blocks, adac_bp_layout *b, const void *d_b_blocks,
+                                     const uint64_t *d_validity, uint64_t *d_sums);
+/* SUM(value), COUNT(*) GROUP BY key with adac_scan_group_sum_valid's semantics: key = the key column's value as an
+ * unsigned number of its own width (a negative key of a signed type is a large one); rows whose key >= ngroups go
+ * to entry [ngroups]; 1 <= ngroups <= 256.  d_sums and d_counts (may be NULL) hold ngroups + 1 words over the whole
+ * column, not per segment.  A row whose bit is clear in d_validity (the values layout's element space) contributes
+ * to no entry, the overflow entry included.  A group whose key column is CONSTANT (a table sorted by the key)
+ * updates its entry once, not once per row. */
+adac_status adac_bp_scan_group_sum(adac_bp_layout *values, const void *d_value_blocks, adac_bp_layout *keys,
+                                   const void *d_key_blocks, const uint64_t *d_validity, uint32_t ngroups,
+                                   uint64_t *d_sums, uint64_t *d_counts);
+
 /* Compress side (BitpackingCompress / BitpackingFinalizeCompress, bitpacking.cpp:514-538): per-group statistics
  * on the device, the mode decision of BitpackingState::Flush (:229-294) and the sequential placement of groups
  * into Storage::BLOCK_SIZE blocks (:453-512) on the host, then one device pass writing every group image.
