@@ -1117,22 +1117,45 @@ extern "C" adac_status adac_scan_group_sum(adac_layout *values, const uint64_t *
 	return adac_scan_group_sum_valid(values, d_value_words, keys, d_key_words, nullptr, ngroups, d_sums, d_counts);
 }
 
+// What the grouped scans share.  cols: the call's layouts with their packed words, `a` / the value layout first; required:
+// the output pointers the call cannot do without.  Checks the arguments (all layouts of one context and over the same
+// rows, segment by segment; 1 <= ngroups <= the bins the kernels hold; words wherever there are values, 16-byte
+// aligned), selects the device and makes sure `a` has its partial buffer (with the hand-over slots and the call counter
+// shared by all grouped entry points, cleared once) and its scan groups, the register-walk kernel's work items.
+struct GroupColumn {
+	adac_layout *l;
+	const uint64_t *d_words;
+};
+template <size_t N, size_t M>
+static adac_status group_scan_setup(const GroupColumn (&cols)[N], uint32_t ngroups, const void *const (&required)[M]) {
+	for (const GroupColumn &c : cols) {
+		if (!c.l) return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	for (const void *out : required) {
+		if (!out) return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	adac_layout *a = cols[0].l;
+	if (ngroups == 0 || ngroups > adac::group_sum_max_groups()) return ADAC_ERR_INVALID_ARGUMENT;
+	for (const GroupColumn &c : cols) {
+		if (c.l->ctx != a->ctx || c.l->counts != a->counts) return ADAC_ERR_INVALID_ARGUMENT;
+		if ((a->total_values && !c.d_words) || !aligned16(c.d_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	ADAC_HIP(hipSetDevice(a->ctx->device));
+	if (!a->d_group_partial) {
+		ADAC_HIP(hipMalloc(&a->d_group_partial, adac::group_sum_partial_bytes()));
+		ADAC_HIP(hipMemsetAsync(a->d_group_partial, 0, adac::group_sum_partial_bytes(), a->ctx->stream));
+	}
+	return ensure_scan_groups(a);
+}
+
 // ... restricted to the rows whose bit is set in d_validity (the value layout's element space; NULL = every row)
 extern "C" adac_status adac_scan_group_sum_valid(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
                                                  const uint64_t *d_key_words, const uint64_t *d_validity, uint32_t ngroups,
                                                  uint64_t *d_sums, uint64_t *d_counts) {
-	if (!values || !keys || values->ctx != keys->ctx || !d_sums || !d_counts) return ADAC_ERR_INVALID_ARGUMENT;
-	if (ngroups == 0 || ngroups > adac::group_sum_max_groups()) return ADAC_ERR_INVALID_ARGUMENT;
-	if (values->counts != keys->counts) return ADAC_ERR_INVALID_ARGUMENT; // the same rows, segment by segment
-	if (values->total_values && (!d_value_words || !d_key_words)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (!aligned16(d_value_words) || !aligned16(d_key_words)) return ADAC_ERR_INVALID_ARGUMENT;
-	ADAC_HIP(hipSetDevice(values->ctx->device));
-	if (!values->d_group_partial) {
-		ADAC_HIP(hipMalloc(&values->d_group_partial, adac::group_sum_partial_bytes()));
-		ADAC_HIP(hipMemsetAsync(values->d_group_partial, 0, adac::group_sum_partial_bytes(), values->ctx->stream));
-	}
-	adac_status gst = ensure_scan_groups(values); // the register-walk kernel's work items
-	if (gst != ADAC_OK) return gst;
+	const GroupColumn cols[] = {{values, d_value_words}, {keys, d_key_words}};
+	const void *const required[] = {d_sums, d_counts};
+	adac_status st = group_scan_setup(cols, ngroups, required);
+	if (st != ADAC_OK) return st;
 	ADAC_HIP(adac::launch_group_sum(values->ctx->stream, values->type_size, values->is_signed, keys->type_size,
 	                                values->d_descs, values->d_tiles, values->ntiles, values->d_groups, values->ngroups,
 	                                d_value_words, keys->d_descs, d_key_words, ngroups, values->d_group_partial,
@@ -1140,24 +1163,16 @@ extern "C" adac_status adac_scan_group_sum_valid(adac_layout *values, const uint
 	return ADAC_OK;
 }
 
-// SUM(a * b) GROUP BY key under a selection bitmap over three packed columns of one table (Q1's sum_disc_price)
+// SUM(a * b) GROUP BY key under a selection bitmap over three packed columns of one table (Q1's sum_disc_price);
+// d_counts may be null
 extern "C" adac_status adac_scan_group_sum_product(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
                                                    const uint64_t *d_b_words, adac_layout *keys,
                                                    const uint64_t *d_key_words, const uint64_t *d_validity,
                                                    uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts) {
-	if (!a || !b || !keys || a->ctx != b->ctx || a->ctx != keys->ctx || !d_sums) return ADAC_ERR_INVALID_ARGUMENT;
-	if (ngroups == 0 || ngroups > adac::group_sum_max_groups()) return ADAC_ERR_INVALID_ARGUMENT;
-	if (a->counts != b->counts || a->counts != keys->counts) return ADAC_ERR_INVALID_ARGUMENT; // the same rows, segment by segment
-	if (a->total_values && (!d_a_words || !d_b_words || !d_key_words)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (!aligned16(d_a_words) || !aligned16(d_b_words) || !aligned16(d_key_words)) return ADAC_ERR_INVALID_ARGUMENT;
-	ADAC_HIP(hipSetDevice(a->ctx->device));
-	// the partial buffer, the call counter and the hand-over slots are a's, shared with adac_scan_group_sum_valid
-	if (!a->d_group_partial) {
-		ADAC_HIP(hipMalloc(&a->d_group_partial, adac::group_sum_partial_bytes()));
-		ADAC_HIP(hipMemsetAsync(a->d_group_partial, 0, adac::group_sum_partial_bytes(), a->ctx->stream));
-	}
-	adac_status gst = ensure_scan_groups(a); // the register-walk kernel's work items
-	if (gst != ADAC_OK) return gst;
+	const GroupColumn cols[] = {{a, d_a_words}, {b, d_b_words}, {keys, d_key_words}};
+	const void *const required[] = {d_sums};
+	adac_status st = group_scan_setup(cols, ngroups, required);
+	if (st != ADAC_OK) return st;
 	ADAC_HIP(adac::launch_group_product(a->ctx->stream, a->type_size, a->is_signed, b->type_size, b->is_signed,
 	                                    keys->type_size, a->d_descs, a->d_tiles, a->ntiles, a->d_groups, a->ngroups,
 	                                    d_a_words, b->d_descs, d_b_words, keys->d_descs, d_key_words, ngroups,
@@ -1166,30 +1181,16 @@ extern "C" adac_status adac_scan_group_sum_product(adac_layout *a, const uint64_
 }
 
 // SUM(a * b * c) GROUP BY key under a selection bitmap over four packed columns of one table (Q1's sum_charge needs
-// SUM(price * disc * tax))
+// SUM(price * disc * tax)); d_counts may be null
 extern "C" adac_status adac_scan_group_sum_product3(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
                                                     const uint64_t *d_b_words, adac_layout *c, const uint64_t *d_c_words,
                                                     adac_layout *keys, const uint64_t *d_key_words,
                                                     const uint64_t *d_validity, uint32_t ngroups, uint64_t *d_sums,
                                                     uint64_t *d_counts) {
-	if (!a || !b || !c || !keys || a->ctx != b->ctx || a->ctx != c->ctx || a->ctx != keys->ctx || !d_sums) {
-		return ADAC_ERR_INVALID_ARGUMENT;
-	}
-	if (ngroups == 0 || ngroups > adac::group_sum_max_groups()) return ADAC_ERR_INVALID_ARGUMENT;
-	// the same rows, segment by segment
-	if (a->counts != b->counts || a->counts != c->counts || a->counts != keys->counts) return ADAC_ERR_INVALID_ARGUMENT;
-	if (a->total_values && (!d_a_words || !d_b_words || !d_c_words || !d_key_words)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (!aligned16(d_a_words) || !aligned16(d_b_words) || !aligned16(d_c_words) || !aligned16(d_key_words)) {
-		return ADAC_ERR_INVALID_ARGUMENT;
-	}
-	ADAC_HIP(hipSetDevice(a->ctx->device));
-	// the partial buffer, the call counter and the hand-over slots are a's, shared with the other grouped scans
-	if (!a->d_group_partial) {
-		ADAC_HIP(hipMalloc(&a->d_group_partial, adac::group_sum_partial_bytes()));
-		ADAC_HIP(hipMemsetAsync(a->d_group_partial, 0, adac::group_sum_partial_bytes(), a->ctx->stream));
-	}
-	adac_status gst = ensure_scan_groups(a); // the register-walk kernel's work items
-	if (gst != ADAC_OK) return gst;
+	const GroupColumn cols[] = {{a, d_a_words}, {b, d_b_words}, {c, d_c_words}, {keys, d_key_words}};
+	const void *const required[] = {d_sums};
+	adac_status st = group_scan_setup(cols, ngroups, required);
+	if (st != ADAC_OK) return st;
 	ADAC_HIP(adac::launch_group_product3(a->ctx->stream, a->type_size, a->is_signed, b->type_size, b->is_signed,
 	                                     c->type_size, c->is_signed, keys->type_size, a->d_descs, a->d_tiles, a->ntiles,
 	                                     a->d_groups, a->ngroups, d_a_words, b->d_descs, d_b_words, c->d_descs, d_c_words,
@@ -1205,28 +1206,10 @@ extern "C" adac_status adac_scan_group_sum_q1(adac_layout *a, const uint64_t *d_
                                               adac_layout *q, const uint64_t *d_q_words, adac_layout *keys,
                                               const uint64_t *d_key_words, const uint64_t *d_validity, uint32_t ngroups,
                                               uint64_t *d_out) {
-	if (!a || !b || !c || !q || !keys || !d_out) return ADAC_ERR_INVALID_ARGUMENT;
-	if (a->ctx != b->ctx || a->ctx != c->ctx || a->ctx != q->ctx || a->ctx != keys->ctx) return ADAC_ERR_INVALID_ARGUMENT;
-	if (ngroups == 0 || ngroups > adac::group_sum_max_groups()) return ADAC_ERR_INVALID_ARGUMENT;
-	// the same rows, segment by segment
-	if (a->counts != b->counts || a->counts != c->counts || a->counts != q->counts || a->counts != keys->counts) {
-		return ADAC_ERR_INVALID_ARGUMENT;
-	}
-	if (a->total_values && (!d_a_words || !d_b_words || !d_c_words || !d_q_words || !d_key_words)) {
-		return ADAC_ERR_INVALID_ARGUMENT;
-	}
-	if (!aligned16(d_a_words) || !aligned16(d_b_words) || !aligned16(d_c_words) || !aligned16(d_q_words) ||
-	    !aligned16(d_key_words)) {
-		return ADAC_ERR_INVALID_ARGUMENT;
-	}
-	ADAC_HIP(hipSetDevice(a->ctx->device));
-	// the partial buffer, the call counter and the hand-over slots are a's, shared with the other grouped scans
-	if (!a->d_group_partial) {
-		ADAC_HIP(hipMalloc(&a->d_group_partial, adac::group_sum_partial_bytes()));
-		ADAC_HIP(hipMemsetAsync(a->d_group_partial, 0, adac::group_sum_partial_bytes(), a->ctx->stream));
-	}
-	adac_status gst = ensure_scan_groups(a); // the register-walk kernel's work items
-	if (gst != ADAC_OK) return gst;
+	const GroupColumn cols[] = {{a, d_a_words}, {b, d_b_words}, {c, d_c_words}, {q, d_q_words}, {keys, d_key_words}};
+	const void *const required[] = {d_out};
+	adac_status st = group_scan_setup(cols, ngroups, required);
+	if (st != ADAC_OK) return st;
 	const uint32_t type_size[5] = {a->type_size, b->type_size, c->type_size, q->type_size, keys->type_size};
 	const bool is_signed[5] = {a->is_signed, b->is_signed, c->is_signed, q->is_signed, keys->is_signed};
 	ADAC_HIP(adac::launch_group_q1(a->ctx->stream, type_size, is_signed, a->d_descs, a->d_tiles, a->ntiles, a->d_groups,

@@ -2047,6 +2047,75 @@ uint64_t group_sum_partial_bytes() { return ((uint64_t)kGroupMaxWorkgroups * 2u 
 uint32_t group_sum_max_groups() { return kGroupMaxBins - 1u; }
 uint64_t group_sum_handover_word(uint32_t call_parity) { return (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + (call_parity & 1u); }
 
+namespace {
+
+// The steps every grouped scan takes on the `a` layout's partial buffer and hand-over slots (d_partial, call_parity:
+// shared between the grouped entry points, each call uses slot (calls & 1) and clears the other one for the call after it):
+//   1. the register-walk kernel over a's scan groups, when there are at most kGroupPrivateBins bins, its knob is on and
+//      there is a scan group; persistent, rw_resident workgroups per CU; it counts the scan groups it cannot take in
+//      the hand-over word;
+//   2. the staged-LDS kernel over a's tiles: everything when the first kernel did not run, else what it left (its
+//      workgroups leave at once when that is nothing).  Persistent: staged_resident workgroups per CU, as many as are
+//      resident at once, so nobody runs a second round on a part of the chip;
+//   3. the final kernel: one workgroup per bin adds the partial rows of both (row_words words per workgroup).
+// `cap`: the most workgroups either kernel may have (its half of the partial buffer).  The launch_* callables launch
+// the call's own kernels with the grids and pointers computed here.
+template <class Rw, class Staged, class Final>
+hipError_t launch_group_scan(uint32_t nbins, bool rw_knob, uint64_t nagroups, uint64_t ntiles, uint32_t rw_resident,
+                             uint32_t staged_resident, uint64_t cap, uint32_t row_words, void *d_partial,
+                             uint32_t call_parity, Rw launch_rw, Staged launch_staged, Final launch_final) {
+	unsigned long long *partial = static_cast<unsigned long long *>(d_partial);
+	unsigned long long *fallback = partial + group_sum_handover_word(call_parity);
+	unsigned long long *next_fallback = partial + group_sum_handover_word(call_parity + 1u);
+	auto grid = [&](uint64_t items, uint32_t resident) {
+		uint64_t most = (uint64_t)resident * device_cus();
+		most = most < cap ? most : cap;
+		return (uint32_t)(items < most ? items : most);
+	};
+	uint32_t nwg_rw = 0;
+	const bool rw = nbins <= kGroupPrivateBins && rw_knob && nagroups > 0;
+	if (rw) {
+		nwg_rw = grid(nagroups, rw_resident);
+		launch_rw(nwg_rw, partial, fallback);
+		hipError_t e = hipGetLastError();
+		if (e != hipSuccess) return e;
+	}
+	const uint32_t nwg = grid(ntiles, staged_resident);
+	if (nwg) {
+		launch_staged(nwg, partial + (uint64_t)nwg_rw * row_words, rw ? fallback : static_cast<const unsigned long long *>(nullptr));
+		hipError_t e = hipGetLastError();
+		if (e != hipSuccess) return e;
+	}
+	launch_final(partial, nwg_rw, nwg, static_cast<const unsigned long long *>(fallback), next_fallback, rw ? 1 : 0);
+	return hipGetLastError();
+}
+
+// the type words the grouped kernels take: all-ones mask of the type's width and its sign bit per column
+GroupProductTypes group_product_types(uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
+                                      uint32_t k_type_size) {
+	GroupProductTypes ty;
+	ty.p.a_tmask = type_mask(a_type_size);
+	ty.p.a_sbit = type_sign_bit(a_type_size, a_signed);
+	ty.p.b_tmask = type_mask(b_type_size);
+	ty.p.b_sbit = type_sign_bit(b_type_size, b_signed);
+	ty.k_tmask = type_mask(k_type_size);
+	ty.a_tile_rows = tile_values(a_type_size);
+	return ty;
+}
+
+// step 3 of the scans that end in {sum, count} pairs per bin: k_group_final (d_counts may be null)
+auto group_pairs_final(hipStream_t s, uint32_t nbins, uint64_t *d_sums, uint64_t *d_counts) {
+	return [=](const unsigned long long *partial, uint32_t nwg_rw, uint32_t nwg, const unsigned long long *fallback,
+	           unsigned long long *next_fallback, int rw_ran) {
+		hipLaunchKernelGGL(k_group_final, dim3(nbins), dim3(kWorkgroup), 0, s, partial, nwg_rw, nwg, nbins, d_sums, d_counts,
+		                   fallback, next_fallback, rw_ran);
+	};
+}
+
+} // namespace
+
+// SUM(value), COUNT(*) GROUP BY key, optionally under a selection bitmap (adac_group_sum.inl).  The register walk is
+// resident with seven workgroups per CU, six under a mask; the staged kernel with seven (21 KiB of LDS each).
 hipError_t launch_group_sum(hipStream_t s, uint32_t v_type_size, bool v_signed, uint32_t k_type_size,
                             const adac_segment_desc *d_vdescs, const TileRef *d_vtiles, uint64_t ntiles,
                             const ScanGroup *d_vgroups, uint64_t nvgroups, const uint64_t *d_vwords,
@@ -2059,54 +2128,28 @@ hipError_t launch_group_sum(hipStream_t s, uint32_t v_type_size, bool v_signed, 
 	ty.v_tile_rows = tile_values(v_type_size);
 	ty.wide_only = g_tuning.group_sum_wide ? 1u : 0u;
 	const uint32_t nbins = ngroups + 1u;
-	unsigned long long *partial = static_cast<unsigned long long *>(d_partial);
-	unsigned long long *fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + (call_parity & 1u);
-	unsigned long long *next_fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + ((call_parity + 1u) & 1u);
-	// 1. the register-walk kernel over the value layout's scan groups (up to 8 bins; persistent, as many workgroups per
-	//    CU as its form is resident with: seven, six under a mask); it counts the segment pairs it cannot take in *fallback
-	uint32_t nwg_rw = 0;
-	const bool rw = nbins <= kGroupPrivateBins && !ty.wide_only && g_tuning.group_sum_rw && nvgroups > 0;
-	if (rw) {
-		const uint64_t cap = (uint64_t)(d_validity ? kGroupRwResident<true> : kGroupRwResident<false>) * device_cus();
-		nwg_rw = (uint32_t)(nvgroups < cap ? nvgroups : cap);
-		nwg_rw = nwg_rw < kGroupMaxWorkgroups / 2 ? nwg_rw : kGroupMaxWorkgroups / 2;
-		if (d_validity) {
-			hipLaunchKernelGGL(k_group_sum_rw<true>, dim3(nwg_rw), dim3(kWorkgroup), 0, s, d_vgroups, (uint32_t)nvgroups,
-			                   d_vwords, d_kdescs, d_kwords, ty, ngroups, partial, fallback, d_validity);
-		} else {
-			hipLaunchKernelGGL(k_group_sum_rw<false>, dim3(nwg_rw), dim3(kWorkgroup), 0, s, d_vgroups, (uint32_t)nvgroups,
-			                   d_vwords, d_kdescs, d_kwords, ty, ngroups, partial, fallback, d_validity);
-		}
-		hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	// 2. the staged-LDS kernel over the tiles: everything when the first kernel did not run, else what it left (its
-	//    workgroups leave at once when that is nothing).  Persistent: as many workgroups as are resident at once (seven
-	//    per CU: 21 KiB of LDS each), so nobody runs a second round on a third of the chip
-	uint64_t cap = 7ull * device_cus();
-	cap = cap < kGroupMaxWorkgroups / 2 ? cap : kGroupMaxWorkgroups / 2;
-	const uint32_t nwg = (uint32_t)(ntiles < cap ? ntiles : cap);
-	if (nwg) {
-		const unsigned long long *handed = rw ? fallback : static_cast<const unsigned long long *>(nullptr);
-		if (d_validity) {
-			hipLaunchKernelGGL(k_group_sum<true>, dim3(nwg), dim3(kWorkgroup), 0, s, d_vdescs, d_vtiles, (uint32_t)ntiles,
-			                   d_vwords, d_kdescs, d_kwords, ty, ngroups, partial + (uint64_t)nwg_rw * 2u * nbins, handed,
-			                   d_validity);
-		} else {
-			hipLaunchKernelGGL(k_group_sum<false>, dim3(nwg), dim3(kWorkgroup), 0, s, d_vdescs, d_vtiles, (uint32_t)ntiles,
-			                   d_vwords, d_kdescs, d_kwords, ty, ngroups, partial + (uint64_t)nwg_rw * 2u * nbins, handed,
-			                   d_validity);
-		}
-		hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	hipLaunchKernelGGL(k_group_final, dim3(nbins), dim3(kWorkgroup), 0, s, partial, nwg_rw, nwg, nbins, d_sums, d_counts,
-	                   static_cast<const unsigned long long *>(fallback), next_fallback, rw ? 1 : 0);
-	return hipGetLastError();
+	return launch_group_scan(
+	    nbins, !ty.wide_only && g_tuning.group_sum_rw, nvgroups, ntiles,
+	    d_validity ? kGroupRwResident<true> : kGroupRwResident<false>, 7u, kGroupMaxWorkgroups / 2, 2u * nbins, d_partial,
+	    call_parity,
+	    [&](uint32_t nwg, unsigned long long *partial, unsigned long long *fallback) {
+		    auto launch = [&](auto kernel) {
+			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_vgroups, (uint32_t)nvgroups, d_vwords, d_kdescs,
+			                       d_kwords, ty, ngroups, partial, fallback, d_validity);
+		    };
+		    if (d_validity) launch(k_group_sum_rw<true>); else launch(k_group_sum_rw<false>);
+	    },
+	    [&](uint32_t nwg, unsigned long long *partial, const unsigned long long *handed) {
+		    auto launch = [&](auto kernel) {
+			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_vdescs, d_vtiles, (uint32_t)ntiles, d_vwords,
+			                       d_kdescs, d_kwords, ty, ngroups, partial, handed, d_validity);
+		    };
+		    if (d_validity) launch(k_group_sum<true>); else launch(k_group_sum<false>);
+	    },
+	    group_pairs_final(s, nbins, d_sums, d_counts));
 }
 
-// SUM(a * b) GROUP BY key under a selection bitmap (adac_group_product.inl).  launch_group_sum's three steps on the
-// same partial buffer and hand-over slots (d_partial, call_parity: the `a` layout's, shared between the two entry points)
+// SUM(a * b) GROUP BY key under a selection bitmap (adac_group_product.inl).  Without d_counts the walk keeps no row counts.
 hipError_t launch_group_product(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
                                 uint32_t k_type_size, const adac_segment_desc *d_adescs, const TileRef *d_atiles,
                                 uint64_t ntiles, const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
@@ -2114,64 +2157,33 @@ hipError_t launch_group_product(hipStream_t s, uint32_t a_type_size, bool a_sign
                                 const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups,
                                 void *d_partial, uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums,
                                 uint64_t *d_counts) {
-	GroupProductTypes ty;
-	ty.p.a_tmask = type_mask(a_type_size);
-	ty.p.a_sbit = type_sign_bit(a_type_size, a_signed);
-	ty.p.b_tmask = type_mask(b_type_size);
-	ty.p.b_sbit = type_sign_bit(b_type_size, b_signed);
-	ty.k_tmask = type_mask(k_type_size);
-	ty.a_tile_rows = tile_values(a_type_size);
+	const GroupProductTypes ty = group_product_types(a_type_size, a_signed, b_type_size, b_signed, k_type_size);
 	const uint32_t nbins = ngroups + 1u;
-	unsigned long long *partial = static_cast<unsigned long long *>(d_partial);
-	unsigned long long *fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + (call_parity & 1u);
-	unsigned long long *next_fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + ((call_parity + 1u) & 1u);
-	// 1. the register-walk kernel over a's scan groups (up to 8 bins; persistent, kGroupProductRwResident = four
-	//    workgroups per CU); it counts the scan groups it cannot take in *fallback
-	uint32_t nwg_rw = 0;
-	const bool rw = nbins <= kGroupPrivateBins && g_tuning.group_product_rw && nagroups > 0;
-	if (rw) {
-		const uint64_t cap = (uint64_t)kGroupProductRwResident * device_cus();
-		nwg_rw = (uint32_t)(nagroups < cap ? nagroups : cap);
-		nwg_rw = nwg_rw < kGroupMaxWorkgroups / 2 ? nwg_rw : kGroupMaxWorkgroups / 2;
-		auto launch = [&](auto kernel) {
-			hipLaunchKernelGGL(kernel, dim3(nwg_rw), dim3(kWorkgroup), 0, s, d_agroups, (uint32_t)nagroups, d_awords, d_bdescs,
-			                   d_bwords, d_kdescs, d_kwords, ty, ngroups, partial, fallback, d_validity);
-		};
-		if (d_validity) { // without d_counts the walk keeps no row counts
-			if (d_counts) launch(k_group_product_rw<true, true>); else launch(k_group_product_rw<true, false>);
-		} else {
-			if (d_counts) launch(k_group_product_rw<false, true>); else launch(k_group_product_rw<false, false>);
-		}
-		hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	// 2. the staged-LDS kernel over a's tiles: everything when the first kernel did not run, else what it left (its
-	//    workgroups leave at once when that is nothing).  Persistent: as many workgroups as are resident at once
-	uint64_t cap = (uint64_t)kGroupProductResident * device_cus();
-	cap = cap < kGroupMaxWorkgroups / 2 ? cap : kGroupMaxWorkgroups / 2;
-	const uint32_t nwg = (uint32_t)(ntiles < cap ? ntiles : cap);
-	if (nwg) {
-		const unsigned long long *handed = rw ? fallback : static_cast<const unsigned long long *>(nullptr);
-		if (d_validity) {
-			hipLaunchKernelGGL(k_group_product<true>, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles,
-			                   d_awords, d_bdescs, d_bwords, d_kdescs, d_kwords, ty, ngroups,
-			                   partial + (uint64_t)nwg_rw * 2u * nbins, handed, d_validity);
-		} else {
-			hipLaunchKernelGGL(k_group_product<false>, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles,
-			                   d_awords, d_bdescs, d_bwords, d_kdescs, d_kwords, ty, ngroups,
-			                   partial + (uint64_t)nwg_rw * 2u * nbins, handed, d_validity);
-		}
-		hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	hipLaunchKernelGGL(k_group_final, dim3(nbins), dim3(kWorkgroup), 0, s, partial, nwg_rw, nwg, nbins, d_sums,
-	                   d_counts, static_cast<const unsigned long long *>(fallback), next_fallback, rw ? 1 : 0);
-	return hipGetLastError();
+	return launch_group_scan(
+	    nbins, g_tuning.group_product_rw != 0, nagroups, ntiles, kGroupProductRwResident, kGroupProductResident,
+	    kGroupMaxWorkgroups / 2, 2u * nbins, d_partial, call_parity,
+	    [&](uint32_t nwg, unsigned long long *partial, unsigned long long *fallback) {
+		    auto launch = [&](auto kernel) {
+			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_agroups, (uint32_t)nagroups, d_awords, d_bdescs,
+			                       d_bwords, d_kdescs, d_kwords, ty, ngroups, partial, fallback, d_validity);
+		    };
+		    if (d_validity) {
+			    if (d_counts) launch(k_group_product_rw<true, true>); else launch(k_group_product_rw<true, false>);
+		    } else {
+			    if (d_counts) launch(k_group_product_rw<false, true>); else launch(k_group_product_rw<false, false>);
+		    }
+	    },
+	    [&](uint32_t nwg, unsigned long long *partial, const unsigned long long *handed) {
+		    auto launch = [&](auto kernel) {
+			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles, d_awords,
+			                       d_bdescs, d_bwords, d_kdescs, d_kwords, ty, ngroups, partial, handed, d_validity);
+		    };
+		    if (d_validity) launch(k_group_product<true>); else launch(k_group_product<false>);
+	    },
+	    group_pairs_final(s, nbins, d_sums, d_counts));
 }
 
-// SUM(a * b * c) GROUP BY key under a selection bitmap (adac_group_product3.inl).  launch_group_product's three steps
-// with a fourth column, on the same partial buffer and hand-over slots (d_partial, call_parity: the `a` layout's, shared
-// between the grouped entry points)
+// SUM(a * b * c) GROUP BY key under a selection bitmap (adac_group_product3.inl)
 hipError_t launch_group_product3(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
                                  uint32_t c_type_size, bool c_signed, uint32_t k_type_size,
                                  const adac_segment_desc *d_adescs, const TileRef *d_atiles, uint64_t ntiles,
@@ -2181,64 +2193,38 @@ hipError_t launch_group_product3(hipStream_t s, uint32_t a_type_size, bool a_sig
                                  const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups,
                                  void *d_partial, uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums,
                                  uint64_t *d_counts) {
-	GroupProduct3Types ty;
-	ty.g.p.a_tmask = type_mask(a_type_size);
-	ty.g.p.a_sbit = type_sign_bit(a_type_size, a_signed);
-	ty.g.p.b_tmask = type_mask(b_type_size);
-	ty.g.p.b_sbit = type_sign_bit(b_type_size, b_signed);
-	ty.g.k_tmask = type_mask(k_type_size);
-	ty.g.a_tile_rows = tile_values(a_type_size);
-	ty.c_tmask = type_mask(c_type_size);
-	ty.c_sbit = type_sign_bit(c_type_size, c_signed);
+	const GroupProduct3Types ty = {group_product_types(a_type_size, a_signed, b_type_size, b_signed, k_type_size),
+	                               type_mask(c_type_size), type_sign_bit(c_type_size, c_signed)};
 	const uint32_t nbins = ngroups + 1u;
-	unsigned long long *partial = static_cast<unsigned long long *>(d_partial);
-	unsigned long long *fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + (call_parity & 1u);
-	unsigned long long *next_fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + ((call_parity + 1u) & 1u);
-	// 1. the register-walk kernel over a's scan groups (up to 8 bins; persistent, kGroupProduct3RwResident workgroups
-	//    per CU); it counts the scan groups it cannot take in *fallback
-	uint32_t nwg_rw = 0;
-	const bool rw = nbins <= kGroupPrivateBins && g_tuning.group_product3_rw && nagroups > 0;
-	if (rw) {
-		const uint64_t cap = (uint64_t)kGroupProduct3RwResident * device_cus();
-		nwg_rw = (uint32_t)(nagroups < cap ? nagroups : cap);
-		nwg_rw = nwg_rw < kGroupMaxWorkgroups / 2 ? nwg_rw : kGroupMaxWorkgroups / 2;
-		auto launch = [&](auto kernel) {
-			hipLaunchKernelGGL(kernel, dim3(nwg_rw), dim3(kWorkgroup), 0, s, d_agroups, (uint32_t)nagroups, d_awords, d_bdescs,
-			                   d_bwords, d_cdescs, d_cwords, d_kdescs, d_kwords, ty, ngroups, partial, fallback, d_validity);
-		};
-		if (d_validity) { // without d_counts the walk keeps no row counts
-			if (d_counts) launch(k_group_product3_rw<true, true>); else launch(k_group_product3_rw<true, false>);
-		} else {
-			if (d_counts) launch(k_group_product3_rw<false, true>); else launch(k_group_product3_rw<false, false>);
-		}
-		hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	// 2. the staged-LDS kernel over a's tiles: everything when the first kernel did not run, else what it left (its
-	//    workgroups leave at once when that is nothing).  Persistent: as many workgroups as are resident at once
-	uint64_t cap = (uint64_t)kGroupProduct3Resident * device_cus();
-	cap = cap < kGroupMaxWorkgroups / 2 ? cap : kGroupMaxWorkgroups / 2;
-	const uint32_t nwg = (uint32_t)(ntiles < cap ? ntiles : cap);
-	if (nwg) {
-		const unsigned long long *handed = rw ? fallback : static_cast<const unsigned long long *>(nullptr);
-		auto launch = [&](auto kernel) {
-			hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles, d_awords,
-			                   d_bdescs, d_bwords, d_cdescs, d_cwords, d_kdescs, d_kwords, ty, ngroups,
-			                   partial + (uint64_t)nwg_rw * 2u * nbins, handed, d_validity);
-		};
-		if (d_validity) launch(k_group_product3<true>); else launch(k_group_product3<false>);
-		hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	hipLaunchKernelGGL(k_group_final, dim3(nbins), dim3(kWorkgroup), 0, s, partial, nwg_rw, nwg, nbins, d_sums,
-	                   d_counts, static_cast<const unsigned long long *>(fallback), next_fallback, rw ? 1 : 0);
-	return hipGetLastError();
+	return launch_group_scan(
+	    nbins, g_tuning.group_product3_rw != 0, nagroups, ntiles, kGroupProduct3RwResident, kGroupProduct3Resident,
+	    kGroupMaxWorkgroups / 2, 2u * nbins, d_partial, call_parity,
+	    [&](uint32_t nwg, unsigned long long *partial, unsigned long long *fallback) {
+		    auto launch = [&](auto kernel) {
+			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_agroups, (uint32_t)nagroups, d_awords, d_bdescs,
+			                       d_bwords, d_cdescs, d_cwords, d_kdescs, d_kwords, ty, ngroups, partial, fallback, d_validity);
+		    };
+		    if (d_validity) {
+			    if (d_counts) launch(k_group_product3_rw<true, true>); else launch(k_group_product3_rw<true, false>);
+		    } else {
+			    if (d_counts) launch(k_group_product3_rw<false, true>); else launch(k_group_product3_rw<false, false>);
+		    }
+	    },
+	    [&](uint32_t nwg, unsigned long long *partial, const unsigned long long *handed) {
+		    auto launch = [&](auto kernel) {
+			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles, d_awords,
+			                       d_bdescs, d_bwords, d_cdescs, d_cwords, d_kdescs, d_kwords, ty, ngroups, partial, handed,
+			                       d_validity);
+		    };
+		    if (d_validity) launch(k_group_product3<true>); else launch(k_group_product3<false>);
+	    },
+	    group_pairs_final(s, nbins, d_sums, d_counts));
 }
 
 // COUNT, SUM(q), SUM(a), SUM(b), SUM(a * b), SUM(a * c), SUM(a * b * c) GROUP BY key under a selection bitmap in one scan
-// (adac_group_q1.inl).  launch_group_product3's three steps with a fifth column and seven terms, on the same partial
-// buffer and hand-over slots (d_partial, call_parity: the `a` layout's, shared between the grouped entry points).  A
-// workgroup's partial row is 7 x nbins words here, not 2 x nbins, so the grids are sized to what the buffer holds too.
+// (adac_group_q1.inl); type_size / is_signed: a, b, c, q, keys.  A workgroup's partial row is 7 x nbins words here, not
+// 2 x nbins, so the grids are capped at the rows the buffer holds, half for either kernel (257 bins: 585 rows each;
+// 8 bins: more than either grid asks for).
 hipError_t launch_group_q1(hipStream_t s, const uint32_t (&type_size)[5], const bool (&is_signed)[5],
                            const adac_segment_desc *d_adescs, const TileRef *d_atiles, uint64_t ntiles,
                            const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
@@ -2247,59 +2233,37 @@ hipError_t launch_group_q1(hipStream_t s, const uint32_t (&type_size)[5], const 
                            const adac_segment_desc *d_qdescs, const uint64_t *d_qwords,
                            const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups, void *d_partial,
                            uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_out) {
-	GroupQ1Types ty; // type_size / is_signed: a, b, c, q, keys
-	ty.g.g.p.a_tmask = type_mask(type_size[0]);
-	ty.g.g.p.a_sbit = type_sign_bit(type_size[0], is_signed[0]);
-	ty.g.g.p.b_tmask = type_mask(type_size[1]);
-	ty.g.g.p.b_sbit = type_sign_bit(type_size[1], is_signed[1]);
-	ty.g.c_tmask = type_mask(type_size[2]);
-	ty.g.c_sbit = type_sign_bit(type_size[2], is_signed[2]);
-	ty.q_tmask = type_mask(type_size[3]);
-	ty.q_sbit = type_sign_bit(type_size[3], is_signed[3]);
-	ty.g.g.k_tmask = type_mask(type_size[4]);
-	ty.g.g.a_tile_rows = tile_values(type_size[0]);
+	const GroupQ1Types ty = {
+	    {group_product_types(type_size[0], is_signed[0], type_size[1], is_signed[1], type_size[4]), type_mask(type_size[2]),
+	     type_sign_bit(type_size[2], is_signed[2])},
+	    type_mask(type_size[3]),
+	    type_sign_bit(type_size[3], is_signed[3])};
 	const uint32_t nbins = ngroups + 1u;
-	unsigned long long *partial = static_cast<unsigned long long *>(d_partial);
-	unsigned long long *fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + (call_parity & 1u);
-	unsigned long long *next_fallback = partial + (uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins + ((call_parity + 1u) & 1u);
-	// partial rows the buffer holds, half for either kernel (257 bins: 585 rows each; 8 bins: more than either grid asks for)
 	const uint64_t rows_cap = ((uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins) / ((uint64_t)kGroupQ1Terms * nbins) / 2u;
-	// 1. the register-walk kernel over a's scan groups (up to 8 bins; persistent, kGroupQ1RwResident workgroups per CU);
-	//    it counts the scan groups it cannot take in *fallback
-	uint32_t nwg_rw = 0;
-	const bool rw = nbins <= kGroupPrivateBins && g_tuning.group_q1_rw && nagroups > 0;
-	if (rw) {
-		uint64_t cap = (uint64_t)kGroupQ1RwResident * device_cus();
-		cap = cap < rows_cap ? cap : rows_cap;
-		nwg_rw = (uint32_t)(nagroups < cap ? nagroups : cap);
-		auto launch = [&](auto kernel) {
-			hipLaunchKernelGGL(kernel, dim3(nwg_rw), dim3(kWorkgroup), 0, s, d_agroups, (uint32_t)nagroups, d_awords, d_bdescs,
-			                   d_bwords, d_cdescs, d_cwords, d_qdescs, d_qwords, d_kdescs, d_kwords, ty, ngroups, partial,
-			                   fallback, d_validity);
-		};
-		if (d_validity) launch(k_group_q1_rw<true>); else launch(k_group_q1_rw<false>);
-		hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	// 2. the staged-LDS kernel over a's tiles: everything when the first kernel did not run, else what it left (its
-	//    workgroups leave at once when that is nothing).  Persistent: as many workgroups as are resident at once
-	uint64_t cap = (uint64_t)kGroupQ1Resident * device_cus();
-	cap = cap < rows_cap ? cap : rows_cap;
-	const uint32_t nwg = (uint32_t)(ntiles < cap ? ntiles : cap);
-	if (nwg) {
-		const unsigned long long *handed = rw ? fallback : static_cast<const unsigned long long *>(nullptr);
-		auto launch = [&](auto kernel) {
-			hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles, d_awords,
-			                   d_bdescs, d_bwords, d_cdescs, d_cwords, d_qdescs, d_qwords, d_kdescs, d_kwords, ty, ngroups,
-			                   partial + (uint64_t)nwg_rw * kGroupQ1Terms * nbins, handed, d_validity);
-		};
-		if (d_validity) launch(k_group_q1<true>); else launch(k_group_q1<false>);
-		hipError_t e = hipGetLastError();
-		if (e != hipSuccess) return e;
-	}
-	hipLaunchKernelGGL(k_group_q1_final, dim3(nbins), dim3(kWorkgroup), 0, s, partial, nwg_rw, nwg, nbins, d_out,
-	                   static_cast<const unsigned long long *>(fallback), next_fallback, rw ? 1 : 0);
-	return hipGetLastError();
+	return launch_group_scan(
+	    nbins, g_tuning.group_q1_rw != 0, nagroups, ntiles, kGroupQ1RwResident, kGroupQ1Resident, rows_cap,
+	    kGroupQ1Terms * nbins, d_partial, call_parity,
+	    [&](uint32_t nwg, unsigned long long *partial, unsigned long long *fallback) {
+		    auto launch = [&](auto kernel) {
+			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_agroups, (uint32_t)nagroups, d_awords, d_bdescs,
+			                       d_bwords, d_cdescs, d_cwords, d_qdescs, d_qwords, d_kdescs, d_kwords, ty, ngroups, partial,
+			                       fallback, d_validity);
+		    };
+		    if (d_validity) launch(k_group_q1_rw<true>); else launch(k_group_q1_rw<false>);
+	    },
+	    [&](uint32_t nwg, unsigned long long *partial, const unsigned long long *handed) {
+		    auto launch = [&](auto kernel) {
+			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles, d_awords,
+			                       d_bdescs, d_bwords, d_cdescs, d_cwords, d_qdescs, d_qwords, d_kdescs, d_kwords, ty, ngroups,
+			                       partial, handed, d_validity);
+		    };
+		    if (d_validity) launch(k_group_q1<true>); else launch(k_group_q1<false>);
+	    },
+	    [&](const unsigned long long *partial, uint32_t nwg_rw, uint32_t nwg, const unsigned long long *fallback,
+	        unsigned long long *next_fallback, int rw_ran) {
+		    hipLaunchKernelGGL(k_group_q1_final, dim3(nbins), dim3(kWorkgroup), 0, s, partial, nwg_rw, nwg, nbins, d_out,
+		                       fallback, next_fallback, rw_ran);
+	    });
 }
 
 // SUM(a * b) per segment under a selection bitmap (adac_sum_product.inl): one workgroup per scan group of `a`; the
