@@ -13,12 +13,19 @@ import json
 import os
 import sys
 import time
+from collections import namedtuple
+from types import SimpleNamespace
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 PKG = "duckdb-adaptive-compression_amd"
+# host mirrors of the kernels' rule "which form takes this scan group": they live in the package (forms.py) and stay
+# importable from here under the names they had when they were defined in this file
+forms = importlib.import_module(PKG + ".forms")
+product_form_groups, group_product_form_groups = forms.product_form_groups, forms.group_product_form_groups
+group_product3_form_groups, group_q1_form_groups = forms.group_product3_form_groups, forms.group_q1_form_groups
 
 
 def load(db, lay, dtype, values):
@@ -118,6 +125,188 @@ def adaptive(host, wl, nseg=400, rows=32767, periods=4):
     return out
 
 
+
+# ----------------------------------------------------------------------------------------------------------------------
+# what the scan jobs below share: the synthetic lineitem table, the column encoders, the timers, Q6's and Q1's plans
+# ----------------------------------------------------------------------------------------------------------------------
+INT32_MIN_BITS = 0x80000000  # int32's minimum as the uint32 bit pattern the scans take for "no lower bound"
+
+# TPC-H lineitem at SF10 size, synthetic: int32 columns in integer decimals and the engine's dictionary code of
+# (l_returnflag, l_linestatus) as a 6-valued uint8
+LINEITEM = {
+    "code": lambda rng, n: rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8),
+    "l_quantity": lambda rng, n: rng.integers(1, 51, size=n).astype(np.int32),
+    "l_extendedprice": lambda rng, n: rng.integers(90_000, 10_495_000, size=n).astype(np.int32),   # cents
+    "l_partkey": lambda rng, n: rng.integers(1, 2_000_001, size=n).astype(np.int32),
+    "l_shipdate": lambda rng, n: rng.integers(8036, 10562, size=n).astype(np.int32),   # days since 1970: 1992-01-02 .. 1998-12-01
+    "l_discount": lambda rng, n: rng.integers(0, 11, size=n).astype(np.int32),          # percent
+    "l_tax": lambda rng, n: rng.integers(0, 9, size=n).astype(np.int32),                # percent
+}
+Q1_CUTOFF_DAY = 10511  # l_shipdate <= cutoff keeps about 98 % of the uniform dates, as Q1's WHERE clause does
+
+
+def lineitem(rng, n, names):
+    """The named columns, drawn from rng in the order given (a job's seed and draw order are part of its numbers)."""
+    return {name: LINEITEM[name](rng, n) for name in names}
+
+
+def packed_bytes(descs):
+    return int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
+
+
+# a column on the device; `lay` and the device image come first in both, which is all q6_selects looks at
+Encoded = namedtuple("Encoded", "lay words nbytes widths descs")        # packed by adac_encode
+Blocks = namedtuple("Blocks", "lay words nseg nbytes counts info")      # DuckDB BITPACKING blocks, one per stride
+
+
+def encode_column(adac, ctx, v, counts):
+    lay = adac.Layout(ctx, v.dtype, counts)
+    d_vals = ctx.upload(v)
+    d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
+    lay.encode(d_vals, d_words)
+    ctx.sync()
+    d_vals.free()
+    descs = lay.get_descs()
+    return Encoded(lay, d_words, packed_bytes(descs), sorted(set(descs["width"].tolist())), descs)
+
+
+def bitpacking_blocks(adac, ctx, comp, dtype, stride=262144):
+    """The block image of an oracle.bitpacking.Compressed column on the device, one block per `stride` bytes."""
+    from oracle import bitpacking as bp
+    nseg = comp.nseg
+    buf = np.zeros(nseg * stride + 64, dtype=np.uint8)
+    counts = np.zeros(nseg, dtype=np.uint32)
+    used = 0
+    for i in range(nseg):
+        buf[i * stride:i * stride + bp.BLOCK_SIZE] = comp.block(i)
+        counts[i] = comp.count(i)
+        used += comp.size(i)
+    d_blocks = ctx.upload(buf)
+    lay = adac.BitpackingLayout(ctx, dtype, np.arange(nseg, dtype=np.uint64) * stride, counts)
+    info = {"segments": nseg, "groups": int(lay.ngroups), "modes": comp.groups_by_mode(),
+            "width_of_group_0": comp.group_info(0, 0)[2]}
+    return Blocks(lay, d_blocks, nseg, used, counts, info)
+
+
+def timed(ctx, fn, reps=20, warm=True):
+    """ms per call of `reps` back-to-back calls between two events, after one untimed call"""
+    if warm:
+        fn()
+    ctx.timer_start()
+    for _ in range(reps):
+        fn()
+    return ctx.timer_stop() / reps
+
+
+ROUNDS, INNER = 8, 5
+
+
+def timed_interleaved(ctx, entries, rounds=ROUNDS, inner=INNER):
+    """{name: ms per call in each round}.  Warm and interleaved: an untimed round, then `rounds` rounds in which every
+    entry runs `inner` times back to back between two events of its own (one call alone, 0.1 ms, would be timed together
+    with its launch gap).  With every entry following a different one, none starts on a cache it warmed alone."""
+    samples = {name: [] for name, _ in entries}
+    for r in range(rounds + 1):
+        for name, fn in entries:
+            ctx.timer_start()
+            for _ in range(inner):
+                fn()
+            t = ctx.timer_stop() / inner
+            if r:
+                samples[name].append(t)
+    return samples
+
+
+Q6_DATES, Q6_DISCOUNT, Q6_MAX_QUANTITY = (8766, 9130), (5, 7), 23   # 1994-01-01 .. 1994-12-31, percent, l_quantity < 24
+
+
+def q6_selects(cols, bm, d_cnt):
+    """Q6's WHERE clause as three chained selection scans; the final bitmap is bm[2].  cols: Encoded or Blocks by name."""
+    def select(name, *args):
+        lay, image = cols[name][:2]
+        lay.scan_select_between(image, *args)
+
+    select("l_shipdate", *Q6_DATES, bm[0], d_cnt)
+    select("l_discount", *Q6_DISCOUNT, bm[1], d_cnt, bm[0])
+    select("l_quantity", INT32_MIN_BITS, Q6_MAX_QUANTITY, bm[2], d_cnt, bm[1])
+
+
+def q6_mask(cols):
+    return ((cols["l_shipdate"] >= Q6_DATES[0]) & (cols["l_shipdate"] <= Q6_DATES[1]) &
+            (cols["l_discount"] >= Q6_DISCOUNT[0]) & (cols["l_discount"] <= Q6_DISCOUNT[1]) &
+            (cols["l_quantity"] <= Q6_MAX_QUANTITY))
+
+
+def q1_outputs(s, c):
+    """Q1's eight output columns per group, as integers, from the sums s["q" "p" "d" "pd" "pt" "pdt"] and the counts
+    c["q" "p" "d"] (ngroups + 1 = 7 entries each).  In integer decimals
+      sum_disc_price = 100 SUM(p) - SUM(p d)
+      sum_charge     = 10000 SUM(p) + 100 SUM(p t) - 100 SUM(p d) - SUM(p d t)
+    and the three averages are exact (sum, count) pairs."""
+    assert all(v[6] == 0 for v in list(s.values()) + list(c.values())), "no row has a key >= 6"
+    g6 = range(6)
+    return {"sum_qty": [s["q"][g] for g in g6],
+            "sum_base_price": [s["p"][g] for g in g6],
+            "sum_disc_price": [100 * s["p"][g] - s["pd"][g] for g in g6],
+            "sum_charge": [10000 * s["p"][g] + 100 * s["pt"][g] - 100 * s["pd"][g] - s["pdt"][g] for g in g6],
+            "avg_qty": [(s["q"][g], c["q"][g]) for g in g6],
+            "avg_price": [(s["p"][g], c["p"][g]) for g in g6],
+            "avg_disc": [(s["d"][g], c["d"][g]) for g in g6],
+            "count_order": [c["p"][g] for g in g6]}
+
+
+def q1_expected(cols, bins):
+    """numpy's Q1 over the rows of each bin (one boolean mask per group), in q1_outputs' form"""
+    q64, p64, d64, t64 = (cols[k].astype(np.int64) for k in ("l_quantity", "l_extendedprice", "l_discount", "l_tax"))
+    rows = [int(b.sum()) for b in bins]
+    sq, sp, sd = ([int(v[b].sum()) for b in bins] for v in (q64, p64, d64))
+    return {"sum_qty": sq, "sum_base_price": sp,
+            "sum_disc_price": [int((p64[b] * (100 - d64[b])).sum()) for b in bins],
+            "sum_charge": [int((p64[b] * (100 - d64[b]) * (100 + t64[b])).sum()) for b in bins],
+            "avg_qty": list(zip(sq, rows)), "avg_price": list(zip(sp, rows)), "avg_disc": list(zip(sd, rows)),
+            "count_order": rows}
+
+
+def q1_json(outputs):
+    return {k: [list(x) if isinstance(x, tuple) else x for x in v] for k, v in outputs.items()}
+
+
+def q1_setup(adac, ctx, n):
+    """What q1_full_packed and q1_fused_packed share: the six columns (seed 1995) encoded on one segment layout, the
+    l_shipdate select and the six grouped calls under its bitmap, every result in a (sums, counts) pair of its own."""
+    t = SimpleNamespace()
+    t.cols = lineitem(np.random.default_rng(1995), n,
+                      ("code", "l_extendedprice", "l_shipdate", "l_quantity", "l_discount", "l_tax"))
+    counts = adac.appender_segment_counts(n, 4)
+    t.enc = enc = {k: encode_column(adac, ctx, t.cols[k], counts)
+                   for k in ("code", "l_shipdate", "l_quantity", "l_extendedprice", "l_discount", "l_tax")}
+    (klay, kwords), (dlay, dwords), (qlay, qwords), (play, pwords), (clay, cwords), (tlay, twords) = (
+        e[:2] for e in enc.values())
+    t.d_filter = d_filter = ctx.alloc((n + 63) // 64 * 8 + 8)
+    d_selcnt = ctx.alloc(len(counts) * 8)
+    t.res = res = {k: (ctx.alloc(7 * 8), ctx.alloc(7 * 8)) for k in ("q", "p", "d", "pd", "pt", "pdt")}
+    t.select = lambda: dlay.scan_select_between(dwords, INT32_MIN_BITS, Q1_CUTOFF_DAY, d_filter, d_selcnt)
+
+    def sum_pdt(mask=True, with_counts=False):
+        play.scan_group_sum_product3(pwords, clay, cwords, tlay, twords, klay, kwords, 6, res["pdt"][0],
+                                     res["pdt"][1] if with_counts else None, d_filter if mask else None)
+
+    t.sum_pdt = sum_pdt
+    t.six = (
+        ("group_sum_quantity_masked", lambda: qlay.scan_group_sum_valid(qwords, klay, kwords, d_filter, 6, *res["q"])),
+        ("group_sum_price_masked", lambda: play.scan_group_sum_valid(pwords, klay, kwords, d_filter, 6, *res["p"])),
+        ("group_sum_discount_masked", lambda: clay.scan_group_sum_valid(cwords, klay, kwords, d_filter, 6, *res["d"])),
+        ("group_sum_product_price_disc_masked",
+         lambda: play.scan_group_sum_product(pwords, clay, cwords, klay, kwords, 6, res["pd"][0], None, d_filter)),
+        ("group_sum_product_price_tax_masked",
+         lambda: play.scan_group_sum_product(pwords, tlay, twords, klay, kwords, 6, res["pt"][0], None, d_filter)),
+        ("group_sum_product3_masked", sum_pdt))
+    t.keep = t.cols["l_shipdate"] <= Q1_CUTOFF_DAY
+    t.all_bins = [t.cols["code"] == g for g in range(6)]
+    t.kept_bins = [b & t.keep for b in t.all_bins]
+    return t
+
+
 def bitpacking_columns(n):
     rng = np.random.default_rng(11)
     return {
@@ -134,20 +323,9 @@ def bitpacking_fused_scans(adac, n=50_000_000):
     from oracle import bitpacking as bp
     ctx = adac.Context(0)
     out = {"rows": n, "cases": []}
-    stride = 262144
-    reps = 20
     for name, v in bitpacking_columns(n).items():
         comp = bp.Compressed(v)
-        nseg = comp.nseg
-        buf = np.zeros(nseg * stride + 64, dtype=np.uint8)
-        counts = np.zeros(nseg, dtype=np.uint32)
-        used = 0
-        for i in range(nseg):
-            buf[i * stride:i * stride + bp.BLOCK_SIZE] = comp.block(i)
-            counts[i] = comp.count(i)
-            used += comp.size(i)
-        d_blocks = ctx.upload(buf)
-        lay = adac.BitpackingLayout(ctx, v.dtype, np.arange(nseg, dtype=np.uint64) * stride, counts)
+        lay, d_blocks, nseg, used, counts, info = bitpacking_blocks(adac, ctx, comp, v.dtype)
         d_out = ctx.alloc(n * v.dtype.itemsize + 64)
         d_sum, d_cnt, d_bm = ctx.alloc(nseg * 8), ctx.alloc(nseg * 8), ctx.alloc((n + 63) // 64 * 8 + 8)
         lo, hi = (int(x) for x in np.quantile(v, [0.45, 0.55]))
@@ -169,15 +347,11 @@ def bitpacking_fused_scans(adac, n=50_000_000):
                          ("select", lambda: lay.scan_select_between(d_blocks, lo, hi, d_bm, d_cnt)),
                          ("decode_again", lambda: lay.unpack(d_blocks, d_out)),
                          ("scan_sum_again", lambda: lay.scan_sum(d_blocks, d_sum))):
-            fn()
-            ctx.timer_start()
-            for _ in range(reps):
-                fn()
-            ms[what] = ctx.timer_stop() / reps
+            ms[what] = timed(ctx, fn)
         dec, ssum = min(ms["decode"], ms["decode_again"]), min(ms["scan_sum"], ms["scan_sum_again"])
         out["cases"].append({
-            "name": name, "dtype": str(v.dtype), "segments": nseg, "groups": int(lay.ngroups), "compressed_bytes": used,
-            "modes": comp.groups_by_mode(), "selectivity": float(hit.mean()), "ms": ms,
+            "name": name, "dtype": str(v.dtype), "segments": nseg, "groups": info["groups"], "compressed_bytes": used,
+            "modes": info["modes"], "selectivity": float(hit.mean()), "ms": ms,
             "decode_ms": dec, "scan_sum_ms": ssum, "select_ms": ms["select"],
             "scan_sum_over_decode": ssum / dec, "select_over_decode": ms["select"] / dec,
             "scan_sum_block_TBps": used / (ssum * 1e-3) / 1e12, "select_block_TBps": used / (ms["select"] * 1e-3) / 1e12,
@@ -194,31 +368,17 @@ def bitpacking_scan(adac, n=50_000_000):
     from oracle import bitpacking as bp
     ctx = adac.Context(0)
     out = {"rows": n, "cases": []}
-    cols = bitpacking_columns(n)
     stride = 262144
-    for name, v in cols.items():
+    for name, v in bitpacking_columns(n).items():
         t0 = time.perf_counter()
         comp = bp.Compressed(v)
         t_cpu = time.perf_counter() - t0
-        nseg = comp.nseg
-        buf = np.zeros(nseg * stride + 64, dtype=np.uint8)
-        counts = np.zeros(nseg, dtype=np.uint32)
-        used = 0
-        for i in range(nseg):
-            buf[i * stride:i * stride + bp.BLOCK_SIZE] = comp.block(i)
-            counts[i] = comp.count(i)
-            used += comp.size(i)
-        d_blocks = ctx.upload(buf)
-        lay = adac.BitpackingLayout(ctx, v.dtype, np.arange(nseg, dtype=np.uint64) * stride, counts)
+        lay, d_blocks, nseg, used, _, info = bitpacking_blocks(adac, ctx, comp, v.dtype, stride)
         d_out = ctx.alloc(n * v.dtype.itemsize + 64)
         lay.unpack(d_blocks, d_out)
         ctx.sync()
         assert np.array_equal(d_out.download(v.dtype, n), v)
-        ctx.timer_start()
-        reps = 20
-        for _ in range(reps):
-            lay.unpack(d_blocks, d_out)
-        ms = ctx.timer_stop() / reps
+        ms = timed(ctx, lambda: lay.unpack(d_blocks, d_out), warm=False)
         # GPU compress of the same column: statistics + host decisions + group writes (wall time, host included)
         d_vals = ctx.upload(v)
         t0 = time.perf_counter()
@@ -227,7 +387,7 @@ def bitpacking_scan(adac, n=50_000_000):
         plan.write(d_vals, d_new)
         ctx.sync()
         t_gpu_compress = time.perf_counter() - t0
-        assert plan.nseg == nseg and plan.groups_by_mode() == comp.groups_by_mode()
+        assert plan.nseg == nseg and plan.groups_by_mode() == info["modes"]
         img = d_new.download(np.uint8, nseg * plan.BLOCK_STRIDE)
         assert all(np.array_equal(img[i * stride:i * stride + comp.size(i)], comp.block(i)[:comp.size(i)])
                    for i in range(0, nseg, max(1, nseg // 16)))
@@ -235,7 +395,7 @@ def bitpacking_scan(adac, n=50_000_000):
         out["cases"].append({
             "gpu_compress_values_per_s": n / t_gpu_compress, "gpu_compress_s": t_gpu_compress,
             "name": name, "dtype": str(v.dtype), "segments": nseg, "compressed_bytes": used,
-            "modes": comp.groups_by_mode(), "cpu_compress_values_per_s": n / t_cpu, "decode_ms": ms,
+            "modes": info["modes"], "cpu_compress_values_per_s": n / t_cpu, "decode_ms": ms,
             "decode_values_per_s": n / (ms * 1e-3),
             "algorithmic_GBps": (used + n * v.dtype.itemsize) / (ms * 1e-3) / 1e9,
         })
@@ -252,92 +412,56 @@ def q6_packed(adac, n=59_986_052):
     adac_scan_sum_product.)  Beside it: the materialising plan (decode the four columns, then filter)
     counted at its decode cost alone."""
     ctx = adac.Context(0)
-    rng = np.random.default_rng(1994)
-    cols = {"l_shipdate": rng.integers(8036, 10562, size=n).astype(np.int32),       # days since 1970: 1992..1998
-            "l_discount": rng.integers(0, 11, size=n).astype(np.int32),               # percent
-            "l_quantity": rng.integers(1, 51, size=n).astype(np.int32),
-            "l_extendedprice": rng.integers(90_000, 10_495_000, size=n).astype(np.int32)}  # cents
+    cols = lineitem(np.random.default_rng(1994), n, ("l_shipdate", "l_discount", "l_quantity", "l_extendedprice"))
     counts = adac.appender_segment_counts(n, 4)
-    enc, packed_bytes = {}, 0
-    for name, v in cols.items():
-        lay = adac.Layout(ctx, np.int32, counts)
-        d_vals = ctx.upload(v)
-        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
-        lay.encode(d_vals, d_words)
-        ctx.sync()
-        descs = lay.get_descs()
-        packed_bytes += int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
-        enc[name] = (lay, d_words, sorted(set(descs["width"].tolist())))
-        del d_vals
+    enc = {name: encode_column(adac, ctx, v, counts) for name, v in cols.items()}
+    total_bytes = sum(e.nbytes for e in enc.values())
     nw = (n + 63) // 64
     bm = [ctx.alloc(nw * 8 + 8) for _ in range(3)]
     d_cnt = ctx.alloc(len(counts) * 8)
     d_sum = ctx.alloc(len(counts) * 8)
-    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
+    ship, disc, price = enc["l_shipdate"], enc["l_discount"], enc["l_extendedprice"]
 
     def q6():
-        lay, w, _ = enc["l_shipdate"]
-        lay.scan_select_between(w, 8766, 9130, bm[0], d_cnt)              # 1994-01-01 .. 1994-12-31
-        lay, w, _ = enc["l_discount"]
-        lay.scan_select_between(w, 5, 7, bm[1], d_cnt, bm[0])
-        lay, w, _ = enc["l_quantity"]
-        lay.scan_select_between(w, int_min, 23, bm[2], d_cnt, bm[1])
-        lay, w, _ = enc["l_extendedprice"]
-        lay.scan_sum(w, d_sum, bm[2])
+        q6_selects(enc, bm, d_cnt)
+        price.lay.scan_sum(price.words, d_sum, bm[2])
 
     q6()
     ctx.sync()
-    m = ((cols["l_shipdate"] >= 8766) & (cols["l_shipdate"] <= 9130) & (cols["l_discount"] >= 5) &
-         (cols["l_discount"] <= 7) & (cols["l_quantity"] < 24))
+    m = q6_mask(cols)
     got = int(d_sum.download(np.uint64, len(counts)).sum(dtype=np.uint64))
     assert got == int(cols["l_extendedprice"][m].astype(np.int64).sum()), "Q6 parity"
     assert int(d_cnt.download(np.uint64, len(counts)).sum()) == int(m.sum())
-    reps = 20
     by_group = {}
     for group in (2, 4, 8, 16):
         adac.set_tuning("scan_tiles_per_wg", group)
-        q6()
-        ctx.timer_start()
-        for _ in range(reps):
-            q6()
-        by_group[group] = ctx.timer_stop() / reps
+        by_group[group] = timed(ctx, q6)
     adac.set_tuning("scan_tiles_per_wg", 0)
-    q6()
-    ctx.timer_start()
-    for _ in range(reps):
-        q6()
-    ms = ctx.timer_stop() / reps
+    ms = timed(ctx, q6)
     steps = {}
-    for name, fn in (("select_shipdate", lambda: enc["l_shipdate"][0].scan_select_between(enc["l_shipdate"][1], 8766, 9130, bm[0], d_cnt)),
-                     ("select_discount_masked", lambda: enc["l_discount"][0].scan_select_between(enc["l_discount"][1], 5, 7, bm[1], d_cnt, bm[0])),
-                     ("sum_price_masked", lambda: enc["l_extendedprice"][0].scan_sum(enc["l_extendedprice"][1], d_sum, bm[2])),
-                     ("count_shipdate", lambda: enc["l_shipdate"][0].scan_count_between(enc["l_shipdate"][1], 8766, 9130, d_cnt))):
-        fn()
-        ctx.timer_start()
-        for _ in range(reps):
-            fn()
-        steps[name] = ctx.timer_stop() / reps
+    for name, fn in (("select_shipdate", lambda: ship.lay.scan_select_between(ship.words, *Q6_DATES, bm[0], d_cnt)),
+                     ("select_discount_masked", lambda: disc.lay.scan_select_between(disc.words, *Q6_DISCOUNT, bm[1], d_cnt, bm[0])),
+                     ("sum_price_masked", lambda: price.lay.scan_sum(price.words, d_sum, bm[2])),
+                     ("count_shipdate", lambda: ship.lay.scan_count_between(ship.words, *Q6_DATES, d_cnt))):
+        steps[name] = timed(ctx, fn)
     # filter then project: only the surviving rows of l_extendedprice are decoded
     d_sel = ctx.alloc(int(m.sum()) * 4 + 64)
-    lay, w, _ = enc["l_extendedprice"]
-    got = lay.unpack_selected(w, bm[2], d_sel)
+    got = price.lay.unpack_selected(price.words, bm[2], d_sel)
     assert got == int(m.sum()) and np.array_equal(d_sel.download(np.int32, got), cols["l_extendedprice"][m])
-    ctx.timer_start()
-    for _ in range(reps):
-        lay.unpack_selected(w, bm[2], d_sel, None, False)
-    steps["project_price_selected"] = ctx.timer_stop() / reps
+    steps["project_price_selected"] = timed(ctx, lambda: price.lay.unpack_selected(price.words, bm[2], d_sel, None, False),
+                                            warm=False)
     d_out = ctx.alloc(n * 4 + 64)
-    ctx.timer_start()
-    for _ in range(reps):
-        for name in cols:
-            lay, w, _ = enc[name]
-            lay.unpack(w, d_out)
-    ms_dec = ctx.timer_stop() / reps
-    out = {"rows": n, "selected_rows": int(m.sum()), "widths": {k: v[2] for k, v in enc.items()},
-           "packed_bytes": packed_bytes, "q6_on_packed_ms": ms, "q6_rows_per_s": n / (ms * 1e-3),
-           "q6_packed_read_GBps": packed_bytes / (ms * 1e-3) / 1e9,
+
+    def decode_four():
+        for e in enc.values():
+            e.lay.unpack(e.words, d_out)
+
+    ms_dec = timed(ctx, decode_four, warm=False)
+    out = {"rows": n, "selected_rows": int(m.sum()), "widths": {k: e.widths for k, e in enc.items()},
+           "packed_bytes": total_bytes, "q6_on_packed_ms": ms, "q6_rows_per_s": n / (ms * 1e-3),
+           "q6_packed_read_GBps": total_bytes / (ms * 1e-3) / 1e9,
            "decode_four_columns_ms": ms_dec,
-           "decode_four_columns_total_GBps": (packed_bytes + 4 * n * 4) / (ms_dec * 1e-3) / 1e9, "q6_ms_by_scan_tiles_per_wg": by_group, "step_ms": steps,
+           "decode_four_columns_total_GBps": (total_bytes + 4 * n * 4) / (ms_dec * 1e-3) / 1e9, "q6_ms_by_scan_tiles_per_wg": by_group, "step_ms": steps,
            "note": "q6_on_packed = 3 chained filter scans (selection bitmaps) + 1 masked SUM; decode_four_columns is "
                    "only the materialisation a decode-then-filter plan would pay before filtering"}
     ctx.close()
@@ -352,32 +476,18 @@ def q1_packed(adac, n=59_986_052):
     HBM; checked against numpy's GROUP BY.  Beside it: decoding the same columns (what the reference's engine needs
     before its hash aggregate can start)."""
     ctx = adac.Context(0)
-    rng = np.random.default_rng(1992)
-    code = rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8)
-    cols = {"l_quantity": rng.integers(1, 51, size=n).astype(np.int32),
-            "l_extendedprice": rng.integers(90_000, 10_495_000, size=n).astype(np.int32),
-            "l_partkey": rng.integers(1, 2_000_001, size=n).astype(np.int32)}
+    cols = lineitem(np.random.default_rng(1992), n, ("code", "l_quantity", "l_extendedprice", "l_partkey"))
+    code = cols.pop("code")
     counts = adac.appender_segment_counts(n, 4)
-
-    def enc_col(v):
-        lay = adac.Layout(ctx, v.dtype, counts)
-        d_vals = ctx.upload(v)
-        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
-        lay.encode(d_vals, d_words)
-        ctx.sync()
-        descs = lay.get_descs()
-        nbytes = int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
-        return lay, d_words, nbytes, sorted(set(descs["width"].tolist()))
-
-    klay, kwords, kbytes, kwidths = enc_col(code)
+    klay, kwords, kbytes, kwidths, _ = encode_column(adac, ctx, code, counts)
     d_sums = ctx.alloc(7 * 8)
     d_cnts = ctx.alloc(7 * 8)
     out = {"rows": n, "groups": 6, "key_widths": kwidths, "key_packed_bytes": kbytes, "columns": []}
     total_ms, total_bytes = 0.0, 0
-    reps = 20
     for name, v in cols.items():
-        lay, words, nbytes, widths = enc_col(v)
-        lay.scan_group_sum(words, klay, kwords, 6, d_sums, d_cnts)
+        lay, words, nbytes, widths, _ = encode_column(adac, ctx, v, counts)
+        group_sum = lambda: lay.scan_group_sum(words, klay, kwords, 6, d_sums, d_cnts)
+        group_sum()
         ctx.sync()
         got_s = d_sums.download(np.uint64, 7).tolist()
         got_c = d_cnts.download(np.uint64, 7).tolist()
@@ -385,25 +495,14 @@ def q1_packed(adac, n=59_986_052):
             m = code == g
             assert got_c[g] == int(m.sum()) and got_s[g] == int(v[m].astype(np.int64).sum()), "Q1 parity"
         assert got_c[6] == 0
-        ctx.timer_start()
-        for _ in range(reps):
-            lay.scan_group_sum(words, klay, kwords, 6, d_sums, d_cnts)
-        ms = ctx.timer_stop() / reps
+        ms = timed(ctx, group_sum, warm=False)
         # the same aggregate through the staged-LDS kernel alone (round 2's form), for the record
         adac.set_tuning("group_sum_rw", 0)
-        lay.scan_group_sum(words, klay, kwords, 6, d_sums, d_cnts)
-        ctx.timer_start()
-        for _ in range(reps):
-            lay.scan_group_sum(words, klay, kwords, 6, d_sums, d_cnts)
-        ms_lds = ctx.timer_stop() / reps
+        ms_lds = timed(ctx, group_sum)
         assert d_sums.download(np.uint64, 7).tolist() == got_s and d_cnts.download(np.uint64, 7).tolist() == got_c
         adac.set_tuning("group_sum_rw", 1)
         d_out = ctx.alloc(n * 4 + 64)
-        lay.unpack(words, d_out)
-        ctx.timer_start()
-        for _ in range(reps):
-            lay.unpack(words, d_out)
-        ms_dec = ctx.timer_stop() / reps
+        ms_dec = timed(ctx, lambda: lay.unpack(words, d_out))
         del d_out
         total_ms += ms
         total_bytes += nbytes + kbytes
@@ -430,40 +529,16 @@ def q1_filtered_packed(adac, n=59_986_052):
     bitmap costs the plain fused SUM (adac_scan_sum_valid with all ones over adac_scan_sum) on that column."""
     ctx = adac.Context(0)
     rng = np.random.default_rng(1992)
-    code = rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8)
-    cols = {"l_quantity": rng.integers(1, 51, size=n).astype(np.int32),
-            "l_extendedprice": rng.integers(90_000, 10_495_000, size=n).astype(np.int32),
-            "l_partkey": rng.integers(1, 2_000_001, size=n).astype(np.int32)}
-    shipdate = rng.integers(8036, 10562, size=n).astype(np.int32)       # days since 1970: 1992-01-02 .. 1998-12-01
-    cutoff = 10511                                                     # the 98th percentile of the uniform dates
+    cols = lineitem(rng, n, ("code", "l_quantity", "l_extendedprice", "l_partkey", "l_shipdate"))
+    code, shipdate = cols.pop("code"), cols.pop("l_shipdate")
+    cutoff = Q1_CUTOFF_DAY
     counts = adac.appender_segment_counts(n, 4)
-
-    def enc_col(v):
-        lay = adac.Layout(ctx, v.dtype, counts)
-        d_vals = ctx.upload(v)
-        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
-        lay.encode(d_vals, d_words)
-        ctx.sync()
-        descs = lay.get_descs()
-        nbytes = int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
-        return lay, d_words, nbytes, sorted(set(descs["width"].tolist()))
-
-    reps = 20
-
-    def timed(fn):
-        fn()
-        ctx.timer_start()
-        for _ in range(reps):
-            fn()
-        return ctx.timer_stop() / reps
-
-    klay, kwords, kbytes, kwidths = enc_col(code)
-    dlay, dwords, dbytes, dwidths = enc_col(shipdate)
+    klay, kwords, kbytes, kwidths, _ = encode_column(adac, ctx, code, counts)
+    dlay, dwords, dbytes, dwidths, _ = encode_column(adac, ctx, shipdate, counts)
     nw = (n + 63) // 64
     d_filter = ctx.alloc(nw * 8 + 8)
     d_selcnt = ctx.alloc(len(counts) * 8)
-    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
-    select = lambda: dlay.scan_select_between(dwords, int_min, cutoff, d_filter, d_selcnt)
+    select = lambda: dlay.scan_select_between(dwords, INT32_MIN_BITS, cutoff, d_filter, d_selcnt)
     select()
     ctx.sync()
     keep = shipdate <= cutoff
@@ -481,20 +556,20 @@ def q1_filtered_packed(adac, n=59_986_052):
 
     out = {"rows": n, "groups": 6, "cutoff_day": cutoff, "selected_rows": int(keep.sum()),
            "selected_fraction": float(keep.mean()), "key_widths": kwidths, "date_widths": dwidths,
-           "filter_ms": timed(select), "filter_packed_bytes": dbytes, "columns": []}
+           "filter_ms": timed(ctx, select), "filter_packed_bytes": dbytes, "columns": []}
     total_masked = total_plain = 0.0
     for name, v in cols.items():
-        lay, words, nbytes, widths = enc_col(v)
+        lay, words, nbytes, widths, _ = encode_column(adac, ctx, v, counts)
         for d_mask, m in ((d_filter, keep), (d_half, half), (d_ones, np.ones(n, dtype=bool)), (None, np.ones(n, dtype=bool))):
             lay.scan_group_sum_valid(words, klay, kwords, d_mask, 6, d_sums, d_cnts)
             ctx.sync()
             assert (d_sums.download(np.uint64, 7).tolist(), d_cnts.download(np.uint64, 7).tolist()) == grouped(v, m), "Q1 parity"
-        ms_plain = timed(lambda: lay.scan_group_sum(words, klay, kwords, 6, d_sums, d_cnts))
-        ms_filter = timed(lambda: lay.scan_group_sum_valid(words, klay, kwords, d_filter, 6, d_sums, d_cnts))
-        ms_ones = timed(lambda: lay.scan_group_sum_valid(words, klay, kwords, d_ones, 6, d_sums, d_cnts))
-        ms_half = timed(lambda: lay.scan_group_sum_valid(words, klay, kwords, d_half, 6, d_sums, d_cnts))
-        ms_sum = timed(lambda: lay.scan_sum(words, d_seg))
-        ms_sum_ones = timed(lambda: lay.scan_sum(words, d_seg, d_ones))
+        ms_plain = timed(ctx, lambda: lay.scan_group_sum(words, klay, kwords, 6, d_sums, d_cnts))
+        ms_filter = timed(ctx, lambda: lay.scan_group_sum_valid(words, klay, kwords, d_filter, 6, d_sums, d_cnts))
+        ms_ones = timed(ctx, lambda: lay.scan_group_sum_valid(words, klay, kwords, d_ones, 6, d_sums, d_cnts))
+        ms_half = timed(ctx, lambda: lay.scan_group_sum_valid(words, klay, kwords, d_half, 6, d_sums, d_cnts))
+        ms_sum = timed(ctx, lambda: lay.scan_sum(words, d_seg))
+        ms_sum_ones = timed(ctx, lambda: lay.scan_sum(words, d_seg, d_ones))
         total_masked += ms_filter
         total_plain += ms_plain
         out["columns"].append({"column": name, "widths": widths, "packed_bytes": nbytes,
@@ -513,71 +588,26 @@ def q1_filtered_packed(adac, n=59_986_052):
     return out
 
 
-def product_form_groups(descs_a, descs_b, type_size=4, signed=True):
-    """Which form of k_scan_product takes how many scan groups of `a` — product_fast_eligible (adac_sum_product.inl)
-    evaluated on the host descriptors, with the default grouping of ensure_scan_groups."""
-    tb = 8 * type_size
-    tmask, sbit = (1 << tb) - 1, (1 << (tb - 1)) if signed else 0
-    tile, per = 16384 // type_size, {8: 12, 4: 6, 2: 8, 1: 4}[type_size]
-
-    def frame_ok(d):
-        if (int(d["flags"]) & 1) and int(d["min"]) != 0xFFFFFFFFFFFFFFFF:
-            bmin = (int(d["min"]) & tmask) ^ sbit
-            return bmin + (1 << int(d["width"])) - 1 <= tmask
-        return sbit == 0
-
-    out = {"fast": 0, "generic": 0}
-    for da, db in zip(descs_a, descs_b):
-        ntiles = (int(da["count"]) + tile - 1) // tile
-        if ntiles == 0:
-            continue
-        wa, wb = int(da["width"]), int(db["width"])
-        fast = (4 <= wa <= 32 and 1 <= wb <= 32 and int(da["count"]) * wa < 2 ** 31 and int(db["count"]) * wb < 2 ** 31
-                and frame_ok(da) and frame_ok(db))
-        out["fast" if fast else "generic"] += (ntiles + per - 1) // per
-    return out
-
-
 def q6_product_packed(adac, n=59_986_052):
     """TPC-H Q6 proper on packed columns: the four int32 columns and the three chained selects of q6_packed, then
     SUM(l_extendedprice * l_discount) under the final bitmap with adac_scan_sum_product — no value is materialised.
     Beside it, in the same process: what a caller paid before (adac_unpack of the two columns, after which the
     multiplication is still to do) and the two masked single-column SUMs, a lower bound for any walk of both columns."""
     ctx = adac.Context(0)
-    rng = np.random.default_rng(1994)
-    cols = {"l_shipdate": rng.integers(8036, 10562, size=n).astype(np.int32),
-            "l_discount": rng.integers(0, 11, size=n).astype(np.int32),
-            "l_quantity": rng.integers(1, 51, size=n).astype(np.int32),
-            "l_extendedprice": rng.integers(90_000, 10_495_000, size=n).astype(np.int32)}
+    cols = lineitem(np.random.default_rng(1994), n, ("l_shipdate", "l_discount", "l_quantity", "l_extendedprice"))
     counts = adac.appender_segment_counts(n, 4)
-    enc, packed_bytes = {}, {}
-    for name, v in cols.items():
-        lay = adac.Layout(ctx, np.int32, counts)
-        d_vals = ctx.upload(v)
-        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
-        lay.encode(d_vals, d_words)
-        ctx.sync()
-        descs = lay.get_descs()
-        packed_bytes[name] = int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
-        enc[name] = (lay, d_words, sorted(set(descs["width"].tolist())), descs)
-        del d_vals
+    enc = {name: encode_column(adac, ctx, v, counts) for name, v in cols.items()}
     nw = (n + 63) // 64
     bm = [ctx.alloc(nw * 8 + 8) for _ in range(3)]
     d_cnt = ctx.alloc(len(counts) * 8)
     d_sum = ctx.alloc(len(counts) * 8)
-    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
     price, disc = enc["l_extendedprice"], enc["l_discount"]
 
     def selects():
-        lay, w = enc["l_shipdate"][:2]
-        lay.scan_select_between(w, 8766, 9130, bm[0], d_cnt)              # 1994-01-01 .. 1994-12-31
-        lay, w = enc["l_discount"][:2]
-        lay.scan_select_between(w, 5, 7, bm[1], d_cnt, bm[0])
-        lay, w = enc["l_quantity"][:2]
-        lay.scan_select_between(w, int_min, 23, bm[2], d_cnt, bm[1])
+        q6_selects(enc, bm, d_cnt)
 
     def product():
-        price[0].scan_sum_product(price[1], disc[0], disc[1], d_sum, bm[2])
+        price.lay.scan_sum_product(price.words, disc.lay, disc.words, d_sum, bm[2])
 
     def q6():
         selects()
@@ -585,41 +615,34 @@ def q6_product_packed(adac, n=59_986_052):
 
     q6()
     ctx.sync()
-    m = ((cols["l_shipdate"] >= 8766) & (cols["l_shipdate"] <= 9130) & (cols["l_discount"] >= 5) &
-         (cols["l_discount"] <= 7) & (cols["l_quantity"] < 24))
-    got = int(d_sum.download(np.uint64, len(counts)).sum(dtype=np.uint64))
-    assert got == int((cols["l_extendedprice"][m].astype(np.int64) * cols["l_discount"][m]).sum()), "Q6 parity"
+    m = q6_mask(cols)
+    want = int((cols["l_extendedprice"][m].astype(np.int64) * cols["l_discount"][m]).sum())
+    assert int(d_sum.download(np.uint64, len(counts)).sum(dtype=np.uint64)) == want, "Q6 parity"
     assert int(d_cnt.download(np.uint64, len(counts)).sum()) == int(m.sum())
-    reps = 20
     d_out = ctx.alloc(n * 4 + 64)
 
     def unpack_two():
-        price[0].unpack(price[1], d_out)
-        disc[0].unpack(disc[1], d_out)
+        price.lay.unpack(price.words, d_out)
+        disc.lay.unpack(disc.words, d_out)
 
     def two_sums():
-        price[0].scan_sum(price[1], d_sum, bm[2])
-        disc[0].scan_sum(disc[1], d_sum, bm[2])
+        price.lay.scan_sum(price.words, d_sum, bm[2])
+        disc.lay.scan_sum(disc.words, d_sum, bm[2])
 
     ms = {}
     for name, fn in (("q6_product_on_packed", q6), ("select_chain", selects), ("sum_product_masked", product),
                      ("unpack_price_and_discount", unpack_two), ("two_masked_scan_sums", two_sums),
-                     ("sum_product_unmasked", lambda: price[0].scan_sum_product(price[1], disc[0], disc[1], d_sum))):
-        fn()
-        ctx.timer_start()
-        for _ in range(reps):
-            fn()
-        ms[name] = ctx.timer_stop() / reps
+                     ("sum_product_unmasked", lambda: price.lay.scan_sum_product(price.words, disc.lay, disc.words, d_sum))):
+        ms[name] = timed(ctx, fn)
     product()  # leave the masked result behind and check it once more after the timed loops
-    got = int(d_sum.download(np.uint64, len(counts)).sum(dtype=np.uint64))
-    assert got == int((cols["l_extendedprice"][m].astype(np.int64) * cols["l_discount"][m]).sum()), "Q6 parity (after timing)"
-    two = packed_bytes["l_extendedprice"] + packed_bytes["l_discount"]
-    out = {"rows": n, "selected_rows": int(m.sum()), "widths": {k: v[2] for k, v in enc.items()},
-           "packed_bytes": packed_bytes, "step_ms": ms,
+    assert int(d_sum.download(np.uint64, len(counts)).sum(dtype=np.uint64)) == want, "Q6 parity (after timing)"
+    two = price.nbytes + disc.nbytes
+    out = {"rows": n, "selected_rows": int(m.sum()), "widths": {k: e.widths for k, e in enc.items()},
+           "packed_bytes": {k: e.nbytes for k, e in enc.items()}, "step_ms": ms,
            "sum_product_packed_read_GBps": (two + n / 8) / (ms["sum_product_masked"] * 1e-3) / 1e9,
            "unpack_two_columns_total_GBps": (two + 2 * n * 4) / (ms["unpack_price_and_discount"] * 1e-3) / 1e9,
            "product_faster_than_unpack": ms["sum_product_masked"] < ms["unpack_price_and_discount"],
-           "groups_by_form": product_form_groups(price[3], disc[3]),
+           "groups_by_form": product_form_groups(price.descs, disc.descs),
            "note": "sum_product_masked = adac_scan_sum_product(l_extendedprice, l_discount) under the final bitmap of the "
                    "three chained selects; unpack_price_and_discount is what a caller paid before it could start to "
                    "multiply; two_masked_scan_sums is a lower bound for any walk of the two columns"}
@@ -636,103 +659,73 @@ def q6_bitpacking(adac, n=59_986_052):
     Q1's bitmap (l_shipdate <= cutoff), against adac_bp_unpack of those two columns."""
     from oracle import bitpacking as bp
     ctx = adac.Context(0)
-    rng = np.random.default_rng(1994)
-    cols = {"l_shipdate": rng.integers(8036, 10562, size=n).astype(np.int32),
-            "l_discount": rng.integers(0, 11, size=n).astype(np.int32),
-            "l_quantity": rng.integers(1, 51, size=n).astype(np.int32),
-            "l_extendedprice": rng.integers(90_000, 10_495_000, size=n).astype(np.int32),
-            "code": rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8)}
-    stride = 262144
-    enc, packed_bytes, info = {}, {}, {}
-    for name, v in cols.items():
-        comp = bp.Compressed(v)
-        nseg = comp.nseg
-        buf = np.zeros(nseg * stride + 64, dtype=np.uint8)
-        counts = np.zeros(nseg, dtype=np.uint32)
-        used = 0
-        for i in range(nseg):
-            buf[i * stride:i * stride + bp.BLOCK_SIZE] = comp.block(i)
-            counts[i] = comp.count(i)
-            used += comp.size(i)
-        lay = adac.BitpackingLayout(ctx, v.dtype, np.arange(nseg, dtype=np.uint64) * stride, counts)
-        enc[name] = (lay, ctx.upload(buf), nseg)
-        packed_bytes[name] = used
-        info[name] = {"segments": nseg, "groups": int(lay.ngroups), "modes": comp.groups_by_mode(),
-                      "width_of_group_0": comp.group_info(0, 0)[2]}
-        del comp, buf
+    cols = lineitem(np.random.default_rng(1994), n, ("l_shipdate", "l_discount", "l_quantity", "l_extendedprice", "code"))
+    enc = {name: bitpacking_blocks(adac, ctx, bp.Compressed(v), v.dtype) for name, v in cols.items()}
     nw = (n + 63) // 64
     bm = [ctx.alloc(nw * 8 + 8) for _ in range(3)]
     d_q1 = ctx.alloc(nw * 8 + 8)
     price, disc, qty, ship, code = (enc[k] for k in ("l_extendedprice", "l_discount", "l_quantity", "l_shipdate", "code"))
-    d_cnt = ctx.alloc(max(e[2] for e in enc.values()) * 8)
-    d_sum = ctx.alloc(price[2] * 8)
+    d_cnt = ctx.alloc(max(e.nseg for e in enc.values()) * 8)
+    d_sum = ctx.alloc(price.nseg * 8)
     d_gsum, d_gcnt = ctx.alloc(7 * 8), ctx.alloc(7 * 8)
-    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
-    cutoff = 10511
+    cutoff = Q1_CUTOFF_DAY
 
     def selects():
-        ship[0].scan_select_between(ship[1], 8766, 9130, bm[0], d_cnt)              # 1994-01-01 .. 1994-12-31
-        disc[0].scan_select_between(disc[1], 5, 7, bm[1], d_cnt, bm[0])
-        qty[0].scan_select_between(qty[1], int_min, 23, bm[2], d_cnt, bm[1])
+        q6_selects(enc, bm, d_cnt)
 
     def product():
-        price[0].scan_sum_product(price[1], disc[0], disc[1], d_sum, bm[2])
+        price.lay.scan_sum_product(price.words, disc.lay, disc.words, d_sum, bm[2])
 
     def q6():
         selects()
         product()
 
     def grouped():
-        qty[0].scan_group_sum(qty[1], code[0], code[1], 6, d_gsum, d_gcnt, d_q1)
+        qty.lay.scan_group_sum(qty.words, code.lay, code.words, 6, d_gsum, d_gcnt, d_q1)
 
     q6()
-    ship[0].scan_select_between(ship[1], int_min, cutoff, d_q1, d_cnt)
+    ship.lay.scan_select_between(ship.words, INT32_MIN_BITS, cutoff, d_q1, d_cnt)
     grouped()
     ctx.sync()
-    m = ((cols["l_shipdate"] >= 8766) & (cols["l_shipdate"] <= 9130) & (cols["l_discount"] >= 5) &
-         (cols["l_discount"] <= 7) & (cols["l_quantity"] < 24))
+    m = q6_mask(cols)
     want_q6 = int((cols["l_extendedprice"][m].astype(np.int64) * cols["l_discount"][m]).sum())
-    assert int(d_sum.download(np.uint64, price[2]).sum(dtype=np.uint64)) == want_q6, "Q6 parity"
+    assert int(d_sum.download(np.uint64, price.nseg).sum(dtype=np.uint64)) == want_q6, "Q6 parity"
     keep = cols["l_shipdate"] <= cutoff
     want_gs = np.bincount(cols["code"][keep], weights=None, minlength=7).astype(np.uint64)
     want_sum = np.zeros(7, dtype=np.int64)
     np.add.at(want_sum, cols["code"][keep], cols["l_quantity"][keep].astype(np.int64))
     assert np.array_equal(d_gcnt.download(np.uint64, 7), want_gs), "grouped COUNT parity"
     assert np.array_equal(d_gsum.download(np.uint64, 7), want_sum.view(np.uint64)), "grouped SUM parity"
-    reps = 20
     d_out = ctx.alloc(n * 4 + 64)
 
     def unpack_price_disc():
-        price[0].unpack(price[1], d_out)
-        disc[0].unpack(disc[1], d_out)
+        price.lay.unpack(price.words, d_out)
+        disc.lay.unpack(disc.words, d_out)
 
     def unpack_qty_code():
-        qty[0].unpack(qty[1], d_out)
-        code[0].unpack(code[1], d_out)
+        qty.lay.unpack(qty.words, d_out)
+        code.lay.unpack(code.words, d_out)
 
     ms = {}
     for name, fn in (("q6_on_bitpacking", q6), ("select_chain", selects), ("sum_product_masked", product),
                      ("unpack_price_and_discount", unpack_price_disc),
-                     ("sum_product_unmasked", lambda: price[0].scan_sum_product(price[1], disc[0], disc[1], d_sum)),
+                     ("sum_product_unmasked", lambda: price.lay.scan_sum_product(price.words, disc.lay, disc.words, d_sum)),
                      ("group_sum_masked", grouped), ("unpack_quantity_and_code", unpack_qty_code),
                      ("sum_product_masked_again", product), ("unpack_price_and_discount_again", unpack_price_disc),
                      ("group_sum_masked_again", grouped), ("unpack_quantity_and_code_again", unpack_qty_code)):
-        fn()
-        ctx.timer_start()
-        for _ in range(reps):
-            fn()
-        ms[name] = ctx.timer_stop() / reps
+        ms[name] = timed(ctx, fn)
     product()  # leave the masked results behind and check them once more after the timed loops
     grouped()
-    assert int(d_sum.download(np.uint64, price[2]).sum(dtype=np.uint64)) == want_q6, "Q6 parity (after timing)"
+    assert int(d_sum.download(np.uint64, price.nseg).sum(dtype=np.uint64)) == want_q6, "Q6 parity (after timing)"
     assert np.array_equal(d_gcnt.download(np.uint64, 7), want_gs), "grouped COUNT parity (after timing)"
     prod = min(ms["sum_product_masked"], ms["sum_product_masked_again"])
     dec = min(ms["unpack_price_and_discount"], ms["unpack_price_and_discount_again"])
     grp = min(ms["group_sum_masked"], ms["group_sum_masked_again"])
     dec2 = min(ms["unpack_quantity_and_code"], ms["unpack_quantity_and_code_again"])
-    two = packed_bytes["l_extendedprice"] + packed_bytes["l_discount"]
-    out = {"rows": n, "selected_rows": int(m.sum()), "q1_selected_rows": int(keep.sum()), "columns": info,
-           "packed_bytes": packed_bytes, "step_ms": ms,
+    two = price.nbytes + disc.nbytes
+    out = {"rows": n, "selected_rows": int(m.sum()), "q1_selected_rows": int(keep.sum()),
+           "columns": {k: e.info for k, e in enc.items()},
+           "packed_bytes": {k: e.nbytes for k, e in enc.items()}, "step_ms": ms,
            "sum_product_masked_ms": prod, "unpack_price_and_discount_ms": dec, "sum_product_over_decode": prod / dec,
            "group_sum_masked_ms": grp, "unpack_quantity_and_code_ms": dec2, "group_sum_over_decode": grp / dec2,
            "sum_product_packed_read_GBps": (two + n / 8) / (prod * 1e-3) / 1e9,
@@ -745,97 +738,6 @@ def q6_bitpacking(adac, n=59_986_052):
     return out
 
 
-def group_product_form_groups(descs_a, descs_b, descs_k, ngroups, a_type=(4, True), b_type=(4, True), k_size=1):
-    """Which form of adac_scan_group_sum_product takes how many scan groups of `a` — group_product_rw_eligible
-    (adac_group_product.inl) evaluated on the host descriptors, with the default grouping of ensure_scan_groups.
-    a_type / b_type: (type size, signed); k_size: the key type's size."""
-    NO_MIN = 0xFFFFFFFFFFFFFFFF
-    tile, per = 16384 // a_type[0], {8: 12, 4: 6, 2: 8, 1: 4}[a_type[0]]
-
-    def frame(d, size, signed):
-        """the widened frame of reference when value = field + frame for every field (product_frame), else None"""
-        tb = 8 * size
-        tmask, sbit = (1 << tb) - 1, (1 << (tb - 1)) if signed else 0
-        if (int(d["flags"]) & 1) and int(d["min"]) != NO_MIN:
-            bmin = (int(d["min"]) & tmask) ^ sbit
-            return bmin - sbit if bmin + (1 << int(d["width"])) - 1 <= tmask else None
-        return 0 if sbit == 0 else None
-
-    def keys_ok(d):
-        wk, kmask = int(d["width"]), (1 << (8 * k_size)) - 1
-        if wk > 8:
-            return False
-        kadd = (int(d["min"]) & kmask) if (int(d["flags"]) & 1) and int(d["min"]) != NO_MIN else 0
-        top = kadd + (1 << wk) - 1
-        return top <= kmask and (top <= 255 or kadd >= ngroups)
-
-    out = {"fast": 0, "generic": 0}
-    for da, db, dk in zip(descs_a, descs_b, descs_k):
-        ntiles = (int(da["count"]) + tile - 1) // tile
-        if ntiles == 0:
-            continue
-        wa, wb = int(da["width"]), int(db["width"])
-        fast = (ngroups + 1 <= 8 and 4 <= wa <= 32 and 1 <= wb <= 32 and int(da["count"]) * wa < 2 ** 31
-                and int(db["count"]) * wb < 2 ** 31)
-        if fast:
-            ma, mb = frame(da, *a_type), frame(db, *b_type)
-            fast = (ma is not None and mb is not None and 0 <= ma and ma + (1 << wa) - 1 < 2 ** 32
-                    and 0 <= mb and mb + (1 << wb) - 1 < 2 ** 32 and keys_ok(dk))
-        out["fast" if fast else "generic"] += (ntiles + per - 1) // per
-    return out
-
-
-def group_product3_form_groups(descs_a, descs_b, descs_c, descs_k, ngroups, a_type=(4, True), b_type=(4, True),
-                               c_type=(4, True), k_size=1):
-    """Which form of adac_scan_group_sum_product3 takes how many scan groups of `a` — group_product3_rw_eligible
-    (adac_group_product3.inl) evaluated on the host descriptors: group_product_rw_eligible on (a, b, keys), and for c
-    what holds for b (1 <= wc <= 32, below 2^31 bits, value = field + frame with 0 <= frame and frame + 2^wc - 1 < 2^32).
-    a_type / b_type / c_type: (type size, signed); k_size: the key type's size."""
-    NO_MIN = 0xFFFFFFFFFFFFFFFF
-
-    def c_ok(d):
-        wc, tb = int(d["width"]), 8 * c_type[0]
-        if not (1 <= wc <= 32 and int(d["count"]) * wc < 2 ** 31):
-            return False
-        tmask, sbit = (1 << tb) - 1, (1 << (tb - 1)) if c_type[1] else 0
-        if (int(d["flags"]) & 1) and int(d["min"]) != NO_MIN:
-            bmin = (int(d["min"]) & tmask) ^ sbit
-            if bmin + (1 << wc) - 1 > tmask:
-                return False
-            mc = bmin - sbit
-        elif sbit == 0:
-            mc = 0
-        else:
-            return False
-        return 0 <= mc and mc + (1 << wc) - 1 < 2 ** 32
-
-    out = {"fast": 0, "generic": 0}
-    for da, db, dc, dk in zip(descs_a, descs_b, descs_c, descs_k):
-        one = group_product_form_groups([da], [db], [dk], ngroups, a_type, b_type, k_size)
-        if one["fast"] and not c_ok(dc):
-            one = {"fast": 0, "generic": one["fast"]}
-        out["fast"] += one["fast"]
-        out["generic"] += one["generic"]
-    return out
-
-
-def group_q1_form_groups(descs_a, descs_b, descs_c, descs_q, descs_k, ngroups, a_type=(4, True), b_type=(4, True),
-                         c_type=(4, True), q_type=(4, True), k_size=1):
-    """Which form of adac_scan_group_sum_q1 takes how many scan groups of `a` — group_q1_rw_eligible
-    (adac_group_q1.inl) evaluated on the host descriptors: group_product3_rw_eligible on (a, b, c, keys), and for q what
-    holds for c.  a_type / b_type / c_type / q_type: (type size, signed); k_size: the key type's size."""
-    out = {"fast": 0, "generic": 0}
-    for da, db, dc, dq, dk in zip(descs_a, descs_b, descs_c, descs_q, descs_k):
-        one = group_product3_form_groups([da], [db], [dc], [dk], ngroups, a_type, b_type, c_type, k_size)
-        # the condition on q is the one on c: the same rule with q in c's place, every other side already decided
-        if one["fast"] and not group_product3_form_groups([da], [db], [dq], [dk], ngroups, a_type, b_type, q_type,
-                                                          k_size)["fast"]:
-            one = {"fast": 0, "generic": one["fast"]}
-        out["fast"] += one["fast"]
-        out["generic"] += one["generic"]
-    return out
-
-
 def q1_disc_price_packed(adac, n=59_986_052):
     """Q1's sum_disc_price on packed columns: the columns of q1_filtered_packed that this plan reads (flag code,
     l_extendedprice, l_shipdate; same shapes, a random stream of its own) plus an int32 l_discount in [0, 10].  One
@@ -845,34 +747,19 @@ def q1_disc_price_packed(adac, n=59_986_052):
     process: what a caller paid before (adac_unpack of the three columns, after which the multiply and the group-by are
     still to do) and a lower bound for any walk of these columns (the grouped SUM of price + the masked SUM of disc)."""
     ctx = adac.Context(0)
-    rng = np.random.default_rng(1993)
-    code = rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8)
-    price = rng.integers(90_000, 10_495_000, size=n).astype(np.int32)
-    shipdate = rng.integers(8036, 10562, size=n).astype(np.int32)
-    disc = rng.integers(0, 11, size=n).astype(np.int32)
-    cutoff = 10511
+    code, price, shipdate, disc = lineitem(np.random.default_rng(1993), n,
+                                           ("code", "l_extendedprice", "l_shipdate", "l_discount")).values()
+    cutoff = Q1_CUTOFF_DAY
     counts = adac.appender_segment_counts(n, 4)
-
-    def enc_col(v):
-        lay = adac.Layout(ctx, v.dtype, counts)
-        d_vals = ctx.upload(v)
-        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
-        lay.encode(d_vals, d_words)
-        ctx.sync()
-        descs = lay.get_descs()
-        nbytes = int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
-        return lay, d_words, nbytes, sorted(set(descs["width"].tolist())), descs
-
-    klay, kwords, kbytes, kwidths, kdescs = enc_col(code)
-    dlay, dwords, dbytes, dwidths, _ = enc_col(shipdate)
-    play, pwords, pbytes, pwidths, pdescs = enc_col(price)
-    clay, cwords, cbytes, cwidths, cdescs = enc_col(disc)
+    klay, kwords, kbytes, kwidths, kdescs = encode_column(adac, ctx, code, counts)
+    dlay, dwords, dbytes, dwidths, _ = encode_column(adac, ctx, shipdate, counts)
+    play, pwords, pbytes, pwidths, pdescs = encode_column(adac, ctx, price, counts)
+    clay, cwords, cbytes, cwidths, cdescs = encode_column(adac, ctx, disc, counts)
     nw = (n + 63) // 64
     d_filter = ctx.alloc(nw * 8 + 8)
     d_selcnt = ctx.alloc(len(counts) * 8)
     d_seg = ctx.alloc(len(counts) * 8)
-    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
-    select = lambda: dlay.scan_select_between(dwords, int_min, cutoff, d_filter, d_selcnt)
+    select = lambda: dlay.scan_select_between(dwords, INT32_MIN_BITS, cutoff, d_filter, d_selcnt)
     d_sp, d_cp = ctx.alloc(7 * 8), ctx.alloc(7 * 8)    # SUM(price), COUNT(*)
     d_spd, d_cpd = ctx.alloc(7 * 8), ctx.alloc(7 * 8)  # SUM(price * disc), COUNT(*)
     sum_price = lambda: play.scan_group_sum_valid(pwords, klay, kwords, d_filter, 6, d_sp, d_cp)
@@ -906,7 +793,6 @@ def q1_disc_price_packed(adac, n=59_986_052):
     # every step is timed warm: 20 back-to-back repetitions after one untimed call.  The new call's working set (packed
     # bytes of three columns + the mask, about 240 MB) can stay in the 256 MB Infinity Cache between repetitions, the
     # unpacks' (the same packed bytes + 540 MB of output) cannot: the comparison favours the new call to that extent
-    reps = 20
     d_out = ctx.alloc(n * 4 + 64)
 
     def unpack_three():
@@ -933,11 +819,7 @@ def q1_disc_price_packed(adac, n=59_986_052):
                      ("group_sum_product_masked_staged_kernel_only", staged_only),
                      ("unpack_price_discount_and_code", unpack_three),
                      ("group_sum_price_plus_masked_sum_disc", lower_bound)):
-        fn()
-        ctx.timer_start()
-        for _ in range(reps):
-            fn()
-        ms[name] = ctx.timer_stop() / reps
+        ms[name] = timed(ctx, fn)
     plan()  # leave the plan's results behind and check them once more after the timed loops
     parity("Q1 sum_disc_price parity (after timing)")
     three = pbytes + cbytes + kbytes
@@ -963,91 +845,27 @@ def q1_full_packed(adac, n=59_986_052):
     """All of Q1 on packed columns: q1_disc_price_packed's columns (same shapes, a random stream of its own) plus
     l_quantity (1 .. 50) and an int32 l_tax in [0, 8].  One adac_scan_select_between (l_shipdate <= cutoff) writes the
     bitmap; under it three adac_scan_group_sum_valid (quantity, price, discount), two adac_scan_group_sum_product
-    ((price, disc), (price, tax)) and one adac_scan_group_sum_product3 (price, disc, tax).  In integer decimals
-      sum_disc_price = 100 SUM(p) - SUM(p d)
-      sum_charge     = 10000 SUM(p) + 100 SUM(p t) - 100 SUM(p d) - SUM(p d t)
-    and the three averages are exact (sum, count) pairs.  Every output column is checked against numpy over the kept rows
+    ((price, disc), (price, tax)) and one adac_scan_group_sum_product3 (price, disc, tax); q1_outputs makes the eight
+    output columns of them.  Every output column is checked against numpy over the kept rows
     before anything is timed.  Timed: every step and the whole plan, warm and INTERLEAVED (one repetition of every step
     per round, so no step has the clock or the cache state of a run of its own), the new call masked / unmasked / with
     its knob at 0, and what a caller paid before: adac_unpack of the four columns the new call reads."""
     ctx = adac.Context(0)
-    rng = np.random.default_rng(1995)
-    code = rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8)
-    price = rng.integers(90_000, 10_495_000, size=n).astype(np.int32)
-    shipdate = rng.integers(8036, 10562, size=n).astype(np.int32)
-    qty = rng.integers(1, 51, size=n).astype(np.int32)
-    disc = rng.integers(0, 11, size=n).astype(np.int32)
-    tax = rng.integers(0, 9, size=n).astype(np.int32)
-    cutoff = 10511
-    counts = adac.appender_segment_counts(n, 4)
-
-    def enc_col(v):
-        lay = adac.Layout(ctx, v.dtype, counts)
-        d_vals = ctx.upload(v)
-        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
-        lay.encode(d_vals, d_words)
-        ctx.sync()
-        d_vals.free()
-        descs = lay.get_descs()
-        nbytes = int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
-        return lay, d_words, nbytes, sorted(set(descs["width"].tolist())), descs
-
-    cols = {"code": enc_col(code), "l_shipdate": enc_col(shipdate), "l_quantity": enc_col(qty),
-            "l_extendedprice": enc_col(price), "l_discount": enc_col(disc), "l_tax": enc_col(tax)}
-    klay, kwords = cols["code"][:2]
-    dlay, dwords = cols["l_shipdate"][:2]
-    qlay, qwords = cols["l_quantity"][:2]
-    play, pwords = cols["l_extendedprice"][:2]
-    clay, cwords = cols["l_discount"][:2]
-    tlay, twords = cols["l_tax"][:2]
-    d_filter = ctx.alloc((n + 63) // 64 * 8 + 8)
-    d_selcnt = ctx.alloc(len(counts) * 8)
-    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
-    res = {k: (ctx.alloc(7 * 8), ctx.alloc(7 * 8)) for k in ("q", "p", "d", "pd", "pt", "pdt")}
-    select = lambda: dlay.scan_select_between(dwords, int_min, cutoff, d_filter, d_selcnt)
-    sum_q = lambda: qlay.scan_group_sum_valid(qwords, klay, kwords, d_filter, 6, *res["q"])
-    sum_p = lambda: play.scan_group_sum_valid(pwords, klay, kwords, d_filter, 6, *res["p"])
-    sum_d = lambda: clay.scan_group_sum_valid(cwords, klay, kwords, d_filter, 6, *res["d"])
-    sum_pd = lambda: play.scan_group_sum_product(pwords, clay, cwords, klay, kwords, 6, res["pd"][0], None, d_filter)
-    sum_pt = lambda: play.scan_group_sum_product(pwords, tlay, twords, klay, kwords, 6, res["pt"][0], None, d_filter)
-
-    def sum_pdt(mask=True, with_counts=False):
-        play.scan_group_sum_product3(pwords, clay, cwords, tlay, twords, klay, kwords, 6, res["pdt"][0],
-                                     res["pdt"][1] if with_counts else None, d_filter if mask else None)
-
-    steps = (select, sum_q, sum_p, sum_d, sum_pd, sum_pt, sum_pdt)
+    t = q1_setup(adac, ctx, n)
+    enc, res, sum_pdt = t.enc, t.res, t.sum_pdt
+    play = enc["l_extendedprice"].lay
+    steps = (t.select,) + tuple(fn for _, fn in t.six)
 
     def plan():
         for f in steps:
             f()
 
-    keep = shipdate <= cutoff
-    bins = [(code == g) & keep for g in range(6)]
-    p64, d64, t64 = price.astype(np.int64), disc.astype(np.int64), tax.astype(np.int64)
-    exp = {"sum_qty": [int(qty[b].sum(dtype=np.int64)) for b in bins],
-           "sum_base_price": [int(p64[b].sum()) for b in bins],
-           "sum_disc_price": [int((p64[b] * (100 - d64[b])).sum()) for b in bins],
-           "sum_charge": [int((p64[b] * (100 - d64[b]) * (100 + t64[b])).sum()) for b in bins],
-           "avg_qty": [(int(qty[b].sum(dtype=np.int64)), int(b.sum())) for b in bins],
-           "avg_price": [(int(p64[b].sum()), int(b.sum())) for b in bins],
-           "avg_disc": [(int(d64[b].sum()), int(b.sum())) for b in bins],
-           "count_order": [int(b.sum()) for b in bins]}
+    exp = q1_expected(t.cols, t.kept_bins)
 
     def outputs():
-        """Q1's eight output columns per group, as integers, from the six results"""
         ctx.sync()
-        s = {k: v[0].download(np.uint64, 7).tolist() for k, v in res.items()}
-        c = {k: res[k][1].download(np.uint64, 7).tolist() for k in ("q", "p", "d")}
-        assert all(s[k][6] == 0 for k in s) and all(c[k][6] == 0 for k in c), "no row has a key >= 6"
-        g6 = range(6)
-        return {"sum_qty": [s["q"][g] for g in g6],
-                "sum_base_price": [s["p"][g] for g in g6],
-                "sum_disc_price": [100 * s["p"][g] - s["pd"][g] for g in g6],
-                "sum_charge": [10000 * s["p"][g] + 100 * s["pt"][g] - 100 * s["pd"][g] - s["pdt"][g] for g in g6],
-                "avg_qty": [(s["q"][g], c["q"][g]) for g in g6],
-                "avg_price": [(s["p"][g], c["p"][g]) for g in g6],
-                "avg_disc": [(s["d"][g], c["d"][g]) for g in g6],
-                "count_order": [c["p"][g] for g in g6]}
+        return q1_outputs({k: v[0].download(np.uint64, 7).tolist() for k, v in res.items()},
+                          {k: res[k][1].download(np.uint64, 7).tolist() for k in ("q", "p", "d")})
 
     def parity(what):
         got = outputs()
@@ -1056,73 +874,57 @@ def q1_full_packed(adac, n=59_986_052):
 
     plan()
     parity("Q1 parity")
-    forms = group_product3_form_groups(cols["l_extendedprice"][4], cols["l_discount"][4], cols["l_tax"][4],
-                                       cols["code"][4], 6)
-    exp_pdt = [int((p64[b] * d64[b] * t64[b]).sum()) for b in bins] + [0]
+    form_groups = group_product3_form_groups(enc["l_extendedprice"].descs, enc["l_discount"].descs, enc["l_tax"].descs,
+                                             enc["code"].descs, 6)
+    p64, d64, t64 = (t.cols[k].astype(np.int64) for k in ("l_extendedprice", "l_discount", "l_tax"))
+    exp_pdt = [int((p64[b] * d64[b] * t64[b]).sum()) for b in t.kept_bins] + [0]
     for knob in (0, 1):  # both forms; with counts; the hand-over against the mirror
         adac.set_tuning("group_product3_rw", knob)
         sum_pdt(with_counts=True)
         ctx.sync()
         assert res["pdt"][0].download(np.uint64, 7).tolist() == exp_pdt, ("SUM(p d t)", knob)
         assert res["pdt"][1].download(np.uint64, 7).tolist() == exp["count_order"] + [0], ("COUNT", knob)
-        assert play.debug_group_handover() == (forms["generic"] if knob else 0), ("hand-over", knob)
+        assert play.debug_group_handover() == (form_groups["generic"] if knob else 0), ("hand-over", knob)
     sum_pdt(mask=False, with_counts=True)
     ctx.sync()
-    allrows = [code == g for g in range(6)]
-    assert res["pdt"][0].download(np.uint64, 7).tolist() == [int((p64[b] * d64[b] * t64[b]).sum()) for b in allrows] + [0]
-    assert res["pdt"][1].download(np.uint64, 7).tolist() == [int(b.sum()) for b in allrows] + [0], "unmasked parity"
+    assert res["pdt"][0].download(np.uint64, 7).tolist() == [int((p64[b] * d64[b] * t64[b]).sum()) for b in t.all_bins] + [0]
+    assert res["pdt"][1].download(np.uint64, 7).tolist() == [int(b.sum()) for b in t.all_bins] + [0], "unmasked parity"
     d_out = ctx.alloc(n * 4 + 64)
+    read = ("l_extendedprice", "l_discount", "l_tax", "code")    # what the new call reads
 
     def unpack_four():
-        play.unpack(pwords, d_out)
-        clay.unpack(cwords, d_out)
-        tlay.unpack(twords, d_out)
-        klay.unpack(kwords, d_out)
+        for k in read:
+            enc[k].lay.unpack(enc[k].words, d_out)
 
     def staged_only():
         adac.set_tuning("group_product3_rw", 0)
         sum_pdt()
         adac.set_tuning("group_product3_rw", 1)
 
-    timed = (("q1_full_on_packed", plan), ("select", select), ("group_sum_quantity_masked", sum_q),
-             ("group_sum_price_masked", sum_p), ("group_sum_discount_masked", sum_d),
-             ("group_sum_product_price_disc_masked", sum_pd), ("group_sum_product_price_tax_masked", sum_pt),
-             ("group_sum_product3_masked", sum_pdt),
-             ("group_sum_product3_masked_with_counts", lambda: sum_pdt(with_counts=True)),
-             ("group_sum_product3_unmasked", lambda: sum_pdt(mask=False)),
-             ("group_sum_product3_masked_staged_kernel_only", staged_only),
-             ("unpack_price_discount_tax_and_code", unpack_four))
-    # warm and interleaved: an untimed round, then `rounds` rounds in which every entry runs `inner` times back to back
-    # between two events of its own (one call alone, 0.1 ms, would be timed together with its launch gap); the figure is
-    # the median over the rounds of the time per call.  The scans' working sets (the new call's: packed bytes of four
-    # columns + the mask, about 270 MB) are near the 256 MB Infinity Cache, the unpacks' (the same packed bytes + 780 MB
-    # of output) are far above it: with every entry following a different one, none starts on a cache it warmed alone
-    rounds, inner = 8, 5
-    samples = {name: [] for name, _ in timed}
-    for r in range(rounds + 1):
-        for name, fn in timed:
-            ctx.timer_start()
-            for _ in range(inner):
-                fn()
-            t = ctx.timer_stop() / inner
-            if r:
-                samples[name].append(t)
+    entries = (("q1_full_on_packed", plan), ("select", t.select)) + t.six + (
+        ("group_sum_product3_masked_with_counts", lambda: sum_pdt(with_counts=True)),
+        ("group_sum_product3_unmasked", lambda: sum_pdt(mask=False)),
+        ("group_sum_product3_masked_staged_kernel_only", staged_only),
+        ("unpack_price_discount_tax_and_code", unpack_four))
+    # the scans' working sets (the new call's: packed bytes of four columns + the mask, about 270 MB) are near the 256 MB
+    # Infinity Cache, the unpacks' (the same packed bytes + 780 MB of output) are far above it
+    samples = timed_interleaved(ctx, entries)
     ms = {name: float(np.median(v)) for name, v in samples.items()}
     plan()  # leave the plan's results behind and check them once more after the timed loops
     parity("Q1 parity (after timing)")
-    four = sum(cols[k][2] for k in ("l_extendedprice", "l_discount", "l_tax", "code"))
-    out = {"rows": n, "groups": 6, "cutoff_day": cutoff, "selected_rows": int(keep.sum()),
-           "widths": {k: v[3] for k, v in cols.items()}, "packed_bytes": {k: v[2] for k, v in cols.items()},
-           "rounds": rounds, "calls_per_round": inner, "step_ms": ms,
+    four = sum(enc[k].nbytes for k in read)
+    out = {"rows": n, "groups": 6, "cutoff_day": Q1_CUTOFF_DAY, "selected_rows": int(t.keep.sum()),
+           "widths": {k: e.widths for k, e in enc.items()}, "packed_bytes": {k: e.nbytes for k, e in enc.items()},
+           "rounds": ROUNDS, "calls_per_round": INNER, "step_ms": ms,
            "step_ms_min": {name: float(min(v)) for name, v in samples.items()},
-           "sum_of_steps_ms": sum(ms[name] for name, _ in timed[1:8]),
+           "sum_of_steps_ms": sum(ms[name] for name, _ in entries[1:8]),
            "group_sum_product3_packed_read_GBps": (four + n / 8) / (ms["group_sum_product3_masked"] * 1e-3) / 1e9,
            "unpack_four_columns_total_GBps": (four + n * (4 + 4 + 4 + 1)) / (ms["unpack_price_discount_tax_and_code"] * 1e-3) / 1e9,
            "product3_faster_than_unpack": ms["group_sum_product3_masked"] < ms["unpack_price_discount_tax_and_code"],
            "product3_over_product": ms["group_sum_product3_masked"] / ms["group_sum_product_price_disc_masked"],
            "register_walk_faster_than_staged_only": ms["group_sum_product3_masked"] < ms["group_sum_product3_masked_staged_kernel_only"],
-           "groups_by_form": forms,
-           "q1_output": {k: [list(x) if isinstance(x, tuple) else x for x in v] for k, v in outputs().items()},
+           "groups_by_form": form_groups,
+           "q1_output": q1_json(outputs()),
            "note": "group_sum_product3_masked = adac_scan_group_sum_product3(l_extendedprice, l_discount, l_tax) GROUP BY "
                    "the flag code under the l_shipdate bitmap, without counts; unpack_price_discount_tax_and_code is what a "
                    "caller paid before it could start to multiply and group; q1_full_on_packed = the select + three "
@@ -1136,100 +938,41 @@ def q1_full_packed(adac, n=59_986_052):
 def q1_fused_packed(adac, n=59_986_052):
     """All of Q1's aggregates from ONE scan: q1_full_packed's data (same generator and seed), the same select, and
     adac_scan_group_sum_q1 (price, discount, tax, quantity GROUP BY the flag code under the l_shipdate bitmap) in place of
-    the six grouped calls.  All eight Q1 output columns are built from the one call's seven terms
-      sum_disc_price = 100 SUM(p) - SUM(p d),   sum_charge = 10000 SUM(p) + 100 SUM(p t) - 100 SUM(p d) - SUM(p d t)
+    the six grouped calls.  All eight Q1 output columns are built from the one call's seven terms (q1_outputs)
     and checked against numpy before and after timing; the seven terms are also held against the six calls' results.
     Timed warm and INTERLEAVED as in q1_full_packed (one process, medians over rounds): the select, each of the six
     grouped calls, the fused call masked / unmasked / with its knob at 0, and adac_unpack of the five columns it reads."""
     ctx = adac.Context(0)
-    rng = np.random.default_rng(1995)
-    code = rng.choice(6, size=n, p=[.2466, .2534, .0004, .2500, .2490, .0006]).astype(np.uint8)
-    price = rng.integers(90_000, 10_495_000, size=n).astype(np.int32)
-    shipdate = rng.integers(8036, 10562, size=n).astype(np.int32)
-    qty = rng.integers(1, 51, size=n).astype(np.int32)
-    disc = rng.integers(0, 11, size=n).astype(np.int32)
-    tax = rng.integers(0, 9, size=n).astype(np.int32)
-    cutoff = 10511
-    counts = adac.appender_segment_counts(n, 4)
-
-    def enc_col(v):
-        lay = adac.Layout(ctx, v.dtype, counts)
-        d_vals = ctx.upload(v)
-        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
-        lay.encode(d_vals, d_words)
-        ctx.sync()
-        d_vals.free()
-        descs = lay.get_descs()
-        nbytes = int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum())
-        return lay, d_words, nbytes, sorted(set(descs["width"].tolist())), descs
-
-    cols = {"code": enc_col(code), "l_shipdate": enc_col(shipdate), "l_quantity": enc_col(qty),
-            "l_extendedprice": enc_col(price), "l_discount": enc_col(disc), "l_tax": enc_col(tax)}
-    klay, kwords = cols["code"][:2]
-    dlay, dwords = cols["l_shipdate"][:2]
-    qlay, qwords = cols["l_quantity"][:2]
-    play, pwords = cols["l_extendedprice"][:2]
-    clay, cwords = cols["l_discount"][:2]
-    tlay, twords = cols["l_tax"][:2]
-    d_filter = ctx.alloc((n + 63) // 64 * 8 + 8)
-    d_selcnt = ctx.alloc(len(counts) * 8)
-    int_min = int(np.array([np.iinfo(np.int32).min]).view(np.uint32)[0])
-    res = {k: (ctx.alloc(7 * 8), ctx.alloc(7 * 8)) for k in ("q", "p", "d", "pd", "pt", "pdt")}
+    t = q1_setup(adac, ctx, n)
+    enc, res = t.enc, t.res
+    read = ("l_extendedprice", "l_discount", "l_tax", "l_quantity", "code")    # what the fused call reads
+    (play, pwords), (clay, cwords), (tlay, twords), (qlay, qwords), (klay, kwords) = (enc[k][:2] for k in read)
     d_q1 = ctx.alloc(7 * 7 * 8)
-    select = lambda: dlay.scan_select_between(dwords, int_min, cutoff, d_filter, d_selcnt)
-    sum_q = lambda: qlay.scan_group_sum_valid(qwords, klay, kwords, d_filter, 6, *res["q"])
-    sum_p = lambda: play.scan_group_sum_valid(pwords, klay, kwords, d_filter, 6, *res["p"])
-    sum_d = lambda: clay.scan_group_sum_valid(cwords, klay, kwords, d_filter, 6, *res["d"])
-    sum_pd = lambda: play.scan_group_sum_product(pwords, clay, cwords, klay, kwords, 6, res["pd"][0], None, d_filter)
-    sum_pt = lambda: play.scan_group_sum_product(pwords, tlay, twords, klay, kwords, 6, res["pt"][0], None, d_filter)
-    sum_pdt = lambda: play.scan_group_sum_product3(pwords, clay, cwords, tlay, twords, klay, kwords, 6, res["pdt"][0],
-                                                   None, d_filter)
-    six = (sum_q, sum_p, sum_d, sum_pd, sum_pt, sum_pdt)
 
     def fused(mask=True):
         play.scan_group_sum_q1(pwords, clay, cwords, tlay, twords, qlay, qwords, klay, kwords, 6, d_q1,
-                               d_filter if mask else None)
+                               t.d_filter if mask else None)
 
     def terms():
         ctx.sync()
         return d_q1.download(np.uint64, 49).reshape(7, 7).tolist()
 
-    keep = shipdate <= cutoff
-    p64, d64, t64, q64 = price.astype(np.int64), disc.astype(np.int64), tax.astype(np.int64), qty.astype(np.int64)
-
-    def expected(bins):
-        rows = [int(b.sum()) for b in bins]
-        sq, sp, sd = ([int(v[b].sum()) for b in bins] for v in (q64, p64, d64))
-        return {"sum_qty": sq, "sum_base_price": sp,
-                "sum_disc_price": [int((p64[b] * (100 - d64[b])).sum()) for b in bins],
-                "sum_charge": [int((p64[b] * (100 - d64[b]) * (100 + t64[b])).sum()) for b in bins],
-                "avg_qty": list(zip(sq, rows)), "avg_price": list(zip(sp, rows)), "avg_disc": list(zip(sd, rows)),
-                "count_order": rows}
-
     def outputs():
-        """Q1's eight output columns per group, as integers, from the one call's seven terms"""
-        t = terms()
-        assert all(row[6] == 0 for row in t), "no row has a key >= 6"
-        cnt, sq, sp, sd, spd, spt, spdt = (t[i] for i in (adac.Q1_COUNT, adac.Q1_SUM_Q, adac.Q1_SUM_A, adac.Q1_SUM_B,
-                                                          adac.Q1_SUM_AB, adac.Q1_SUM_AC, adac.Q1_SUM_ABC))
-        g6 = range(6)
-        return {"sum_qty": [sq[g] for g in g6], "sum_base_price": [sp[g] for g in g6],
-                "sum_disc_price": [100 * sp[g] - spd[g] for g in g6],
-                "sum_charge": [10000 * sp[g] + 100 * spt[g] - 100 * spd[g] - spdt[g] for g in g6],
-                "avg_qty": [(sq[g], cnt[g]) for g in g6], "avg_price": [(sp[g], cnt[g]) for g in g6],
-                "avg_disc": [(sd[g], cnt[g]) for g in g6], "count_order": [cnt[g] for g in g6]}
+        tm = terms()
+        cnt = tm[adac.Q1_COUNT]
+        return q1_outputs({"q": tm[adac.Q1_SUM_Q], "p": tm[adac.Q1_SUM_A], "d": tm[adac.Q1_SUM_B], "pd": tm[adac.Q1_SUM_AB],
+                           "pt": tm[adac.Q1_SUM_AC], "pdt": tm[adac.Q1_SUM_ABC]}, {"q": cnt, "p": cnt, "d": cnt})
 
     def parity(what, exp):
         got = outputs()
         for name, want in exp.items():
             assert got[name] == want, (what, name)
 
-    exp_masked = expected([(code == g) & keep for g in range(6)])
-    exp_all = expected([code == g for g in range(6)])
-    forms = group_q1_form_groups(cols["l_extendedprice"][4], cols["l_discount"][4], cols["l_tax"][4],
-                                 cols["l_quantity"][4], cols["code"][4], 6)
-    select()
-    for f in six:
+    exp_masked = q1_expected(t.cols, t.kept_bins)
+    exp_all = q1_expected(t.cols, t.all_bins)
+    form_groups = group_q1_form_groups(*(enc[k].descs for k in read), 6)
+    t.select()
+    for _, f in t.six:
         f()
     ctx.sync()
     s6 = {k: v[0].download(np.uint64, 7).tolist() for k, v in res.items()}
@@ -1239,48 +982,32 @@ def q1_fused_packed(adac, n=59_986_052):
         fused()
         parity(("Q1 parity", knob), exp_masked)
         assert terms() == [c6, s6["q"], s6["p"], s6["d"], s6["pd"], s6["pt"], s6["pdt"]], ("the six calls", knob)
-        assert play.debug_group_handover() == (forms["generic"] if knob else 0), ("hand-over", knob)
+        assert play.debug_group_handover() == (form_groups["generic"] if knob else 0), ("hand-over", knob)
     fused(mask=False)
     parity("Q1 parity, unmasked", exp_all)
     d_out = ctx.alloc(n * 4 + 64)
 
     def unpack_five():
-        play.unpack(pwords, d_out)
-        clay.unpack(cwords, d_out)
-        tlay.unpack(twords, d_out)
-        qlay.unpack(qwords, d_out)
-        klay.unpack(kwords, d_out)
+        for k in read:
+            enc[k].lay.unpack(enc[k].words, d_out)
 
     def staged_only():
         adac.set_tuning("group_q1_rw", 0)
         fused()
         adac.set_tuning("group_q1_rw", 1)
 
-    six_names = ("group_sum_quantity_masked", "group_sum_price_masked", "group_sum_discount_masked",
-                 "group_sum_product_price_disc_masked", "group_sum_product_price_tax_masked", "group_sum_product3_masked")
-    timed = (("select", select),) + tuple(zip(six_names, six)) + (
+    entries = (("select", t.select),) + t.six + (
         ("group_sum_q1_masked", fused), ("group_sum_q1_unmasked", lambda: fused(mask=False)),
         ("group_sum_q1_masked_staged_kernel_only", staged_only), ("unpack_price_discount_tax_quantity_and_code", unpack_five))
-    # warm and interleaved, as in q1_full_packed: an untimed round, then `rounds` rounds in which every entry runs `inner`
-    # times back to back between two events of its own; the figure is the median over the rounds of the time per call
-    rounds, inner = 8, 5
-    samples = {name: [] for name, _ in timed}
-    for r in range(rounds + 1):
-        for name, fn in timed:
-            ctx.timer_start()
-            for _ in range(inner):
-                fn()
-            t = ctx.timer_stop() / inner
-            if r:
-                samples[name].append(t)
+    samples = timed_interleaved(ctx, entries)
     ms = {name: float(np.median(v)) for name, v in samples.items()}
     fused()  # leave the masked result behind and check it once more after the timed loops
     parity("Q1 parity (after timing)", exp_masked)
-    five = sum(cols[k][2] for k in ("l_extendedprice", "l_discount", "l_tax", "l_quantity", "code"))
-    six_ms = sum(ms[name] for name in six_names)
-    out = {"rows": n, "groups": 6, "cutoff_day": cutoff, "selected_rows": int(keep.sum()),
-           "widths": {k: v[3] for k, v in cols.items()}, "packed_bytes": {k: v[2] for k, v in cols.items()},
-           "rounds": rounds, "calls_per_round": inner, "step_ms": ms,
+    five = sum(enc[k].nbytes for k in read)
+    six_ms = sum(ms[name] for name, _ in t.six)
+    out = {"rows": n, "groups": 6, "cutoff_day": Q1_CUTOFF_DAY, "selected_rows": int(t.keep.sum()),
+           "widths": {k: e.widths for k, e in enc.items()}, "packed_bytes": {k: e.nbytes for k, e in enc.items()},
+           "rounds": ROUNDS, "calls_per_round": INNER, "step_ms": ms,
            "step_ms_min": {name: float(min(v)) for name, v in samples.items()},
            "six_grouped_calls_ms": six_ms,
            "fused_over_six_calls": ms["group_sum_q1_masked"] / six_ms,
@@ -1288,8 +1015,8 @@ def q1_fused_packed(adac, n=59_986_052):
            "group_sum_q1_packed_read_GBps": (five + n / 8) / (ms["group_sum_q1_masked"] * 1e-3) / 1e9,
            "fused_over_unpack_five_columns": ms["group_sum_q1_masked"] / ms["unpack_price_discount_tax_quantity_and_code"],
            "register_walk_faster_than_staged_only": ms["group_sum_q1_masked"] < ms["group_sum_q1_masked_staged_kernel_only"],
-           "groups_by_form": forms,
-           "q1_output": {k: [list(x) if isinstance(x, tuple) else x for x in v] for k, v in outputs().items()},
+           "groups_by_form": form_groups,
+           "q1_output": q1_json(outputs()),
            "note": "group_sum_q1_masked = adac_scan_group_sum_q1(l_extendedprice, l_discount, l_tax, l_quantity) GROUP BY the "
                    "flag code under the l_shipdate bitmap: the seven terms all eight Q1 output columns are made of; "
                    "six_grouped_calls_ms = the sum of the medians of the six grouped calls it replaces; all figures are "
@@ -1310,11 +1037,7 @@ def c1_lookups(adac, wl, n=10_000_000, nlookups=10_000):
     ctx = adac.Context(0)
     vals = np.arange(n, dtype=np.uint32)
     counts = adac.appender_segment_counts(n, 4)
-    lay = adac.Layout(ctx, np.uint32, counts)
-    d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
-    lay.encode(ctx.upload(vals), d_words)
-    ctx.sync()
-    descs = lay.get_descs()
+    lay, d_words, nbytes, _, descs = encode_column(adac, ctx, vals, counts)
     keys = (wl.zipf_column(nlookups, np.uint32, domain=n, skew=1.0, seed=42, threads=1).astype(np.int64) - 1) % n
     d_cnt = ctx.alloc(len(counts) * 8)
     lay.scan_count_eq(d_words, int(keys[0]), d_cnt)
@@ -1331,7 +1054,7 @@ def c1_lookups(adac, wl, n=10_000_000, nlookups=10_000):
         lay.scan_count_eq(d_words, int(k), d_cnt)
     dev_ms = ctx.timer_stop() / 2000
     out = {"rows": n, "segments": int(len(counts)), "max_width": int(descs["width"].max()),
-           "packed_bytes": int(((descs["count"].astype(np.uint64) * descs["width"] + 63) // 64 * 8).sum()),
+           "packed_bytes": nbytes,
            "lookups": nlookups, "lookups_per_s_wall": nlookups / wall, "device_us_per_lookup": dev_ms * 1e3,
            "note": "one fused COUNT(== k) launch per look-up, results stay on the device; wall = Python loop included"}
     ctx.close()

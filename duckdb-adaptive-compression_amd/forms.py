@@ -1,0 +1,92 @@
+"""Host mirror of the device rule "which kernel form takes this scan group" (no device code, no library).
+
+The product scans choose per scan group of `a` between a register walk ("fast") and a staged kernel ("generic").
+The rule is product_fast_eligible (csrc/adac_sum_product.inl), group_product_rw_eligible (csrc/adac_group_product.inl)
+and group_product3_rw_eligible / group_q1_rw_eligible, which chain onto it.  Read as one rule over N value columns, a
+scan group is fast when
+  * 4 <= w_a <= 32, and 1 <= w <= 32 for every other value column;
+  * count * w < 2^31 bits for every value column;
+  * value = field + frame holds for every field of every value column (frame());
+  * grouped forms only: ngroups + 1 <= 8; 0 <= frame and frame + 2^w - 1 < 2^32 for every value column; and the key
+    column passes keys_ok().
+Descriptors are rows of SEGMENT_DESC_DTYPE (Layout.get_descs()); a type is (size in bytes, signed).  Every function
+returns {"fast": scan groups of a, "generic": scan groups of a} with the default grouping of ensure_scan_groups.
+"""
+from itertools import repeat
+
+NO_MIN = 0xFFFFFFFFFFFFFFFF
+TILE_BYTES = 16384
+TILES_PER_SCAN_GROUP = {8: 12, 4: 6, 2: 8, 1: 4}   # by the type size of a
+
+
+def has_min(d):
+    return bool(int(d["flags"]) & 1) and int(d["min"]) != NO_MIN
+
+
+def frame(d, size, signed):
+    """product_frame: the widened frame of reference when value = field + frame for every field, else None"""
+    tb = 8 * size
+    tmask, sbit = (1 << tb) - 1, (1 << (tb - 1)) if signed else 0
+    if has_min(d):
+        bmin = (int(d["min"]) & tmask) ^ sbit
+        return bmin - sbit if bmin + (1 << int(d["width"])) - 1 <= tmask else None
+    return 0 if sbit == 0 else None
+
+
+def value_ok(d, kind, min_width, grouped):
+    """One value column's side of the rule; min_width is 4 for a and 1 for the others."""
+    w = int(d["width"])
+    if not (min_width <= w <= 32 and int(d["count"]) * w < 2 ** 31):
+        return False
+    m = frame(d, *kind)
+    return m is not None and (not grouped or (0 <= m and m + (1 << w) - 1 < 2 ** 32))
+
+
+def keys_ok(d, k_size, ngroups):
+    """The key side of group_product_rw_eligible: at most 8 bits, the keys do not wrap in their type, and all keys of
+    the segment fit a byte or all of them are >= ngroups."""
+    wk, kmask = int(d["width"]), (1 << (8 * k_size)) - 1
+    if wk > 8:
+        return False
+    kadd = (int(d["min"]) & kmask) if has_min(d) else 0
+    top = kadd + (1 << wk) - 1
+    return top <= kmask and (top <= 255 or kadd >= ngroups)
+
+
+def form_groups(value_descs, kinds, descs_k=None, ngroups=None, k_size=1):
+    """The rule over the value columns value_descs (a first) of types kinds; grouped when descs_k is given."""
+    grouped = descs_k is not None
+    size_a = kinds[0][0]
+    tile, per = TILE_BYTES // size_a, TILES_PER_SCAN_GROUP[size_a]
+    out = {"fast": 0, "generic": 0}
+    for *ds, dk in zip(*value_descs, descs_k if grouped else repeat(None)):
+        ntiles = (int(ds[0]["count"]) + tile - 1) // tile
+        if ntiles == 0:
+            continue
+        fast = all(value_ok(d, kind, 1 if i else 4, grouped) for i, (d, kind) in enumerate(zip(ds, kinds)))
+        if fast and grouped:
+            fast = ngroups + 1 <= 8 and keys_ok(dk, k_size, ngroups)
+        out["fast" if fast else "generic"] += (ntiles + per - 1) // per
+    return out
+
+
+def product_form_groups(descs_a, descs_b, type_size=4, signed=True):
+    """adac_scan_sum_product (k_scan_product): product_fast_eligible; both columns of one type."""
+    return form_groups((descs_a, descs_b), [(type_size, signed)] * 2)
+
+
+def group_product_form_groups(descs_a, descs_b, descs_k, ngroups, a_type=(4, True), b_type=(4, True), k_size=1):
+    """adac_scan_group_sum_product: group_product_rw_eligible."""
+    return form_groups((descs_a, descs_b), (a_type, b_type), descs_k, ngroups, k_size)
+
+
+def group_product3_form_groups(descs_a, descs_b, descs_c, descs_k, ngroups, a_type=(4, True), b_type=(4, True),
+                               c_type=(4, True), k_size=1):
+    """adac_scan_group_sum_product3: group_product3_rw_eligible (for c what holds for b)."""
+    return form_groups((descs_a, descs_b, descs_c), (a_type, b_type, c_type), descs_k, ngroups, k_size)
+
+
+def group_q1_form_groups(descs_a, descs_b, descs_c, descs_q, descs_k, ngroups, a_type=(4, True), b_type=(4, True),
+                         c_type=(4, True), q_type=(4, True), k_size=1):
+    """adac_scan_group_sum_q1: group_q1_rw_eligible (for q what holds for c)."""
+    return form_groups((descs_a, descs_b, descs_c, descs_q), (a_type, b_type, c_type, q_type), descs_k, ngroups, k_size)

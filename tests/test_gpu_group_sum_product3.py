@@ -8,12 +8,13 @@ product against Python integers), grouped by the key as an unsigned number of it
 (k_group_product3_rw) with the staged kernel (k_group_product3) for what it leaves, and the staged kernel alone under
 group_product3_rw = 0.  Results are poisoned before every call and one word past ngroups + 1 is asserted untouched.
 Which kernel took what is read back after every call (adac_debug_group_handover) and held against the host mirror of
-the eligibility rule (bench_configs.group_product3_form_groups), so the walk cannot quietly hand its work to the staged
+the eligibility rule (forms.group_product3_form_groups), so the walk cannot quietly hand its work to the staged
 kernel."""
+import importlib
+
 import numpy as np
 import pytest
 
-from bench_configs import group_product3_form_groups
 from test_gpu_group_sum import reference_groups
 from test_gpu_group_sum_product import (ALL, COUNTS1, INVALID_ARGUMENT, KEY_CASES, POISON, Col, NullLayout,
                                         column_at_width, mixed_product_column, shared_columns, widen)
@@ -21,6 +22,7 @@ from test_gpu_group_sum_product import reference as reference2
 from test_gpu_group_sum_rw import every_width_column
 from test_gpu_group_sum_valid import clustered, element_mask, make_case, mask_shapes, phase_column
 
+group_product3_form_groups = importlib.import_module("duckdb-adaptive-compression_amd.forms").group_product3_form_groups
 pytestmark = pytest.mark.gpu
 
 # (type of b, type of c): every type of {uint8, int16, int32, uint64} once on either side, never twice in a pair
