@@ -66,13 +66,16 @@ def widen(v):
 class Packed:
     """A column as BITPACKING blocks (host side only): the block buffer, the segment table, what the oracle decodes
     from the blocks and every metadata group's (mode, width).  counts: compress these row ranges as one segment each
-    instead of letting the codec cut the column into blocks."""
+    instead of letting the codec cut the column into blocks.  validity: the NULL mask the column is compressed under
+    (rows that are NULL decode to whatever the codec left there).  phase: segment i starts at element phase + its
+    first row."""
 
-    def __init__(self, v, force_mode=bp.MODE_AUTO, counts=None, out_offs=None):
+    def __init__(self, v, force_mode=bp.MODE_AUTO, counts=None, out_offs=None, validity=None, phase=0):
         v = np.ascontiguousarray(v)
         self.dtype = v.dtype
+        nz = validity is not None
         if counts is None:
-            comp = bp.Compressed(v, force_mode=force_mode)
+            comp = bp.Compressed(v, validity, force_mode, null_zero=nz)
             self.buf, self.offs, self.counts = host_blocks(comp)
             comps = [(comp, i) for i in range(comp.nseg)]
         else:
@@ -83,7 +86,8 @@ class Packed:
             comps, row = [], 0
             for i, c in enumerate(self.counts):
                 if c:
-                    comp = bp.Compressed(v[row:row + int(c)], force_mode=force_mode)
+                    comp = bp.Compressed(v[row:row + int(c)], validity[row:row + int(c)] if nz else None, force_mode,
+                                         null_zero=nz)
                     assert comp.nseg == 1
                     self.buf[i * STRIDE:i * STRIDE + bp.BLOCK_SIZE] = comp.block(0)
                     comps.append((comp, 0))
@@ -92,6 +96,8 @@ class Packed:
                 row += int(c)
         self.segs = [np.zeros(0, self.dtype) if c is None else c.scan(i) for c, i in comps]
         self.nseg = len(self.counts)
+        if out_offs is None and phase:
+            out_offs = phase + np.concatenate([[0], np.cumsum(self.counts[:-1], dtype=np.uint64)]).astype(np.uint64)
         self.out_offs = (np.concatenate([[0], np.cumsum(self.counts[:-1], dtype=np.uint64)]).astype(np.uint64)
                          if out_offs is None else np.asarray(out_offs, dtype=np.uint64))
         self.explicit_offs = out_offs is not None

@@ -76,9 +76,13 @@ class Column:
         self.nwords = (self.span + 63) // 64
 
     @classmethod
-    def from_values(cls, adac, ctx, v, force_mode=bp.MODE_AUTO, out_offs=None):
-        comp = bp.Compressed(v, force_mode=force_mode)
+    def from_values(cls, adac, ctx, v, force_mode=bp.MODE_AUTO, out_offs=None, validity=None, phase=0):
+        """validity: the NULL mask the column is compressed under.  phase: segment i starts at element phase + its
+        first row."""
+        comp = bp.Compressed(v, validity, force_mode, null_zero=validity is not None)
         buf, offs, counts = host_blocks(comp)
+        if out_offs is None and phase:
+            out_offs = phase + np.concatenate([[0], np.cumsum(counts[:-1], dtype=np.uint64)]).astype(np.uint64)
         col = cls(adac, ctx, v.dtype, buf, offs, counts, [comp.scan(i) for i in range(comp.nseg)], out_offs)
         col.comp = comp
         return col
