@@ -738,6 +738,83 @@ def q6_bitpacking(adac, n=59_986_052):
     return out
 
 
+def bitpacking_select_gather(adac, n=59_986_052):
+    """Filter -> project on DuckDB's own BITPACKING blocks: adac_bp_unpack_selected (values only, then values + ids) of
+    l_extendedprice (int32, FOR), the 6-valued uint8 code and a sorted copy of l_partkey (DELTA_FOR) under five bitmaps
+    — Q6's final bitmap from the three chained adac_bp_scan_select_between calls, Q1's l_shipdate <= cutoff, uniform
+    random 10 % and 50 %, one contiguous 10 % run — each interleaved in the same process with adac_bp_unpack of the
+    same column.  The timed calls pass no total_out (they only enqueue); values and ids are checked against numpy
+    before and after the timing."""
+    from oracle import bitpacking as bp
+    ctx = adac.Context(0)
+    rng = np.random.default_rng(1994)
+    cols = lineitem(rng, n, ("l_shipdate", "l_discount", "l_quantity", "l_extendedprice", "code", "l_partkey"))
+    cols["l_partkey_sorted"] = np.sort(cols.pop("l_partkey"))
+    enc = {name: bitpacking_blocks(adac, ctx, bp.Compressed(v), v.dtype) for name, v in cols.items()}
+    nw = (n + 63) // 64
+    bm = [ctx.alloc(nw * 8 + 8) for _ in range(3)]
+    d_q1 = ctx.alloc(nw * 8 + 8)
+    d_cnt = ctx.alloc(max(e.nseg for e in enc.values()) * 8)
+    q6_selects(enc, bm, d_cnt)
+    ship = enc["l_shipdate"]
+    ship.lay.scan_select_between(ship.words, INT32_MIN_BITS, Q1_CUTOFF_DAY, d_q1, d_cnt)
+    ctx.sync()
+    run = np.zeros(n, dtype=bool)
+    run[n // 3:n // 3 + n // 10] = True
+    host_masks = {"q6": q6_mask(cols), "q1": cols["l_shipdate"] <= Q1_CUTOFF_DAY, "uniform_10": rng.random(n) < 0.1,
+                  "uniform_50": rng.random(n) < 0.5, "run_10": run}
+    d_masks = {"q6": bm[2], "q1": d_q1}
+
+    def bits(mask):
+        full = np.zeros(nw * 64, dtype=bool)
+        full[:n] = mask
+        return np.packbits(full, bitorder="little").view(np.uint64)
+
+    for name in ("q6", "q1"):     # the device's bitmaps are the ones numpy expects
+        assert np.array_equal(d_masks[name].download(np.uint64, nw), bits(host_masks[name])), name + " bitmap parity"
+    for name in ("uniform_10", "uniform_50", "run_10"):
+        d_masks[name] = ctx.upload(bits(host_masks[name]))
+    d_out, d_ids, d_dec = ctx.alloc(n * 4 + 64), ctx.alloc(n * 8 + 64), ctx.alloc(n * 4 + 64)
+    cells = {}
+    for cname in ("l_extendedprice", "code", "l_partkey_sorted"):
+        col, v = enc[cname], cols[cname]
+        cells[cname] = {}
+        for mname, mask in host_masks.items():
+            d_mask = d_masks[mname]
+            want_v, want_i = v[mask], np.flatnonzero(mask).astype(np.uint64)
+
+            def parity(when):
+                d_out.zero(), d_ids.zero()
+                total = col.lay.unpack_selected(col.words, d_mask, d_out, d_ids)
+                assert total == len(want_v), "%s / %s: total (%s)" % (cname, mname, when)
+                assert np.array_equal(d_out.download(v.dtype, total), want_v), "%s / %s: values (%s)" % (cname, mname, when)
+                assert np.array_equal(d_ids.download(np.uint64, total), want_i), "%s / %s: ids (%s)" % (cname, mname, when)
+
+            parity("before timing")
+            s = timed_interleaved(ctx, [
+                ("selected", lambda: col.lay.unpack_selected(col.words, d_mask, d_out, None, False)),
+                ("decode", lambda: col.lay.unpack(col.words, d_dec)),
+                ("selected_ids", lambda: col.lay.unpack_selected(col.words, d_mask, d_out, d_ids, False))])
+            parity("after timing")
+            med = {k: float(np.median(x)) for k, x in s.items()}
+            sel = len(want_v)
+            cells[cname][mname] = {
+                "selected_rows": sel, "ms": med["selected"], "ms_with_ids": med["selected_ids"],
+                "decode_ms": med["decode"], "over_decode": med["selected"] / med["decode"],
+                "with_ids_over_decode": med["selected_ids"] / med["decode"], "packed_bytes": col.nbytes,
+                "bytes_written": sel * v.dtype.itemsize, "bytes_written_with_ids": sel * (v.dtype.itemsize + 8),
+                "decode_bytes_written": n * v.dtype.itemsize,
+                "samples_ms": {k: [round(t, 5) for t in x] for k, x in s.items()}}
+            print("bitpacking_select_gather %s / %s: %.4f ms (ids %.4f), decode %.4f" %
+                  (cname, mname, med["selected"], med["selected_ids"], med["decode"]), file=sys.stderr, flush=True)
+    out = {"rows": n, "columns": {k: enc[k].info for k in cells}, "cells": cells,
+           "note": "ms / ms_with_ids = adac_bp_unpack_selected without / with d_out_ids, total_out NULL (enqueue only); "
+                   "decode_ms = adac_bp_unpack of the same column; medians of %d interleaved rounds of %d calls each; "
+                   "the bitmap words read are rows / 8 bytes on top of packed_bytes" % (ROUNDS, INNER)}
+    ctx.close()
+    return out
+
+
 def q1_disc_price_packed(adac, n=59_986_052):
     """Q1's sum_disc_price on packed columns: the columns of q1_filtered_packed that this plan reads (flag code,
     l_extendedprice, l_shipdate; same shapes, a random stream of its own) plus an int32 l_discount in [0, 10].  One
@@ -1072,6 +1149,7 @@ def main():
             "bitpacking_scan": lambda: bitpacking_scan(adac), "q6_packed": lambda: q6_packed(adac),
             "bitpacking_fused_scans": lambda: bitpacking_fused_scans(adac),
             "q6_bitpacking": lambda: q6_bitpacking(adac),
+            "bitpacking_select_gather": lambda: bitpacking_select_gather(adac),
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "q1_filtered_packed": lambda: q1_filtered_packed(adac),
             "q1_disc_price_packed": lambda: q1_disc_price_packed(adac),

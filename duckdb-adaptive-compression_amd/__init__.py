@@ -189,6 +189,7 @@ SIGNATURES = {
     "adac_bp_scan_min_max": (_int, [_vp, _vp, _vp, _vp]),
     "adac_bp_scan_sum_product": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "adac_bp_scan_group_sum": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "adac_bp_unpack_selected": (_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "adac_bp_bind": (_int, [_vp, _vp]),
     "adac_bp_unpack": (_int, [_vp, _vp, _vp]),
     "adac_bp_unpack_range": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64]),
@@ -689,6 +690,16 @@ class BitpackingLayout:
         the rows whose bit is set in d_validity; ngroups + 1 results each, keys >= ngroups in the last."""
         _check(lib().adac_bp_scan_group_sum(self._h, _dptr(d_blocks), keys._h, _dptr(d_key_blocks), _dptr(d_validity),
                                             int(ngroups), _dptr(d_sums), _dptr(d_counts)), "adac_bp_scan_group_sum")
+
+    def unpack_selected(self, d_blocks, d_bitmap, d_out, d_out_ids=None, want_total=True):
+        """Values (and optionally element indices) of the rows whose bitmap bit is set, dense, segment by segment and
+        in row order.  Returns the number of rows written (None when want_total is False: the call then stays
+        asynchronous)."""
+        total = _u64()
+        _check(lib().adac_bp_unpack_selected(self._h, _dptr(d_blocks), _dptr(d_bitmap), _dptr(d_out),
+                                             _dptr(d_out_ids), C.byref(total) if want_total else None),
+               "adac_bp_unpack_selected")
+        return total.value if want_total else None
 
 
 class BitpackingPlan:

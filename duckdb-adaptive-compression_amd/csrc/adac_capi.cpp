@@ -1349,6 +1349,11 @@ struct adac_bp_layout {
 	uint32_t *d_group_seg = nullptr; // segment of every group (the fused scans' results are per segment)
 	uint64_t *d_block_offs = nullptr;
 	const void *bound_blocks = nullptr; // blocks buffer whose group headers are parsed into d_groups
+	// scratch of adac_bp_unpack_selected (allocated on first use): selected rows per metadata group, their exclusive
+	// prefix, block totals + grand total
+	uint32_t *d_group_cnt = nullptr;
+	uint64_t *d_group_off = nullptr;
+	uint64_t *d_block_tot = nullptr;
 };
 
 extern "C" adac_status adac_bp_layout_create(adac_ctx *c, int physical_type, const uint64_t *block_offs,
@@ -1419,6 +1424,9 @@ extern "C" void adac_bp_layout_destroy(adac_bp_layout *l) {
 	if (l->d_groups) (void)hipFree(l->d_groups);
 	if (l->d_group_seg) (void)hipFree(l->d_group_seg);
 	if (l->d_block_offs) (void)hipFree(l->d_block_offs);
+	if (l->d_group_cnt) (void)hipFree(l->d_group_cnt);
+	if (l->d_group_off) (void)hipFree(l->d_group_off);
+	if (l->d_block_tot) (void)hipFree(l->d_block_tot);
 	adac_ctx *c = l->ctx;
 	delete l;
 	ctx_release(c);
@@ -1472,6 +1480,32 @@ extern "C" adac_status adac_bp_fetch_rows(adac_bp_layout *l, const void *d_block
 	if (!d_blocks || !d_segs || !d_rows || !d_out || !aligned16(d_blocks)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	ADAC_HIP(adac::launch_bp_fetch(l->ctx->stream, l->type_size, l->d_block_offs, d_blocks, d_segs, d_rows, n, d_out));
+	return ADAC_OK;
+}
+
+// ---- scan with selection on BITPACKING blocks (adac_bp_select_gather.inl) ----
+
+extern "C" adac_status adac_bp_unpack_selected(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_bitmap,
+                                               void *d_out, uint64_t *d_out_ids, uint64_t *total_out) {
+	if (!l) return ADAC_ERR_INVALID_ARGUMENT;
+	if (l->total_values == 0) { // no rows: nothing is enqueued, no pointer is looked at
+		if (total_out) *total_out = 0;
+		return ADAC_OK;
+	}
+	if (!d_blocks || !aligned16(d_blocks) || !d_bitmap || !d_out) return ADAC_ERR_INVALID_ARGUMENT;
+	if (l->bound_blocks != d_blocks) {
+		adac_status st = adac_bp_bind(l, d_blocks);
+		if (st != ADAC_OK) return st;
+	}
+	ADAC_HIP(hipSetDevice(l->ctx->device));
+	const uint64_t nblocks = (l->ngroups + 1023) / 1024;
+	if (!l->d_group_cnt) ADAC_HIP(hipMalloc((void **)&l->d_group_cnt, l->ngroups * sizeof(uint32_t)));
+	if (!l->d_group_off) ADAC_HIP(hipMalloc((void **)&l->d_group_off, l->ngroups * sizeof(uint64_t)));
+	if (!l->d_block_tot) ADAC_HIP(hipMalloc((void **)&l->d_block_tot, (nblocks + 1) * sizeof(uint64_t)));
+	uint64_t *d_total = l->d_block_tot + nblocks; // the spare slot after the block totals
+	ADAC_HIP(adac::launch_bp_gather_selected(l->ctx->stream, l->type_size, l->d_groups, l->ngroups, d_blocks, d_bitmap,
+	                                         l->d_group_cnt, l->d_group_off, l->d_block_tot, d_out, d_out_ids, d_total));
+	if (total_out) return adac_memcpy_d2h(l->ctx, total_out, d_total, sizeof(uint64_t));
 	return ADAC_OK;
 }
 

@@ -303,5 +303,11 @@ hipError_t launch_bp_scan_pair_sum(hipStream_t s, const BpPairColumn &a, const B
                                    uint64_t *d_sums);
 hipError_t launch_bp_scan_pair_gsum(hipStream_t s, const BpPairColumn &v, const BpPairColumn &k, uint64_t ngroups,
                                     const uint64_t *d_validity, uint32_t nkeys, uint64_t *d_sums, uint64_t *d_counts);
+// scan with selection on the block images (adac_bp_select_gather.inl).  d_group_cnt / d_group_off: ngroups entries of
+// scratch, d_block_tot: ceil(ngroups / 1024) words; *d_total = rows written
+hipError_t launch_bp_gather_selected(hipStream_t s, uint32_t type_size, const void *d_groups, uint64_t ngroups,
+                                     const void *d_blocks, const uint64_t *d_bitmap, uint32_t *d_group_cnt,
+                                     uint64_t *d_group_off, uint64_t *d_block_tot, void *d_out, uint64_t *d_out_ids,
+                                     uint64_t *d_total);
 
 } // namespace adac

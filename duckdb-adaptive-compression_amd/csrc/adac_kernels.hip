@@ -1948,6 +1948,7 @@ hipError_t dispatch_size(uint32_t type_size, F &&f) {
 #include "adac_bitpacking.inl"
 #include "adac_bp_scans.inl"
 #include "adac_bp_pair_scans.inl"
+#include "adac_bp_select_gather.inl"
 #include "adac_select_gather.inl"
 #include "adac_block_image.inl"
 #include "adac_encode_1p.inl"
@@ -2642,6 +2643,41 @@ hipError_t launch_bp_scan_pair_gsum(hipStream_t st, const BpPairColumn &v, const
 	if (d_validity) hipLaunchKernelGGL(k_bp_scan_pair_gsum<true>, grid, dim3(kWorkgroup), 0, st, gv, gk, s);
 	else hipLaunchKernelGGL(k_bp_scan_pair_gsum<false>, grid, dim3(kWorkgroup), 0, st, gv, gk, s);
 	return hipGetLastError();
+}
+
+// Scan with selection on BITPACKING blocks (adac_bp_select_gather.inl): counts per metadata group, the succinct
+// gather's exclusive prefix over them, then the gather in launch_bp_scan's shape (8 workgroups = 32 waves per CU).
+hipError_t launch_bp_gather_selected(hipStream_t s, uint32_t type_size, const void *d_groups, uint64_t ngroups,
+                                     const void *d_blocks, const uint64_t *d_bitmap, uint32_t *d_group_cnt,
+                                     uint64_t *d_group_off, uint64_t *d_block_tot, void *d_out, uint64_t *d_out_ids,
+                                     uint64_t *d_total) {
+	if (ngroups == 0) return hipMemsetAsync(d_total, 0, sizeof(uint64_t), s);
+	constexpr uint64_t kWaves = kWorkgroup / 64;
+	const BpGroup *groups = static_cast<const BpGroup *>(d_groups);
+	hipLaunchKernelGGL(k_bp_group_popc, dim3((unsigned)((ngroups + kWaves - 1) / kWaves)), dim3(kWorkgroup), 0, s, groups,
+	                   (uint32_t)ngroups, d_bitmap, d_group_cnt);
+	const uint64_t nblocks = (ngroups + kScanBlock - 1) / kScanBlock;
+	hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_group_cnt, ngroups, d_group_off,
+	                   d_block_tot);
+	hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(kScanBlock), 0, s, d_block_tot, nblocks, d_total);
+	hipLaunchKernelGGL(k_scan_fixup, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_group_off, ngroups, d_block_tot);
+	const uint64_t cap = device_cus() * 8 * kWaves;
+	BpGatherArgs a;
+	a.ngroups = (uint32_t)ngroups;
+	a.per_wave = (uint32_t)((ngroups + cap - 1) / cap);
+	a.blocks = static_cast<const uint8_t *>(d_blocks);
+	a.bitmap = d_bitmap;
+	a.tmask = type_mask(type_size);
+	a.group_cnt = d_group_cnt;
+	a.group_off = d_group_off;
+	const uint64_t nwaves = (ngroups + a.per_wave - 1) / a.per_wave;
+	const dim3 grid((unsigned)((nwaves + kWaves - 1) / kWaves));
+	return dispatch_size(type_size, [&](auto tag) {
+		using U = decltype(tag);
+		if (d_out_ids) hipLaunchKernelGGL((k_bp_gather<U, true>), grid, dim3(kWorkgroup), 0, s, groups, a, static_cast<U *>(d_out), d_out_ids);
+		else hipLaunchKernelGGL((k_bp_gather<U, false>), grid, dim3(kWorkgroup), 0, s, groups, a, static_cast<U *>(d_out), d_out_ids);
+		return hipGetLastError();
+	});
 }
 
 hipError_t launch_gather_selected(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs,

@@ -608,6 +608,23 @@ adac_status adac_bp_scan_group_sum(adac_bp_layout *values, const void *d_value_b
                                    const void *d_key_blocks, const uint64_t *d_validity, uint32_t ngroups,
                                    uint64_t *d_sums, uint64_t *d_counts);
 
+/* Scan with selection on the block images — adac_unpack_selected for BITPACKING, the scan-with-selection half of
+ * ColumnSegment::FilterSelection (column_segment.cpp:575-844): d_out receives, densely, as values of the layout's
+ * type, the rows whose bit is set in d_bitmap, in group-table order (segment by segment, row order inside a segment);
+ * the bit index is element out_offs[seg] + row, the index space of the adac_bp_scan_* calls' d_validity / d_bitmap
+ * (the result of adac_bp_scan_select_between, or any mask over it).  The values equal what adac_bp_unpack writes at
+ * those elements.  d_out_ids, if not NULL, receives the element indices.  *total_out, if not NULL, is set to the
+ * number of rows written, which makes the call synchronous; with total_out == NULL the call only enqueues on the
+ * context's stream.  d_out (and d_out_ids) must hold at least that many entries — the sum of the select's d_counts,
+ * or total_values in the worst case; nothing is written at or past slot total.  Bits of elements that no segment
+ * covers are ignored and no bitmap word outside ceil(value_span / 64) is read.  A metadata group without a selected
+ * row reads no payload byte, and a CONSTANT, CONSTANT_DELTA or width-0 group reads none either.  Binds like
+ * adac_bp_unpack when handed a buffer the layout is not bound to.  ADAC_ERR_INVALID_ARGUMENT, checked on the host
+ * before anything is enqueued: a NULL layout; while the layout has rows, a NULL d_bitmap or d_out, or a d_blocks that
+ * is NULL or not 16-byte aligned.  A layout without rows sets *total_out = 0 and writes nothing else. */
+adac_status adac_bp_unpack_selected(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_bitmap, void *d_out,
+                                    uint64_t *d_out_ids, uint64_t *total_out);
+
 /* Compress side (BitpackingCompress / BitpackingFinalizeCompress, bitpacking.cpp:514-538): per-group statistics
  * on the device, the mode decision of BitpackingState::Flush (:229-294) and the sequential placement of groups
  * into Storage::BLOCK_SIZE blocks (:453-512) on the host, then one device pass writing every group image.
