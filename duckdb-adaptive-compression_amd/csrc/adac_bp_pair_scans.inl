@@ -1,12 +1,12 @@
 // adac_bp_pair_scans.inl — fused scans over TWO columns of DuckDB BITPACKING blocks walked in step: SUM(a * b) per
 // segment (Q6's aggregate) and SUM(v), COUNT(*) GROUP BY key (Q1's basic shape), under an optional selection bitmap,
-// nothing decoded to HBM.  Included into adac_kernels.hip after adac_bp_scans.inl: the BpGroup table, the mask window
-// of a group, BpScanAcc and the staging scheme of bp_scan_packed are k_bp_scan's.
+// nothing decoded to HBM.  Included into adac_kernels.hip after adac_bp_scans.inl: the wave's run of groups, the mask
+// window of a group, the staging of a piece and the kind dispatch are adac_bp_walk.inl's, BpScanAcc is k_bp_scan's.
 //
-// Work shape (k_bp_scan's): a WAVE walks a run of consecutive metadata groups on its own — no barrier anywhere.  The
-// host has checked that group i of both layouts covers the same rows at the same element offset, so the wave takes
-// group i of both columns; lane l of step k owns row 64 k + l of both, and the mask bits of a step are one 64-bit
-// window in the FIRST layout's element space.
+// Work shape (adac_bp_walk.inl): a WAVE walks a run of consecutive metadata groups on its own.  The host has checked
+// that group i of both layouts covers the same rows at the same element offset, so the wave takes group i of both
+// columns; lane l of step k owns row 64 k + l of both, and the mask bits of a step are one 64-bit window in the FIRST
+// layout's element space.
 //
 // A column is read through a cursor (BpCursor) that yields the lane's value of step k as 64 bits masked to the type's
 // width (the prefix mod 2^64 and then mod 2^bits is the prefix mod 2^bits), so one kernel serves every pair of types:
@@ -26,11 +26,9 @@
 // once.
 
 constexpr uint32_t kBpPairBins = 257; // 256 groups + overflow
-enum : int { kBpCurLinear = 0, kBpCurFor = 1, kBpCurDelta = 2 };
 
 struct BpPairArgs {
-	uint32_t ngroups;  // metadata groups (the same number in both layouts)
-	uint32_t per_wave; // consecutive groups one wave walks
+	BpRun run; // metadata groups: the same number in both layouts
 	const uint8_t *a_blocks, *b_blocks;
 	const uint64_t *validity; // bit e = element out_off + row of the first layout; read only by the <V> kernels
 	uint64_t a_tmask, a_sbit, b_tmask, b_sbit; // all-ones of the type's width; its sign bit, 0 for the unsigned types
@@ -78,33 +76,11 @@ __device__ __forceinline__ int bp_cursor_open(BpCursor &c, const BpGroup &g, con
 	return g.mode == kBpFor ? kBpCurFor : kBpCurDelta;
 }
 
-// Make the piece that holds step k resident (bp_scan_packed's aligned, index-clamped 16-byte loads).
+// Make the piece that holds step k resident.
 __device__ __forceinline__ void bp_cursor_stage(BpCursor &c, uint32_t k /* uniform */, uint32_t lane) {
-	const uint32_t stage_rows = c.w <= 16u ? (uint32_t)kBpGroupRows : ((kBpScanStageBytes * 8u / c.w) & ~63u);
-	const uint32_t r0 = (k * 64u / stage_rows) * stage_rows;
-	const uint32_t r1 = r0 + stage_rows < c.n ? r0 + stage_rows : c.n;
-	const uint32_t bits = c.pbit + r0 * c.w;
-	const uint4 *src = c.src16 + (bits >> 7);
-	const uint32_t bit0 = bits & 127u;
-	const uint32_t nchunks = (bit0 + (r1 - r0) * c.w + 127u) >> 7; // <= kBpScanStageBytes / 16 + 1
-	uint4 q[kBpScanStageLoads];
-#pragma unroll
-	for (uint32_t i = 0; i < kBpScanStageLoads; i++) { // all requested before the first is stored
-		const uint32_t ch = lane + 64u * i;
-		q[i] = make_uint4(0u, 0u, 0u, 0u);
-		if (64u * i < nchunks) q[i] = src[ch < nchunks ? ch : nchunks - 1u]; // uniform test, index clamped
-	}
-	// LDS operations of one wave execute in order: these stores come after the reads of the piece before
-	__builtin_amdgcn_wave_barrier();
-#pragma unroll
-	for (uint32_t i = 0; i < kBpScanStageLoads; i++) {
-		const uint32_t ch = lane + 64u * i;
-		if (ch < nchunks) c.stage[ch] = q[i];
-	}
-	__builtin_amdgcn_wave_barrier();
-	c.r0 = r0;
-	c.r1 = r1;
-	c.bit0 = bit0;
+	const uint32_t stage_rows = bp_stage_rows(c.w);
+	c.r0 = (k * 64u / stage_rows) * stage_rows;
+	bp_stage_piece<true>(c.src16, c.pbit, c.w, c.n, stage_rows, c.r0, c.stage, lane, c.r1, c.bit0);
 }
 
 // The lane's value of step k, masked to the type's width.  DELTA: call for every k = 0, 1, 2 ... of the group.
@@ -134,23 +110,6 @@ __device__ __forceinline__ uint64_t bp_cursor_value(BpCursor &c, uint32_t k /* u
 	return val & c.tmask;
 }
 
-// lane j: which of the rows [64 j, 64 j + 64) of the group exist and are wanted (bp_scan_group's window)
-template <bool V>
-__device__ __forceinline__ uint64_t bp_pair_window(const BpGroup &g, const uint64_t *validity, uint32_t lane) {
-	const uint32_t n = g.rows;
-	const uint32_t left = 64u * lane < n ? n - 64u * lane : 0u;
-	uint64_t win = left >= 64u ? ~0ull : ((1ull << left) - 1ull);
-	if (V) {
-		const uint32_t sh = (uint32_t)(g.out_off & 63u);
-		const uint64_t word0 = g.out_off >> 6;
-		const uint32_t nwords = (uint32_t)(((g.out_off + n - 1u) >> 6) - word0) + 1u; // <= 33
-		const uint64_t vw = lane < nwords ? validity[word0 + lane] : 0ull;
-		const uint64_t nx = __shfl_down(vw, 1, 64);
-		win &= sh ? (vw >> sh) | (nx << (64u - sh)) : vw;
-	}
-	return win;
-}
-
 __device__ __forceinline__ uint64_t bp_widen(uint64_t v, uint64_t sbit) { return (v ^ sbit) - sbit; }
 
 // ---- SUM(a * b) -----------------------------------------------------------------------------------------------
@@ -175,44 +134,29 @@ __device__ __forceinline__ void bp_pair_sum_steps(const BpPairArgs &s, BpCursor 
 	}
 }
 
-template <int KA>
-__device__ __forceinline__ void bp_pair_sum_b(const BpPairArgs &s, int kb, BpCursor &ca, BpCursor &cb, uint64_t win,
-                                              uint32_t lane, BpScanAcc<kBpScanSum> &acc) {
-	if (kb == kBpCurLinear) bp_pair_sum_steps<KA, kBpCurLinear>(s, ca, cb, win, lane, acc);
-	else if (kb == kBpCurFor) bp_pair_sum_steps<KA, kBpCurFor>(s, ca, cb, win, lane, acc);
-	else bp_pair_sum_steps<KA, kBpCurDelta>(s, ca, cb, win, lane, acc);
-}
-
 template <bool V>
 __global__ __launch_bounds__(kWorkgroup) void k_bp_scan_pair_sum(const BpGroup *__restrict__ a_groups,
                                                                  const BpGroup *__restrict__ b_groups,
                                                                  const uint32_t *__restrict__ group_seg /* of a */,
                                                                  const BpPairArgs s) {
-	constexpr uint32_t kWaves = kWorkgroup / 64;
-	__shared__ uint4 lds[kWaves * 2 * kBpScanWaveChunks];
-	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-	const uint32_t lane = threadIdx.x & 63u;
-	const uint64_t first = ((uint64_t)blockIdx.x * kWaves + wave) * s.per_wave;
-	if (first >= s.ngroups) return; // uniform per wave; no barrier follows
-	const uint32_t g0 = (uint32_t)first;
-	const uint32_t g1 = first + s.per_wave < s.ngroups ? g0 + s.per_wave : s.ngroups;
-	uint4 *stage_a = lds + wave * 2 * kBpScanWaveChunks, *stage_b = stage_a + kBpScanWaveChunks;
+	__shared__ uint4 lds[kBpWaves * 2 * kBpScanWaveChunks];
+	const BpWaveRun w(s.run, lds, 2);
+	if (w.none) return;
+	const uint32_t lane = w.lane;
 	BpScanAcc<kBpScanSum> acc;
-	uint32_t seg = group_seg[g0];
-	for (uint32_t gi = g0; gi < g1; gi++) {
-		const uint32_t gs = group_seg[gi];
-		if (gs != seg) {
-			acc.flush(s.res, seg, lane);
-			seg = gs;
-		}
+	uint32_t seg = group_seg[w.g0];
+	for (uint32_t gi = w.g0; gi < w.g1; gi++) {
+		acc.enter(group_seg[gi], seg, s.res, lane);
 		const BpGroup ga = a_groups[gi], gb = b_groups[gi];
 		BpCursor ca, cb;
-		const int ka = bp_cursor_open(ca, ga, s.a_blocks, s.a_tmask, stage_a);
-		const int kb = bp_cursor_open(cb, gb, s.b_blocks, s.b_tmask, stage_b);
-		const uint64_t win = bp_pair_window<V>(ga, s.validity, lane);
-		if (ka == kBpCurLinear) bp_pair_sum_b<kBpCurLinear>(s, kb, ca, cb, win, lane, acc);
-		else if (ka == kBpCurFor) bp_pair_sum_b<kBpCurFor>(s, kb, ca, cb, win, lane, acc);
-		else bp_pair_sum_b<kBpCurDelta>(s, kb, ca, cb, win, lane, acc);
+		const int ka = bp_cursor_open(ca, ga, s.a_blocks, s.a_tmask, w.stage);
+		const int kb = bp_cursor_open(cb, gb, s.b_blocks, s.b_tmask, w.stage + kBpScanWaveChunks);
+		const uint64_t win = bp_group_window<V>(ga, s.validity, lane);
+		bp_with_kind(ka, [&](auto ta) __attribute__((always_inline)) {
+			bp_with_kind(kb, [&](auto tb) __attribute__((always_inline)) {
+				bp_pair_sum_steps<decltype(ta)::value, decltype(tb)::value>(s, ca, cb, win, lane, acc);
+			});
+		});
 	}
 	acc.flush(s.res, seg, lane);
 }
@@ -271,44 +215,33 @@ __device__ __forceinline__ void bp_pair_gsum_steps(const BpPairArgs &s, BpCursor
 	}
 }
 
-template <int KV>
-__device__ __forceinline__ void bp_pair_gsum_k(const BpPairArgs &s, int kk, BpCursor &cv, BpCursor &ck, uint64_t win,
-                                               uint32_t lane, const BpPairBins &bins) {
-	if (kk == kBpCurLinear) bp_pair_gsum_steps<KV, kBpCurLinear>(s, cv, ck, win, lane, bins);
-	else if (kk == kBpCurFor) bp_pair_gsum_steps<KV, kBpCurFor>(s, cv, ck, win, lane, bins);
-	else bp_pair_gsum_steps<KV, kBpCurDelta>(s, cv, ck, win, lane, bins);
-}
-
 template <bool V>
 __global__ __launch_bounds__(kWorkgroup) void k_bp_scan_pair_gsum(const BpGroup *__restrict__ v_groups,
                                                                   const BpGroup *__restrict__ k_groups,
                                                                   const BpPairArgs s) {
-	constexpr uint32_t kWaves = kWorkgroup / 64;
-	__shared__ uint4 lds[kWaves * 2 * kBpScanWaveChunks];
-	__shared__ unsigned long long lds_bins[kWaves * 2 * kBpPairBins];
-	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-	const uint32_t lane = threadIdx.x & 63u;
-	const uint64_t first = ((uint64_t)blockIdx.x * kWaves + wave) * s.per_wave;
-	if (first >= s.ngroups) return; // uniform per wave; no barrier follows
-	const uint32_t g0 = (uint32_t)first;
-	const uint32_t g1 = first + s.per_wave < s.ngroups ? g0 + s.per_wave : s.ngroups;
-	uint4 *stage_v = lds + wave * 2 * kBpScanWaveChunks, *stage_k = stage_v + kBpScanWaveChunks;
+	__shared__ uint4 lds[kBpWaves * 2 * kBpScanWaveChunks];
+	__shared__ unsigned long long lds_bins[kBpWaves * 2 * kBpPairBins];
+	const BpWaveRun w(s.run, lds, 2);
+	if (w.none) return;
+	const uint32_t lane = w.lane;
 	const uint32_t nbins = s.nkeys + 1u; // <= kBpPairBins
 	BpPairBins bins;
-	bins.sums = lds_bins + wave * 2 * kBpPairBins;
+	bins.sums = lds_bins + w.wave * 2 * kBpPairBins;
 	bins.counts = bins.sums + kBpPairBins;
 	bins.copies = nbins <= 16u ? 16u : nbins <= 32u ? 8u : nbins <= 64u ? 4u : nbins <= 128u ? 2u : 1u; // * nbins <= 257
 	for (uint32_t i = lane; i < 2 * kBpPairBins; i += 64u) bins.sums[i] = 0ull;
 	__builtin_amdgcn_wave_barrier();
-	for (uint32_t gi = g0; gi < g1; gi++) {
+	for (uint32_t gi = w.g0; gi < w.g1; gi++) {
 		const BpGroup gv = v_groups[gi], gk = k_groups[gi];
 		BpCursor cv, ck;
-		const int kv = bp_cursor_open(cv, gv, s.a_blocks, s.a_tmask, stage_v);
-		const int kk = bp_cursor_open(ck, gk, s.b_blocks, s.b_tmask, stage_k);
-		const uint64_t win = bp_pair_window<V>(gv, s.validity, lane);
-		if (kv == kBpCurLinear) bp_pair_gsum_k<kBpCurLinear>(s, kk, cv, ck, win, lane, bins);
-		else if (kv == kBpCurFor) bp_pair_gsum_k<kBpCurFor>(s, kk, cv, ck, win, lane, bins);
-		else bp_pair_gsum_k<kBpCurDelta>(s, kk, cv, ck, win, lane, bins);
+		const int kv = bp_cursor_open(cv, gv, s.a_blocks, s.a_tmask, w.stage);
+		const int kk = bp_cursor_open(ck, gk, s.b_blocks, s.b_tmask, w.stage + kBpScanWaveChunks);
+		const uint64_t win = bp_group_window<V>(gv, s.validity, lane);
+		bp_with_kind(kv, [&](auto tv) __attribute__((always_inline)) {
+			bp_with_kind(kk, [&](auto tk) __attribute__((always_inline)) {
+				bp_pair_gsum_steps<decltype(tv)::value, decltype(tk)::value>(s, cv, ck, win, lane, bins);
+			});
+		});
 	}
 	// the wave's LDS adds have executed before these reads (in order); one global atomic per bin
 	__builtin_amdgcn_wave_barrier();

@@ -1,14 +1,13 @@
 // adac_bp_scans.inl — fused filter / aggregate scans on DuckDB BITPACKING blocks: SUM, COUNT / select BETWEEN and
 // MIN / MAX per segment straight from the block images, under an optional validity mask, nothing decoded to HBM.
-// Included into adac_kernels.hip after adac_bitpacking.inl: the BpGroup table filled by k_bp_prepare, read_field, the
-// 16-byte-aligned staging of a payload that starts at an arbitrary byte and wave_inclusive_sum are shared with the
-// decode.  Every result equals the same aggregate over what k_bp_unpack writes for these bytes (value = T(field +
-// frame) wrapping in T, DELTA_FOR prefix wrapping in T): shortcuts are taken only where that is provable.
+// Included into adac_kernels.hip after adac_bp_walk.inl: the wave's run of groups, the mask window of a group and
+// the staging of its payload are written there; the BpGroup table filled by k_bp_prepare, read_field and
+// wave_inclusive_sum are shared with the decode (adac_bitpacking.inl).  Every result equals the same aggregate over
+// what k_bp_unpack writes for these bytes (value = T(field + frame) wrapping in T, DELTA_FOR prefix wrapping in T):
+// shortcuts are taken only where that is provable.
 //
-// Work shape: a WAVE walks a run of consecutive metadata groups on its own — no barrier anywhere.  Lane l of step k
-// owns row 64 k + l of the group, so
-//   * a step's fields are 64 neighbours of the bit stream (conflict-free LDS reads of a wave-private stage of at most
-//     4 KiB of payload: a group wider than 16 bits is staged in pieces of whole steps);
+// Work shape (adac_bp_walk.inl): lane l of step k owns row 64 k + l of the group, so
+//   * a step's fields are 64 neighbours of the bit stream (conflict-free LDS reads of the wave's stage);
 //   * the mask bits of a step are ONE 64-bit window of the validity mask and its hits ONE ballot: lane k keeps the
 //     window / the ballot of step k, and a group's bitmap words leave with one store per lane;
 //   * DELTA_FOR is one DPP wave scan per step, carried from step to step in a uniform register; every row of the
@@ -25,14 +24,10 @@
 // atomic per result (k_scan_product's scheme).  Bitmap words wholly inside a group are stored, a group's first and
 // last word go through atomicOr: neighbouring groups and segments may share them at any bit phase.
 
-constexpr uint32_t kBpScanStageBytes = 4096;                     // payload bytes a wave stages at a time
-constexpr uint32_t kBpScanWaveChunks = kBpScanStageBytes / 16 + 3; // + the start's misalignment + read_field's over-read
-constexpr uint32_t kBpScanStageLoads = (kBpScanStageBytes / 16 + 1 + 63) / 64;
 enum : int { kBpScanSum = 0, kBpScanRange = 1, kBpScanMinMax = 2 };
 
 struct BpScanArgs {
-	uint32_t ngroups;
-	uint32_t per_wave; // consecutive groups one wave walks
+	BpRun run;
 	const uint8_t *blocks;
 	const uint64_t *validity; // bit e = element out_off + row; read only by the <V> kernels
 	uint64_t sbit;            // T's sign bit, 0 for the unsigned types
@@ -40,12 +35,6 @@ struct BpScanArgs {
 	unsigned long long *res;  // sums | counts | min, max pairs in the ordered domain
 	unsigned long long *bitmap; // select; nullptr: count only
 };
-
-__device__ __forceinline__ uint64_t bp_readlane64(uint64_t v, uint32_t k /* uniform */) {
-	const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)k);
-	const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)k);
-	return ((uint64_t)hi << 32) | lo;
-}
 
 // what a lane gathered over the groups of one segment
 template <int OP>
@@ -65,6 +54,13 @@ struct BpScanAcc {
 			const uint64_t t = wave_sum(a);
 			if (lane == 0 && t != 0ull) atomicAdd(res + seg, (unsigned long long)t);
 			a = 0ull;
+		}
+	}
+	// the walk reaches a group of segment gs: what was gathered over another segment leaves first
+	__device__ __forceinline__ void enter(uint32_t gs, uint32_t &seg, unsigned long long *res, uint32_t lane) {
+		if (gs != seg) {
+			flush(res, seg, lane);
+			seg = gs;
 		}
 	}
 };
@@ -89,9 +85,7 @@ __device__ __forceinline__ void bp_scan_row(const BpScanArgs &s, uint32_t k, uin
 	}
 }
 
-// FOR / DELTA_FOR at width >= 1: the payload in stages of whole steps through the wave's LDS buffer.
-// (bp_cursor_stage in adac_bp_pair_scans.inl stages the same way — piece size, chunk count, clamped loads — for a
-// cursor per column: a change to the staging here belongs there too.)
+// FOR / DELTA_FOR at width >= 1: the payload piece by piece (bp_stage_piece) through the wave's LDS buffer.
 // SCAN32 (DELTA_FOR of a 64-bit type at w <= 26): the fields of a step sum to less than 2^32, so the wave scan runs
 // on one dword.
 template <typename U, int OP, bool V, bool WIDE, bool DELTA, bool SCAN32 = false>
@@ -103,7 +97,7 @@ __device__ __forceinline__ void bp_scan_packed(const BpScanArgs &s, const BpGrou
 	const uintptr_t addr = reinterpret_cast<uintptr_t>(s.blocks + g.payload_off);
 	const uint4 *src16 = reinterpret_cast<const uint4 *>(addr & ~uintptr_t(15));
 	const uint32_t pbit = (uint32_t)(addr & 15) * 8u;
-	const uint32_t stage_rows = w <= 16u ? (uint32_t)kBpGroupRows : ((kBpScanStageBytes * 8u / w) & ~63u);
+	const uint32_t stage_rows = bp_stage_rows(w);
 	const uint32_t *lds32 = reinterpret_cast<const uint32_t *>(stage);
 	const U frame = (U)g.frame;
 	// DELTA_FOR: v[i] = delta_offset + (i + 1) * frame + sum_{j <= i} field[j], all mod 2^bits; `base` is the part of
@@ -111,26 +105,8 @@ __device__ __forceinline__ void bp_scan_packed(const BpScanArgs &s, const BpGrou
 	U base = (U)g.extra;
 	const U lane_frames = (U)((U)(lane + 1u) * frame);
 	for (uint32_t r0 = 0; r0 < n; r0 += stage_rows) { // uniform
-		const uint32_t r1 = r0 + stage_rows < n ? r0 + stage_rows : n;
-		const uint32_t bits = pbit + r0 * w;
-		const uint4 *src = src16 + (bits >> 7);
-		const uint32_t bit0 = bits & 127u;
-		const uint32_t nchunks = (bit0 + (r1 - r0) * w + 127u) >> 7; // <= kBpScanStageBytes / 16 + 1
-		uint4 q[kBpScanStageLoads];
-#pragma unroll
-		for (uint32_t i = 0; i < kBpScanStageLoads; i++) { // all requested before the first is stored
-			const uint32_t c = lane + 64u * i;
-			q[i] = make_uint4(0u, 0u, 0u, 0u);
-			if (64u * i < nchunks) q[i] = src[c < nchunks ? c : nchunks - 1u]; // uniform test, index clamped
-		}
-#pragma unroll
-		for (uint32_t i = 0; i < kBpScanStageLoads; i++) {
-			const uint32_t c = lane + 64u * i;
-			if (c < nchunks) stage[c] = q[i];
-		}
-		// LDS operations of one wave execute in order: the reads below see the stores above, and the next stage's
-		// stores come after this stage's reads
-		__builtin_amdgcn_wave_barrier();
+		uint32_t r1, bit0;
+		bp_stage_piece<false>(src16, pbit, w, n, stage_rows, r0, stage, lane, r1, bit0);
 		uint32_t fbit = bit0 + lane * w; // of the lane's row in the staged image: 64 rows further every step
 #pragma unroll 2
 		for (uint32_t k = r0 >> 6; k * 64u < r1; k++, fbit += 64u * w) {
@@ -153,7 +129,6 @@ __device__ __forceinline__ void bp_scan_packed(const BpScanArgs &s, const BpGrou
 			}
 			bp_scan_row<U, OP>(s, k, lane, val, keep, acc, hits);
 		}
-		__builtin_amdgcn_wave_barrier();
 	}
 }
 
@@ -161,17 +136,7 @@ template <typename U, int OP, bool V>
 __device__ __forceinline__ void bp_scan_group(const BpScanArgs &s, const BpGroup &g, uint4 *stage, uint32_t lane,
                                               BpScanAcc<OP> &acc) {
 	const uint32_t n = g.rows;
-	const uint32_t sh = (uint32_t)(g.out_off & 63u);
-	const uint64_t word0 = g.out_off >> 6;
-	const uint32_t nwords = (uint32_t)(((g.out_off + n - 1u) >> 6) - word0) + 1u; // <= 33
-	// lane j: which of the rows [64 j, 64 j + 64) exist and are wanted
-	const uint32_t left = 64u * lane < n ? n - 64u * lane : 0u;
-	uint64_t win = left >= 64u ? ~0ull : ((1ull << left) - 1ull);
-	if (V) {
-		const uint64_t vw = lane < nwords ? s.validity[word0 + lane] : 0ull;
-		const uint64_t nx = __shfl_down(vw, 1, 64);
-		win &= sh ? (vw >> sh) | (nx << (64u - sh)) : vw;
-	}
+	const uint64_t win = bp_group_window<V>(g, s.validity, lane);
 	const uint64_t tmask = (uint64_t)(U)~(U)0;
 	const uint32_t steps = (n + 63u) >> 6;
 	uint64_t hits = 0ull;
@@ -232,6 +197,10 @@ __device__ __forceinline__ void bp_scan_group(const BpScanArgs &s, const BpGroup
 	if (OP == kBpScanRange) {
 		acc.a += (uint64_t)__popcll(hits);
 		if (s.bitmap != nullptr) {
+			// the group's words of the bitmap, as bp_group_window takes them from the mask
+			const uint32_t sh = (uint32_t)(g.out_off & 63u);
+			const uint64_t word0 = g.out_off >> 6;
+			const uint32_t nwords = (uint32_t)(((g.out_off + n - 1u) >> 6) - word0) + 1u; // <= 33
 			// word j of the group holds the rows [64 j - sh, 64 j - sh + 64): the top of step j - 1, the bottom of step j
 			uint64_t prev = __shfl_up(hits, 1, 64);
 			if (lane == 0) prev = 0ull;
@@ -251,27 +220,17 @@ template <typename U, int OP, bool V>
 __global__ __launch_bounds__(kWorkgroup) void k_bp_scan(const BpGroup *__restrict__ groups,
                                                         const uint32_t *__restrict__ group_seg /* of every group */,
                                                         const BpScanArgs s) {
-	constexpr uint32_t kWaves = kWorkgroup / 64;
-	__shared__ uint4 lds[kWaves * kBpScanWaveChunks];
-	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-	const uint32_t lane = threadIdx.x & 63u;
-	const uint64_t first = ((uint64_t)blockIdx.x * kWaves + wave) * s.per_wave;
-	if (first >= s.ngroups) return; // uniform per wave; no barrier follows
-	const uint32_t g0 = (uint32_t)first;
-	const uint32_t g1 = first + s.per_wave < s.ngroups ? g0 + s.per_wave : s.ngroups;
-	uint4 *stage = lds + wave * kBpScanWaveChunks;
+	__shared__ uint4 lds[kBpWaves * kBpScanWaveChunks];
+	const BpWaveRun w(s.run, lds, 1);
+	if (w.none) return;
 	BpScanAcc<OP> acc;
-	uint32_t seg = group_seg[g0];
-	for (uint32_t gi = g0; gi < g1; gi++) {
-		const uint32_t gs = group_seg[gi];
-		if (gs != seg) {
-			acc.flush(s.res, seg, lane);
-			seg = gs;
-		}
+	uint32_t seg = group_seg[w.g0];
+	for (uint32_t gi = w.g0; gi < w.g1; gi++) {
+		acc.enter(group_seg[gi], seg, s.res, w.lane);
 		const BpGroup g = groups[gi];
-		bp_scan_group<U, OP, V>(s, g, stage, lane, acc);
+		bp_scan_group<U, OP, V>(s, g, w.stage, w.lane, acc);
 	}
-	acc.flush(s.res, seg, lane);
+	acc.flush(s.res, seg, w.lane);
 }
 
 // min / max cells from the ordered domain back to T's bits; a segment without a selected row reports the empty

@@ -1,23 +1,23 @@
 // adac_bp_select_gather.inl — materialise only the rows a selection bitmap keeps, straight from DuckDB BITPACKING
 // blocks (adac_bp_unpack_selected): the scan-with-selection half of ColumnSegment::FilterSelection for the persistent
 // codec, the counterpart of adac_select_gather.inl.  Included into adac_kernels.hip after adac_bp_pair_scans.inl: the
-// BpGroup table, the mask window of a group (bp_pair_window) and the column cursor (BpCursor) are the pair scans'.
+// wave's run of groups, the mask window of a group (bp_group_window) and the kind dispatch are adac_bp_walk.inl's, the
+// column cursor (BpCursor) is the pair scans'.
 // Three steps, all on the device:
 //   k_bp_group_popc  rows selected per metadata group (one wave per group, popcount over the group's mask window);
-//   k_scan_*         adac_select_gather.inl's exclusive prefix over the group table (group order = segment order = row
-//                    order) -> each group's first output slot, and the grand total;
-//   k_bp_gather      k_bp_scan's work shape: a WAVE walks a run of consecutive metadata groups on its own, no barrier
-//                    anywhere, one wave-private LDS stage.  Lane l of step k owns row 64 k + l; the selected lanes of a
-//                    step store their values at CONSECUTIVE slots (slot = the group's running offset + the selected
-//                    lanes below), so a step's stores are one contiguous run of the output.
+//   k_scan_*         adac_select_gather.inl's exclusive prefix (launch_exclusive_prefix) over the group table (group
+//                    order = segment order = row order) -> each group's first output slot, and the grand total;
+//   k_bp_gather      adac_bp_walk.inl's work shape: a WAVE walks a run of consecutive metadata groups on its own, one
+//                    wave-private LDS stage.  Lane l of step k owns row 64 k + l; the selected lanes of a step store
+//                    their values at CONSECUTIVE slots (slot = the group's running offset + the selected lanes
+//                    below), so a step's stores are one contiguous run of the output.
 // What is never read: a group without a selected row leaves on its count — no header, no mask word, no payload byte;
 // a CONSTANT, CONSTANT_DELTA or width-0 group has no payload (the cursor's linear kind); in a FOR group a step whose
 // mask word is zero is passed over, and with it every stage piece that holds such steps only.  A DELTA_FOR group is
 // taken through its steps in order up to its last selected row: the prefix needs every row before that one.
 
 struct BpGatherArgs {
-	uint32_t ngroups;
-	uint32_t per_wave; // consecutive groups one wave walks
+	BpRun run;
 	const uint8_t *blocks;
 	const uint64_t *bitmap; // bit e = element out_off + row
 	uint64_t tmask;         // all-ones of the type's width
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(kWorkgroup) void k_bp_group_popc(const BpGroup *__r
 	if (gi >= ngroups) return; // uniform per wave
 	const uint32_t lane = threadIdx.x & 63u;
 	const BpGroup g = groups[gi];
-	const uint64_t win = bp_pair_window<true>(g, bitmap, lane);
+	const uint64_t win = bp_group_window<true>(g, bitmap, lane);
 	const uint64_t c = wave_sum((uint64_t)__popcll(win));
 	if (lane == 0) group_cnt[gi] = (uint32_t)c; // <= 2048
 }
@@ -63,25 +63,20 @@ __device__ __forceinline__ void bp_gather_steps(BpCursor &c, uint64_t win, uint3
 template <typename U, bool IDS>
 __global__ __launch_bounds__(kWorkgroup) void k_bp_gather(const BpGroup *__restrict__ groups, const BpGatherArgs s,
                                                           U *__restrict__ out, uint64_t *__restrict__ out_ids) {
-	constexpr uint32_t kWaves = kWorkgroup / 64;
-	__shared__ uint4 lds[kWaves * kBpScanWaveChunks];
-	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-	const uint32_t lane = threadIdx.x & 63u;
-	const uint64_t first = ((uint64_t)blockIdx.x * kWaves + wave) * s.per_wave;
-	if (first >= s.ngroups) return; // uniform per wave; no barrier follows
-	const uint32_t g0 = (uint32_t)first;
-	const uint32_t g1 = first + s.per_wave < s.ngroups ? g0 + s.per_wave : s.ngroups;
-	uint4 *stage = lds + wave * kBpScanWaveChunks;
-	for (uint32_t gi = g0; gi < g1; gi++) {
+	__shared__ uint4 lds[kBpWaves * kBpScanWaveChunks];
+	const BpWaveRun w(s.run, lds, 1);
+	if (w.none) return;
+	const uint32_t lane = w.lane;
+	for (uint32_t gi = w.g0; gi < w.g1; gi++) {
 		const uint32_t cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.group_cnt[gi]);
 		if (cnt == 0u) continue; // nothing selected here: neither the header nor a mask word nor the payload is read
 		const uint64_t off = s.group_off[gi];
 		const BpGroup g = groups[gi];
 		BpCursor c;
-		const int kind = bp_cursor_open(c, g, s.blocks, s.tmask, stage);
-		const uint64_t win = bp_pair_window<true>(g, s.bitmap, lane);
-		if (kind == kBpCurLinear) bp_gather_steps<U, IDS, kBpCurLinear>(c, win, lane, off, cnt, g.out_off, out, out_ids);
-		else if (kind == kBpCurFor) bp_gather_steps<U, IDS, kBpCurFor>(c, win, lane, off, cnt, g.out_off, out, out_ids);
-		else bp_gather_steps<U, IDS, kBpCurDelta>(c, win, lane, off, cnt, g.out_off, out, out_ids);
+		const int kind = bp_cursor_open(c, g, s.blocks, s.tmask, w.stage);
+		const uint64_t win = bp_group_window<true>(g, s.bitmap, lane);
+		bp_with_kind(kind, [&](auto tk) __attribute__((always_inline)) {
+			bp_gather_steps<U, IDS, decltype(tk)::value>(c, win, lane, off, cnt, g.out_off, out, out_ids);
+		});
 	}
 }

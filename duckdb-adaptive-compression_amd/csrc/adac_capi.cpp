@@ -1444,13 +1444,17 @@ extern "C" adac_status adac_bp_bind(adac_bp_layout *l, const void *d_blocks) {
 	return ADAC_OK;
 }
 
+// the implicit bind of every entry point that reads the group table: a no-op while the layout's headers are parsed
+// from this buffer
+static adac_status bp_ensure_bound(adac_bp_layout *l, const void *d_blocks) {
+	return l->bound_blocks == d_blocks ? ADAC_OK : adac_bp_bind(l, d_blocks);
+}
+
 extern "C" adac_status adac_bp_unpack(adac_bp_layout *l, const void *d_blocks, void *d_out) {
 	if (!l || ((!d_blocks || !d_out) && l->total_values)) return ADAC_ERR_INVALID_ARGUMENT;
 	if (!aligned16(d_blocks) || !aligned16(d_out)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (l->bound_blocks != d_blocks) {
-		adac_status st = adac_bp_bind(l, d_blocks);
-		if (st != ADAC_OK) return st;
-	}
+	adac_status st = bp_ensure_bound(l, d_blocks);
+	if (st != ADAC_OK) return st;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	ADAC_HIP(adac::launch_bp_unpack(l->ctx->stream, l->type_size, l->d_groups, l->ngroups, d_blocks, d_out));
 	return ADAC_OK;
@@ -1462,10 +1466,8 @@ extern "C" adac_status adac_bp_unpack_range(adac_bp_layout *l, const void *d_blo
 	if (start > l->counts[seg] || count > l->counts[seg] - start) return ADAC_ERR_INVALID_ARGUMENT;
 	if (count == 0) return ADAC_OK;
 	if (!d_blocks || !d_out || !aligned16(d_blocks) || !aligned16(d_out)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (l->bound_blocks != d_blocks) {
-		adac_status st = adac_bp_bind(l, d_blocks);
-		if (st != ADAC_OK) return st;
-	}
+	adac_status st = bp_ensure_bound(l, d_blocks);
+	if (st != ADAC_OK) return st;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	const uint64_t g0 = l->seg_first_group[seg] + start / 2048;
 	ADAC_HIP(adac::launch_bp_unpack_range(l->ctx->stream, l->type_size, l->d_groups, (uint32_t)g0,
@@ -1493,10 +1495,8 @@ extern "C" adac_status adac_bp_unpack_selected(adac_bp_layout *l, const void *d_
 		return ADAC_OK;
 	}
 	if (!d_blocks || !aligned16(d_blocks) || !d_bitmap || !d_out) return ADAC_ERR_INVALID_ARGUMENT;
-	if (l->bound_blocks != d_blocks) {
-		adac_status st = adac_bp_bind(l, d_blocks);
-		if (st != ADAC_OK) return st;
-	}
+	adac_status st = bp_ensure_bound(l, d_blocks);
+	if (st != ADAC_OK) return st;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	const uint64_t nblocks = (l->ngroups + 1023) / 1024;
 	if (!l->d_group_cnt) ADAC_HIP(hipMalloc((void **)&l->d_group_cnt, l->ngroups * sizeof(uint32_t)));
@@ -1519,16 +1519,11 @@ static adac_status bp_scan_begin(adac_bp_layout *l, const void *d_blocks, const 
 	return ADAC_OK;
 }
 
-static adac_status bp_scan_bind(adac_bp_layout *l, const void *d_blocks) {
-	if (l->total_values && l->bound_blocks != d_blocks) return adac_bp_bind(l, d_blocks);
-	return ADAC_OK;
-}
-
 extern "C" adac_status adac_bp_scan_sum(adac_bp_layout *l, const void *d_blocks, const uint64_t *d_validity,
                                         uint64_t *d_sums) {
 	adac_status st = bp_scan_begin(l, d_blocks, d_sums);
 	if (st != ADAC_OK || l->nseg == 0) return st;
-	if ((st = bp_scan_bind(l, d_blocks)) != ADAC_OK) return st;
+	if ((st = bp_ensure_bound(l, d_blocks)) != ADAC_OK) return st;
 	// every wave adds its part: the sums start from zero (this also writes the segments without rows)
 	ADAC_HIP(hipMemsetAsync(d_sums, 0, l->nseg * sizeof(uint64_t), l->ctx->stream));
 	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, l->type_size, l->is_signed, adac::kBpScanOpSum, l->d_groups,
@@ -1553,7 +1548,7 @@ static adac_status bp_scan_range(adac_bp_layout *l, const void *d_blocks, const 
 	}
 	ADAC_HIP(hipMemsetAsync(d_counts, 0, l->nseg * sizeof(uint64_t), l->ctx->stream));
 	if (bhi < blo) return ADAC_OK; // empty range: all counts (and bits) are zero
-	if ((st = bp_scan_bind(l, d_blocks)) != ADAC_OK) return st;
+	if ((st = bp_ensure_bound(l, d_blocks)) != ADAC_OK) return st;
 	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, l->type_size, l->is_signed, adac::kBpScanOpRange, l->d_groups,
 	                              l->d_group_seg, l->ngroups, d_blocks, d_validity, blo, bhi - blo, d_counts,
 	                              want_bitmap ? d_bitmap : nullptr));
@@ -1574,7 +1569,7 @@ extern "C" adac_status adac_bp_scan_min_max(adac_bp_layout *l, const void *d_blo
                                             uint64_t *d_minmax) {
 	adac_status st = bp_scan_begin(l, d_blocks, d_minmax);
 	if (st != ADAC_OK || l->nseg == 0) return st;
-	if ((st = bp_scan_bind(l, d_blocks)) != ADAC_OK) return st;
+	if ((st = bp_ensure_bound(l, d_blocks)) != ADAC_OK) return st;
 	// the scan works in the ordered domain bits ^ signbit from the empty interval [all-ones, 0]; a kernel over the
 	// segments maps the cells back to T's bits
 	ADAC_HIP(adac::launch_minmax_init(l->ctx->stream, d_minmax, l->nseg));
@@ -1602,8 +1597,9 @@ static adac_status bp_pair_begin(adac_bp_layout *a, const void *d_a_blocks, adac
 }
 
 static adac_status bp_pair_bind(adac_bp_layout *a, const void *d_a_blocks, adac_bp_layout *b, const void *d_b_blocks) {
-	adac_status st = bp_scan_bind(a, d_a_blocks);
-	if (st == ADAC_OK && b != a) st = bp_scan_bind(b, d_b_blocks);
+	// a layout without rows has no group to parse, and bp_pair_begin has not looked at its pointer
+	adac_status st = a->total_values ? bp_ensure_bound(a, d_a_blocks) : ADAC_OK;
+	if (st == ADAC_OK && b != a && b->total_values) st = bp_ensure_bound(b, d_b_blocks);
 	return st;
 }
 

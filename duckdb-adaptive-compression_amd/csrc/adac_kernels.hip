@@ -1946,6 +1946,7 @@ hipError_t dispatch_size(uint32_t type_size, F &&f) {
 }
 
 #include "adac_bitpacking.inl"
+#include "adac_bp_walk.inl"
 #include "adac_bp_scans.inl"
 #include "adac_bp_pair_scans.inl"
 #include "adac_bp_select_gather.inl"
@@ -2550,19 +2551,36 @@ hipError_t launch_bp_fetch(hipStream_t s, uint32_t type_size, const uint64_t *d_
 	});
 }
 
-// Fused scans on BITPACKING blocks: a wave walks `per_wave` consecutive groups; the grid is sized so that a whole
-// device holds it at once (8 workgroups = 32 waves per CU) and every wave gets about the same number of groups.
+// The wave-per-run kernels on BITPACKING blocks (adac_bp_walk.inl): a wave walks `per_wave` consecutive groups; the
+// grid is sized so that a whole device holds it at once, `resident` workgroups per CU, and every wave gets about the
+// same number of groups.
+static dim3 bp_wave_grid(uint64_t ngroups, uint64_t resident, BpRun &run) {
+	const uint64_t cap = device_cus() * resident * kBpWaves;
+	run.ngroups = (uint32_t)ngroups;
+	run.per_wave = (uint32_t)((ngroups + cap - 1) / cap);
+	const uint64_t nwaves = (ngroups + run.per_wave - 1) / run.per_wave;
+	return dim3((unsigned)((nwaves + kBpWaves - 1) / kBpWaves));
+}
+
+// d_off[i] = d_cnt[0] + ... + d_cnt[i - 1] for i < n (n >= 1), *d_total = the sum of all; d_block_tot: a word per
+// kScanBlock counts
+static void launch_exclusive_prefix(hipStream_t s, const uint32_t *d_cnt, uint64_t n, uint64_t *d_off,
+                                    uint64_t *d_block_tot, uint64_t *d_total) {
+	const uint64_t nblocks = (n + kScanBlock - 1) / kScanBlock;
+	hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_cnt, n, d_off, d_block_tot);
+	hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(kScanBlock), 0, s, d_block_tot, nblocks, d_total);
+	hipLaunchKernelGGL(k_scan_fixup, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_off, n, d_block_tot);
+}
+
+// Fused scans on BITPACKING blocks (adac_bp_scans.inl): 8 workgroups = 32 waves per CU.
 hipError_t launch_bp_scan(hipStream_t s, uint32_t type_size, bool is_signed, int op, const void *d_groups,
                           const uint32_t *d_group_seg, uint64_t ngroups, const void *d_blocks,
                           const uint64_t *d_validity, uint64_t blo, uint64_t bspan, uint64_t *d_res, uint64_t *d_bitmap) {
 	static_assert(kBpScanOpSum == kBpScanSum && kBpScanOpRange == kBpScanRange && kBpScanOpMinMax == kBpScanMinMax, "ops");
 	if (ngroups == 0) return hipSuccess;
-	constexpr uint64_t kWaves = kWorkgroup / 64;
-	const uint64_t cap = device_cus() * 8 * kWaves;
 	BpScanArgs a;
 	const BpGroup *groups = static_cast<const BpGroup *>(d_groups);
-	a.ngroups = (uint32_t)ngroups;
-	a.per_wave = (uint32_t)((ngroups + cap - 1) / cap);
+	const dim3 grid = bp_wave_grid(ngroups, 8, a.run);
 	a.blocks = static_cast<const uint8_t *>(d_blocks);
 	a.validity = d_validity;
 	a.sbit = type_sign_bit(type_size, is_signed);
@@ -2570,8 +2588,6 @@ hipError_t launch_bp_scan(hipStream_t s, uint32_t type_size, bool is_signed, int
 	a.bspan = bspan;
 	a.res = reinterpret_cast<unsigned long long *>(d_res);
 	a.bitmap = reinterpret_cast<unsigned long long *>(d_bitmap);
-	const uint64_t nwaves = (ngroups + a.per_wave - 1) / a.per_wave;
-	const dim3 grid((unsigned)((nwaves + kWaves - 1) / kWaves));
 	return dispatch_size(type_size, [&](auto tag) {
 		using U = decltype(tag);
 #define ADAC_BP_SCAN(OP)                                                                                               \
@@ -2595,15 +2611,12 @@ hipError_t launch_bp_scan_minmax_finish(hipStream_t s, uint32_t type_size, bool 
 	return hipGetLastError();
 }
 
-// Pair scans on BITPACKING blocks (adac_bp_pair_scans.inl): launch_bp_scan's shape.  Two stage buffers per wave (and
-// the grouped kernel's bins) leave room for `resident` workgroups per CU.
+// Pair scans on BITPACKING blocks (adac_bp_pair_scans.inl).  Two stage buffers per wave (and the grouped kernel's
+// bins) leave room for `resident` workgroups per CU.
 static BpPairArgs bp_pair_args(const BpPairColumn &a, const BpPairColumn &b, uint64_t ngroups, uint64_t resident,
                                const uint64_t *d_validity, uint64_t *d_res, dim3 &grid) {
-	constexpr uint64_t kWaves = kWorkgroup / 64;
-	const uint64_t cap = device_cus() * resident * kWaves;
 	BpPairArgs s;
-	s.ngroups = (uint32_t)ngroups;
-	s.per_wave = (uint32_t)((ngroups + cap - 1) / cap);
+	grid = bp_wave_grid(ngroups, resident, s.run);
 	s.a_blocks = static_cast<const uint8_t *>(a.d_blocks);
 	s.b_blocks = static_cast<const uint8_t *>(b.d_blocks);
 	s.validity = d_validity;
@@ -2614,8 +2627,6 @@ static BpPairArgs bp_pair_args(const BpPairColumn &a, const BpPairColumn &b, uin
 	s.res = reinterpret_cast<unsigned long long *>(d_res);
 	s.counts = nullptr;
 	s.nkeys = 0;
-	const uint64_t nwaves = (ngroups + s.per_wave - 1) / s.per_wave;
-	grid = dim3((unsigned)((nwaves + kWaves - 1) / kWaves));
 	return s;
 }
 
@@ -2645,33 +2656,24 @@ hipError_t launch_bp_scan_pair_gsum(hipStream_t st, const BpPairColumn &v, const
 	return hipGetLastError();
 }
 
-// Scan with selection on BITPACKING blocks (adac_bp_select_gather.inl): counts per metadata group, the succinct
-// gather's exclusive prefix over them, then the gather in launch_bp_scan's shape (8 workgroups = 32 waves per CU).
+// Scan with selection on BITPACKING blocks (adac_bp_select_gather.inl): counts per metadata group, their exclusive
+// prefix, then the gather at launch_bp_scan's 8 workgroups = 32 waves per CU.
 hipError_t launch_bp_gather_selected(hipStream_t s, uint32_t type_size, const void *d_groups, uint64_t ngroups,
                                      const void *d_blocks, const uint64_t *d_bitmap, uint32_t *d_group_cnt,
                                      uint64_t *d_group_off, uint64_t *d_block_tot, void *d_out, uint64_t *d_out_ids,
                                      uint64_t *d_total) {
 	if (ngroups == 0) return hipMemsetAsync(d_total, 0, sizeof(uint64_t), s);
-	constexpr uint64_t kWaves = kWorkgroup / 64;
 	const BpGroup *groups = static_cast<const BpGroup *>(d_groups);
-	hipLaunchKernelGGL(k_bp_group_popc, dim3((unsigned)((ngroups + kWaves - 1) / kWaves)), dim3(kWorkgroup), 0, s, groups,
-	                   (uint32_t)ngroups, d_bitmap, d_group_cnt);
-	const uint64_t nblocks = (ngroups + kScanBlock - 1) / kScanBlock;
-	hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_group_cnt, ngroups, d_group_off,
-	                   d_block_tot);
-	hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(kScanBlock), 0, s, d_block_tot, nblocks, d_total);
-	hipLaunchKernelGGL(k_scan_fixup, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_group_off, ngroups, d_block_tot);
-	const uint64_t cap = device_cus() * 8 * kWaves;
+	hipLaunchKernelGGL(k_bp_group_popc, dim3((unsigned)((ngroups + kBpWaves - 1) / kBpWaves)), dim3(kWorkgroup), 0, s,
+	                   groups, (uint32_t)ngroups, d_bitmap, d_group_cnt);
+	launch_exclusive_prefix(s, d_group_cnt, ngroups, d_group_off, d_block_tot, d_total);
 	BpGatherArgs a;
-	a.ngroups = (uint32_t)ngroups;
-	a.per_wave = (uint32_t)((ngroups + cap - 1) / cap);
+	const dim3 grid = bp_wave_grid(ngroups, 8, a.run);
 	a.blocks = static_cast<const uint8_t *>(d_blocks);
 	a.bitmap = d_bitmap;
 	a.tmask = type_mask(type_size);
 	a.group_cnt = d_group_cnt;
 	a.group_off = d_group_off;
-	const uint64_t nwaves = (ngroups + a.per_wave - 1) / a.per_wave;
-	const dim3 grid((unsigned)((nwaves + kWaves - 1) / kWaves));
 	return dispatch_size(type_size, [&](auto tag) {
 		using U = decltype(tag);
 		if (d_out_ids) hipLaunchKernelGGL((k_bp_gather<U, true>), grid, dim3(kWorkgroup), 0, s, groups, a, static_cast<U *>(d_out), d_out_ids);
@@ -2691,11 +2693,7 @@ hipError_t launch_gather_selected(hipStream_t s, uint32_t type_size, const adac_
 		const unsigned per = kWorkgroup / 64;
 		hipLaunchKernelGGL(k_tile_popc<U>, dim3((unsigned)((ntiles + per - 1) / per)), dim3(kWorkgroup), 0, s, d_descs,
 		                   d_tiles, (uint32_t)ntiles, d_bitmap, d_tile_cnt);
-		const uint64_t nblocks = (ntiles + kScanBlock - 1) / kScanBlock;
-		hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_tile_cnt, ntiles, d_tile_off,
-		                   d_block_tot);
-		hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(kScanBlock), 0, s, d_block_tot, nblocks, d_total);
-		hipLaunchKernelGGL(k_scan_fixup, dim3((unsigned)nblocks), dim3(kScanBlock), 0, s, d_tile_off, ntiles, d_block_tot);
+		launch_exclusive_prefix(s, d_tile_cnt, ntiles, d_tile_off, d_block_tot, d_total);
 		if (g_tuning.gather_compact && bitmap_words < (1ull << 31)) { // (32-bit dword indices into the bitmap)
 			hipLaunchKernelGGL(k_gather_c<U>, dim3((unsigned)ntiles), dim3(kWorkgroup), 0, s, d_descs, d_tiles, d_recs, d_words,
 			                   d_bitmap, (uint32_t)(2 * bitmap_words - 1), d_tile_cnt, d_tile_off, static_cast<U *>(d_out), d_out_ids,

@@ -51,4 +51,5 @@ def test_pair_scan_kernels_have_no_spills_and_no_scratch(lib):
     assert sorted(table) == sorted(k + v + ">" for k in KERNELS for v in ("false", "true")), sorted(table)
     for name, r in table.items():
         assert r["vgpr_spills"] == 0 and r["sgpr_spills"] == 0 and r["scratch"] == 0, (name, r)
-    assert not any(k.startswith(kr.BUDGETED) for k in table)
+    # and tests/test_kernel_budget.py holds their registers, LDS and occupancy against profiles/kernel_budget.json
+    assert all(k.startswith(kr.BUDGETED) for k in table)

@@ -54,4 +54,6 @@ def test_scan_kernels_have_no_spills_and_no_scratch(lib):
     assert any(k.startswith("k_bp_scan<") for k in table)
     for name, r in table.items():
         assert r["vgpr_spills"] == 0 and r["sgpr_spills"] == 0 and r["scratch"] == 0, (name, r)
-    assert not any(k.startswith(kr.BUDGETED) for k in table)
+    # and tests/test_kernel_budget.py holds their registers, LDS and occupancy against profiles/kernel_budget.json
+    # (all but the one-thread-per-segment k_bp_scan_minmax_finish)
+    assert all(k.startswith(kr.BUDGETED) for k in table if k != "k_bp_scan_minmax_finish")
