@@ -139,6 +139,10 @@ LINEITEM = {
     "l_extendedprice": lambda rng, n: rng.integers(90_000, 10_495_000, size=n).astype(np.int32),   # cents
     "l_partkey": lambda rng, n: rng.integers(1, 2_000_001, size=n).astype(np.int32),
     "l_shipdate": lambda rng, n: rng.integers(8036, 10562, size=n).astype(np.int32),   # days since 1970: 1992-01-02 .. 1998-12-01
+    # independent uniform draws in l_shipdate's range: dbgen's commit and receipt dates follow the ship date closely, so
+    # a predicate between two of these selects more rows here than on the real table
+    "l_commitdate": lambda rng, n: rng.integers(8036, 10562, size=n).astype(np.int32),
+    "l_receiptdate": lambda rng, n: rng.integers(8036, 10562, size=n).astype(np.int32),
     "l_discount": lambda rng, n: rng.integers(0, 11, size=n).astype(np.int32),          # percent
     "l_tax": lambda rng, n: rng.integers(0, 9, size=n).astype(np.int32),                # percent
 }
@@ -738,6 +742,112 @@ def q6_bitpacking(adac, n=59_986_052):
     return out
 
 
+Q12_RECEIPT_DATES = (8766, 9130)   # l_receiptdate in 1994
+
+
+def q12_bitpacking(adac, n=59_986_052):
+    """TPC-H Q12's WHERE clause on DuckDB's own BITPACKING blocks, three int32 day columns: l_receiptdate BETWEEN one
+    year (adac_bp_scan_select_between), then l_commitdate < l_receiptdate under that bitmap and l_shipdate <
+    l_commitdate under that one (adac_bp_scan_select_compare); the final bitmap and counts checked against numpy before
+    and after the timing.  Interleaved in the same process: the chain; the BETWEEN; each compare in the chain and alone
+    (no validity); adac_bp_scan_count_compare; adac_bp_unpack of the two columns each compare reads;
+    adac_bp_scan_sum_product on the same pair, the pair walk that was there before."""
+    from oracle import bitpacking as bp
+    ctx = adac.Context(0)
+    cols = lineitem(np.random.default_rng(1994), n, ("l_shipdate", "l_commitdate", "l_receiptdate"))
+    enc = {name: bitpacking_blocks(adac, ctx, bp.Compressed(v), v.dtype) for name, v in cols.items()}
+    ship, commit, receipt = (enc[k] for k in ("l_shipdate", "l_commitdate", "l_receiptdate"))
+    nw = (n + 63) // 64
+    bm = [ctx.alloc(nw * 8 + 8) for _ in range(3)]
+    d_alone = ctx.alloc(nw * 8 + 8)
+    nseg = max(e.nseg for e in enc.values())
+    d_cnt, d_final, d_sum = ctx.alloc(nseg * 8), ctx.alloc(nseg * 8), ctx.alloc(nseg * 8)
+    d_out = ctx.alloc(n * 4 + 64)
+    LT = adac.CMP_LT
+    pairs = {"commit_lt_receipt": (commit, receipt, bm[0], bm[1], d_cnt), "ship_lt_commit": (ship, commit, bm[1], bm[2], d_final)}
+
+    def between():
+        receipt.lay.scan_select_between(receipt.words, *Q12_RECEIPT_DATES, bm[0], d_cnt)
+
+    def compare(name, masked):
+        a, b, d_valid, d_bitmap, d_counts = pairs[name]
+        if masked:
+            return lambda: a.lay.scan_select_compare(a.words, b.lay, b.words, LT, d_bitmap, d_counts, d_valid)
+        return lambda: a.lay.scan_select_compare(a.words, b.lay, b.words, LT, d_alone, d_cnt)
+
+    def count(name):
+        a, b = pairs[name][:2]
+        return lambda: a.lay.scan_count_compare(a.words, b.lay, b.words, LT, d_cnt)
+
+    def unpack(name):
+        a, b = pairs[name][:2]
+
+        def both():
+            a.lay.unpack(a.words, d_out)
+            b.lay.unpack(b.words, d_out)
+        return both
+
+    def product(name):
+        a, b = pairs[name][:2]
+        return lambda: a.lay.scan_sum_product(a.words, b.lay, b.words, d_sum)
+
+    def chain():
+        between()
+        compare("commit_lt_receipt", True)()
+        compare("ship_lt_commit", True)()
+
+    m1 = (cols["l_receiptdate"] >= Q12_RECEIPT_DATES[0]) & (cols["l_receiptdate"] <= Q12_RECEIPT_DATES[1])
+    m2 = m1 & (cols["l_commitdate"] < cols["l_receiptdate"])
+    m3 = m2 & (cols["l_shipdate"] < cols["l_commitdate"])
+    full = np.zeros(nw * 64, dtype=bool)
+    full[:n] = m3
+    want_words = np.packbits(full, bitorder="little").view(np.uint64)
+    starts = np.concatenate([[0], np.cumsum(ship.counts[:-1], dtype=np.int64)])
+    want_counts = np.add.reduceat(m3.astype(np.uint64), starts)
+
+    def parity(when):
+        chain()
+        ctx.sync()
+        assert np.array_equal(bm[2].download(np.uint64, nw), want_words), "Q12 bitmap parity (%s)" % when
+        assert np.array_equal(d_final.download(np.uint64, ship.nseg), want_counts), "Q12 counts parity (%s)" % when
+
+    parity("before timing")
+    entries = [("q12_where_chain", chain), ("select_between_receiptdate", between)]
+    for name in pairs:
+        entries += [(name + "_in_chain", compare(name, True)), (name + "_alone", compare(name, False)),
+                    (name + "_count", count(name)), (name + "_unpack_two_columns", unpack(name)),
+                    (name + "_sum_product", product(name))]
+    samples = timed_interleaved(ctx, entries)
+    parity("after timing")
+    med = {k: float(np.median(x)) for k, x in samples.items()}
+    out = {"rows": n, "selected_rows": {"receiptdate_in_year": int(m1.sum()), "and_commit_lt_receipt": int(m2.sum()),
+                                        "and_ship_lt_commit": int(m3.sum())},
+           "columns": {k: e.info for k, e in enc.items()}, "packed_bytes": {k: e.nbytes for k, e in enc.items()},
+           "ms": med, "q12_where_chain_ms": med["q12_where_chain"],
+           "samples_ms": {k: [round(t, 5) for t in x] for k, x in samples.items()}}
+    for name, (a, b, _, _, _) in pairs.items():
+        sel, dec, prod = med[name + "_alone"], med[name + "_unpack_two_columns"], med[name + "_sum_product"]
+        two = a.nbytes + b.nbytes
+        out[name] = {"select_alone_ms": sel, "select_in_chain_ms": med[name + "_in_chain"], "count_ms": med[name + "_count"],
+                     "unpack_two_columns_ms": dec, "sum_product_ms": prod, "select_over_decode": sel / dec,
+                     "select_in_chain_over_decode": med[name + "_in_chain"] / dec,
+                     "count_over_decode": med[name + "_count"] / dec, "select_over_sum_product": sel / prod,
+                     "count_over_sum_product": med[name + "_count"] / prod,
+                     "select_packed_read_GBps": two / (sel * 1e-3) / 1e9, "bitmap_bytes_written": nw * 8,
+                     "sum_product_packed_read_GBps": two / (prod * 1e-3) / 1e9,
+                     "unpack_two_columns_total_GBps": (two + 2 * n * 4) / (dec * 1e-3) / 1e9}
+        print("q12_bitpacking %s: select %.4f ms (in chain %.4f, count %.4f), decode of both %.4f, sum_product %.4f" %
+              (name, sel, med[name + "_in_chain"], med[name + "_count"], dec, prod), file=sys.stderr, flush=True)
+    out["note"] = ("l_commitdate and l_receiptdate are independent uniform draws in l_shipdate's range: dbgen's dates are "
+                   "correlated and select fewer rows.  *_alone = adac_bp_scan_select_compare(LT) with d_validity NULL, "
+                   "*_in_chain = the same call under the previous step's bitmap, *_count = adac_bp_scan_count_compare "
+                   "with d_validity NULL, *_unpack_two_columns = adac_bp_unpack of the two columns the compare reads, "
+                   "*_sum_product = adac_bp_scan_sum_product on the same pair without a mask; medians of %d interleaved "
+                   "rounds of %d calls each" % (ROUNDS, INNER))
+    ctx.close()
+    return out
+
+
 def bitpacking_select_gather(adac, n=59_986_052):
     """Filter -> project on DuckDB's own BITPACKING blocks: adac_bp_unpack_selected (values only, then values + ids) of
     l_extendedprice (int32, FOR), the 6-valued uint8 code and a sorted copy of l_partkey (DELTA_FOR) under five bitmaps
@@ -1149,6 +1259,7 @@ def main():
             "bitpacking_scan": lambda: bitpacking_scan(adac), "q6_packed": lambda: q6_packed(adac),
             "bitpacking_fused_scans": lambda: bitpacking_fused_scans(adac),
             "q6_bitpacking": lambda: q6_bitpacking(adac),
+            "q12_bitpacking": lambda: q12_bitpacking(adac),
             "bitpacking_select_gather": lambda: bitpacking_select_gather(adac),
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "q1_filtered_packed": lambda: q1_filtered_packed(adac),

@@ -26,6 +26,9 @@ SEG_PACKED = 1
 # adac_scan_group_sum_q1: term t of group g is d_out[t * (ngroups + 1) + g]
 Q1_TERMS = 7
 Q1_COUNT, Q1_SUM_Q, Q1_SUM_A, Q1_SUM_B, Q1_SUM_AB, Q1_SUM_AC, Q1_SUM_ABC = range(7)
+# adac_bp_scan_select_compare / adac_bp_scan_count_compare: ADAC_CMP_* and their ORs
+CMP_LT, CMP_EQ, CMP_GT = 1, 2, 4
+CMP_LE, CMP_NE, CMP_GE = CMP_LT | CMP_EQ, CMP_LT | CMP_GT, CMP_EQ | CMP_GT
 
 _NP2TYPE = {
     np.dtype(np.uint8): UINT8, np.dtype(np.int8): INT8, np.dtype(np.uint16): UINT16, np.dtype(np.int16): INT16,
@@ -189,6 +192,8 @@ SIGNATURES = {
     "adac_bp_scan_min_max": (_int, [_vp, _vp, _vp, _vp]),
     "adac_bp_scan_sum_product": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "adac_bp_scan_group_sum": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "adac_bp_scan_select_compare": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "adac_bp_scan_count_compare": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "adac_bp_unpack_selected": (_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "adac_bp_bind": (_int, [_vp, _vp]),
     "adac_bp_unpack": (_int, [_vp, _vp, _vp]),
@@ -690,6 +695,20 @@ class BitpackingLayout:
         the rows whose bit is set in d_validity; ngroups + 1 results each, keys >= ngroups in the last."""
         _check(lib().adac_bp_scan_group_sum(self._h, _dptr(d_blocks), keys._h, _dptr(d_key_blocks), _dptr(d_validity),
                                             int(ngroups), _dptr(d_sums), _dptr(d_counts)), "adac_bp_scan_group_sum")
+
+    def scan_select_compare(self, d_blocks, other, d_other_blocks, cmp, d_bitmap, d_counts, d_validity=None):
+        """Selection bitmap (this layout's element space) + per-segment counts of the rows where self <cmp> other,
+        cmp one of CMP_LT ... CMP_GE; the values compare as mathematical integers whatever the two types are.  `other`:
+        a BitpackingLayout whose metadata groups cover the same rows."""
+        _check(lib().adac_bp_scan_select_compare(self._h, _dptr(d_blocks), other._h, _dptr(d_other_blocks),
+                                                 _dptr(d_validity), int(cmp), _dptr(d_bitmap), _dptr(d_counts)),
+               "adac_bp_scan_select_compare")
+
+    def scan_count_compare(self, d_blocks, other, d_other_blocks, cmp, d_counts, d_validity=None):
+        """The counts of scan_select_compare alone."""
+        _check(lib().adac_bp_scan_count_compare(self._h, _dptr(d_blocks), other._h, _dptr(d_other_blocks),
+                                                _dptr(d_validity), int(cmp), _dptr(d_counts)),
+               "adac_bp_scan_count_compare")
 
     def unpack_selected(self, d_blocks, d_bitmap, d_out, d_out_ids=None, want_total=True):
         """Values (and optionally element indices) of the rows whose bitmap bit is set, dense, segment by segment and

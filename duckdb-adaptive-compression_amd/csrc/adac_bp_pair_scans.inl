@@ -1,7 +1,9 @@
 // adac_bp_pair_scans.inl — fused scans over TWO columns of DuckDB BITPACKING blocks walked in step: SUM(a * b) per
-// segment (Q6's aggregate) and SUM(v), COUNT(*) GROUP BY key (Q1's basic shape), under an optional selection bitmap,
-// nothing decoded to HBM.  Included into adac_kernels.hip after adac_bp_scans.inl: the wave's run of groups, the mask
-// window of a group, the staging of a piece and the kind dispatch are adac_bp_walk.inl's, BpScanAcc is k_bp_scan's.
+// segment (Q6's aggregate), SUM(v), COUNT(*) GROUP BY key (Q1's basic shape) and the selection of the rows where
+// a <cmp> b (Q12's l_commitdate < l_receiptdate), under an optional selection bitmap, nothing decoded to HBM.
+// Included into adac_kernels.hip after adac_bp_scans.inl: the wave's run of groups, the mask window of a group, the
+// staging of a piece, the kind dispatch and the bitmap words of a group are adac_bp_walk.inl's, BpScanAcc is
+// k_bp_scan's.
 //
 // Work shape (adac_bp_walk.inl): a WAVE walks a run of consecutive metadata groups on its own.  The host has checked
 // that group i of both layouts covers the same rows at the same element offset, so the wave takes group i of both
@@ -23,7 +25,9 @@
 // first layout with one 64-bit atomic.  Grouped: bins live in LDS per wave — 16 / 8 / 4 / 2 / 1 copies of the
 // ngroups + 1 bins, lane & (copies - 1) picks one, so few lanes collide on an LDS add when there are few keys — and at
 // its end the wave touches every bin with one global atomic.  A group whose key column is a constant updates its bin
-// once.
+// once.  Compare: counts per segment as SUM(a * b)'s sums; one ballot per step, and a group's words of the bitmap
+// leave as k_bp_scan's do (bp_group_emit).  The values are compared as mathematical integers (BpMath), so the two
+// types may differ in width and signedness.  What only a group's end needs waits in vector registers (bp_park).
 
 constexpr uint32_t kBpPairBins = 257; // 256 groups + overflow
 
@@ -256,4 +260,141 @@ __global__ __launch_bounds__(kWorkgroup) void k_bp_scan_pair_gsum(const BpGroup 
 			if (s.counts != nullptr) atomicAdd(s.counts + b, (unsigned long long)cnt);
 		}
 	}
+}
+
+// ---- select / count the rows where value(a) <cmp> value(b) ----------------------------------------------------
+
+enum : uint32_t { kBpCmpLt = 1u, kBpCmpEq = 2u, kBpCmpGt = 4u }; // ADAC_CMP_* of adacodec.h
+
+struct BpPairCmpArgs {
+	BpPairArgs p;               // p.res: rows selected per segment of the first layout
+	unsigned long long *bitmap; // select: bit e = element out_off + row of the first layout; nullptr: count only
+	uint32_t cmp;               // an OR of kBpCmpLt / Eq / Gt, 1 ... 6
+};
+
+// A mathematical integer in [-2^63, 2^64), what a value of any of the eight types is, as the 65-bit number
+// value + 2^63 = top * 2^64 + low.  From the value widened to 64 bits by its type's signedness: adding 2^63 flips
+// bit 63, and only an unsigned type (sbit = 0, of 64 bits) has values of 2^63 and more.
+struct BpMath {
+	uint64_t low;
+	uint32_t top;
+	__device__ __forceinline__ BpMath(uint64_t wide, uint64_t sbit)
+	    : low(wide ^ (1ull << 63)), top(sbit == 0ull ? (uint32_t)(wide >> 63) : 0u) {}
+};
+// the borrow of the 65-bit difference
+__device__ __forceinline__ bool bp_math_lt(const BpMath &x, const BpMath &y) {
+	return (int32_t)(x.top - y.top - (uint32_t)(x.low < y.low)) < 0;
+}
+__device__ __forceinline__ bool bp_math_eq(const BpMath &x, const BpMath &y) {
+	return ((x.low ^ y.low) | (uint64_t)(x.top ^ y.top)) == 0ull;
+}
+// which of the three bits of cmp the pair (x, y) answers to
+__device__ __forceinline__ uint32_t bp_math_cmp(const BpMath &x, const BpMath &y) {
+	return bp_math_lt(x, y) ? kBpCmpLt : bp_math_eq(x, y) ? kBpCmpEq : kBpCmpGt;
+}
+
+// A wave-uniform value kept in a vector register from here on: the step loops are short of scalar registers (two
+// cursors, the window and the kernel's arguments), and what is needed only at a group's end can wait in a lane.
+template <typename T>
+__device__ __forceinline__ T bp_park(T x) {
+	asm volatile("" : "+v"(x));
+	return x;
+}
+// ... and a parked pointer back in scalar registers for the stretch that reads through it
+template <typename T>
+__device__ __forceinline__ T *bp_unpark(T *p) {
+	const uint64_t v = reinterpret_cast<uint64_t>(p);
+	const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+	const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+	return reinterpret_cast<T *>(((uint64_t)hi << 32) | lo);
+}
+
+// [olo, ohi]: the ordered numbers every value of the group lies between, had from the header alone — a constant
+// (linear with step 0), or a FOR group whose [frame, frame + 2^w) does not wrap in its type's ordered domain
+// (bp_scan_group's test).  false: the group has to be walked.
+__device__ __forceinline__ bool bp_cursor_interval(const BpCursor &c, int kind, uint64_t sbit, uint64_t &olo,
+                                                   uint64_t &ohi) {
+	olo = ohi = (c.frame & c.tmask) ^ sbit;
+	if (kind == kBpCurLinear) return c.base == 0ull;
+	if (kind != kBpCurFor) return false;
+	const uint64_t span = mask64(c.w);
+	if (span > c.tmask - olo) return false;
+	ohi = olo + span;
+	return true;
+}
+
+// lane k of the result keeps step k's ballot, as bp_scan_row does for kBpScanRange
+template <int KA, int KB>
+__device__ __forceinline__ uint64_t bp_pair_cmp_steps(const BpPairArgs &s, uint32_t cmp, BpCursor &ca, BpCursor &cb,
+                                                      uint64_t win, uint32_t lane) {
+	uint64_t hits = 0ull;
+	const uint32_t steps = (ca.n + 63u) >> 6;
+	for (uint32_t k = 0; k < steps; k++) {
+		const uint64_t wk = bp_readlane64(win, k);
+		// nothing of the step is wanted: legal to pass over only when no prefix has to advance
+		if (KA != kBpCurDelta && KB != kBpCurDelta && wk == 0ull) continue;
+		const uint64_t va = bp_cursor_value<KA>(ca, k, lane);
+		const uint64_t vb = bp_cursor_value<KB>(cb, k, lane);
+		const BpMath ma(bp_widen(va, s.a_sbit), s.a_sbit), mb(bp_widen(vb, s.b_sbit), s.b_sbit);
+		const uint64_t ballot = __ballot(((wk >> lane) & 1ull) && (cmp & bp_math_cmp(ma, mb)) != 0u);
+		if (lane == k) hits = ballot;
+	}
+	return hits;
+}
+
+template <bool V>
+__global__ __launch_bounds__(kWorkgroup) void k_bp_scan_pair_cmp(const BpGroup *__restrict__ a_groups,
+                                                                 const BpGroup *__restrict__ b_groups,
+                                                                 const uint32_t *__restrict__ group_seg /* of a */,
+                                                                 const BpPairCmpArgs c) {
+	__shared__ uint4 lds[kBpWaves * 2 * kBpScanWaveChunks];
+	const BpPairArgs &s = c.p;
+	const BpWaveRun w(s.run, lds, 2);
+	if (w.none) return;
+	const uint32_t lane = w.lane;
+	BpScanAcc<kBpScanRange> acc;
+	// Beside k_bp_scan_pair_sum's state the step loops hold the comparison's lane masks; with everything below in
+	// scalar registers the kernel is 4 (<V>: 11) of them short, so what a group needs only at its start or end is parked
+	// (the results, the comparison and the mask are read per lane anyway and stay where they are)
+	unsigned long long *const res = bp_park(s.res), *const bitmap = bp_park(c.bitmap);
+	const uint32_t cmp = bp_park(c.cmp);
+	const uint64_t *const validity = bp_park(s.validity);
+	const uint8_t *const pa_blocks = bp_park(s.a_blocks), *const pb_blocks = bp_park(s.b_blocks);
+	const uint32_t *const pgroup_seg = bp_park(group_seg);
+	uint32_t seg = group_seg[w.g0];
+	for (uint32_t gi = w.g0; gi < w.g1; gi++) {
+		acc.enter(bp_unpark(pgroup_seg)[gi], seg, res, lane);
+		const BpGroup ga = a_groups[gi];
+		const uint64_t out_off = bp_park(ga.out_off);
+		const uint64_t win = bp_group_window<V>(ga, validity, lane);
+		// no row of the group is wanted: nothing is read and, the cursors being opened per group, no prefix is owed
+		if (V && __ballot(win != 0ull) == 0ull) continue;
+		const BpGroup gb = b_groups[gi];
+		BpCursor ca, cb;
+		const int ka = bp_cursor_open(ca, ga, bp_unpark(pa_blocks), s.a_tmask, w.stage);
+		const int kb = bp_cursor_open(cb, gb, bp_unpark(pb_blocks), s.b_tmask, w.stage + kBpScanWaveChunks);
+		// the two headers decide the group when every value of a lies on one side of every value of b, or both columns
+		// are one value: no payload byte of either is read
+		uint32_t is = 0u;
+		uint64_t alo, ahi, blo, bhi;
+		if (bp_cursor_interval(ca, ka, s.a_sbit, alo, ahi) && bp_cursor_interval(cb, kb, s.b_sbit, blo, bhi)) {
+			// (an ordered number less its type's sign bit is the widened value)
+			if (bp_math_lt(BpMath(ahi - s.a_sbit, s.a_sbit), BpMath(blo - s.b_sbit, s.b_sbit))) is = kBpCmpLt;
+			else if (bp_math_lt(BpMath(bhi - s.b_sbit, s.b_sbit), BpMath(alo - s.a_sbit, s.a_sbit))) is = kBpCmpGt;
+			else if (alo == ahi && blo == bhi) is = kBpCmpEq; // neither below the other
+		}
+		uint64_t hits = 0ull;
+		if (is != 0u) {
+			hits = (cmp & is) != 0u ? win : 0ull;
+		} else {
+			bp_with_kind(ka, [&](auto ta) __attribute__((always_inline)) {
+				bp_with_kind(kb, [&](auto tb) __attribute__((always_inline)) {
+					hits = bp_pair_cmp_steps<decltype(ta)::value, decltype(tb)::value>(s, cmp, ca, cb, win, lane);
+				});
+			});
+		}
+		acc.a += (uint64_t)__popcll(hits);
+		if (bitmap != nullptr) bp_group_emit(out_off, ga.rows, hits, bitmap, lane);
+	}
+	acc.flush(res, seg, lane);
 }

@@ -196,23 +196,7 @@ __device__ __forceinline__ void bp_scan_group(const BpScanArgs &s, const BpGroup
 	}
 	if (OP == kBpScanRange) {
 		acc.a += (uint64_t)__popcll(hits);
-		if (s.bitmap != nullptr) {
-			// the group's words of the bitmap, as bp_group_window takes them from the mask
-			const uint32_t sh = (uint32_t)(g.out_off & 63u);
-			const uint64_t word0 = g.out_off >> 6;
-			const uint32_t nwords = (uint32_t)(((g.out_off + n - 1u) >> 6) - word0) + 1u; // <= 33
-			// word j of the group holds the rows [64 j - sh, 64 j - sh + 64): the top of step j - 1, the bottom of step j
-			uint64_t prev = __shfl_up(hits, 1, 64);
-			if (lane == 0) prev = 0ull;
-			const uint64_t word = sh ? (hits << sh) | (prev >> (64u - sh)) : hits;
-			if (lane < nwords && word != 0ull) {
-				if (lane == 0 || lane == nwords - 1u) {
-					atomicOr(s.bitmap + word0 + lane, (unsigned long long)word);
-				} else {
-					s.bitmap[word0 + lane] = word;
-				}
-			}
-		}
+		if (s.bitmap != nullptr) bp_group_emit(g.out_off, n, hits, s.bitmap, lane);
 	}
 }
 

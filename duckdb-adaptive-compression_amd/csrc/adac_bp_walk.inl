@@ -1,7 +1,7 @@
 // adac_bp_walk.inl — what the wave-per-run kernels on DuckDB BITPACKING blocks share: k_bp_scan (adac_bp_scans.inl),
-// k_bp_scan_pair_sum and k_bp_scan_pair_gsum (adac_bp_pair_scans.inl), k_bp_gather and k_bp_group_popc
-// (adac_bp_select_gather.inl).  Included into adac_kernels.hip after adac_bitpacking.inl (the BpGroup table filled by
-// k_bp_prepare) and before those three.
+// k_bp_scan_pair_sum, k_bp_scan_pair_gsum and k_bp_scan_pair_cmp (adac_bp_pair_scans.inl), k_bp_gather and
+// k_bp_group_popc (adac_bp_select_gather.inl).  Included into adac_kernels.hip after adac_bitpacking.inl (the BpGroup
+// table filled by k_bp_prepare) and before those three.
 //
 // Work shape: a WAVE walks a run of `per_wave` consecutive metadata groups on its own — no barrier anywhere.  Lane l
 // of step k owns row 64 k + l of the group, so a step's fields are 64 neighbours of the bit stream and its mask bits
@@ -9,6 +9,7 @@
 //   BpRun, BpWaveRun  the run's description in the kernel arguments (bp_wave_grid in adac_kernels.hip sizes it) and
 //                     the wave's part of it: groups [g0, g1), the lane, the wave's LDS stage buffers
 //   bp_group_window   lane j: which of the rows [64 j, 64 j + 64) of a group exist and are wanted
+//   bp_group_emit     the other way round: lane j's ballot of step j into the group's words of a selection bitmap
 //   bp_stage_piece    payload rows [r0, r1) of a group into a wave-private LDS buffer of at most 4 KiB of payload: a
 //                     group wider than 16 bits is staged in pieces of whole steps (bp_stage_rows)
 //   bp_with_kind      how a group's values are had (linear / FOR / DELTA) as a compile-time constant
@@ -64,6 +65,27 @@ __device__ __forceinline__ uint64_t bp_group_window(const BpGroup &g, const uint
 		win &= sh ? (vw >> sh) | (nx << (64u - sh)) : vw;
 	}
 	return win;
+}
+
+// lane j holds the hits of step j (rows [64 j, 64 j + 64) of a group of n rows, bit e = element out_off + row): the
+// group's words of the zeroed `bitmap`, as bp_group_window takes them from a mask.  Words wholly inside the group are
+// stored, its first and last go through atomicOr: neighbouring groups and segments may share them at any bit phase.
+__device__ __forceinline__ void bp_group_emit(uint64_t out_off, uint32_t n, uint64_t hits, unsigned long long *bitmap,
+                                              uint32_t lane) {
+	const uint32_t sh = (uint32_t)(out_off & 63u);
+	const uint64_t word0 = out_off >> 6;
+	const uint32_t nwords = (uint32_t)(((out_off + n - 1u) >> 6) - word0) + 1u; // <= 33
+	// word j of the group holds the rows [64 j - sh, 64 j - sh + 64): the top of step j - 1, the bottom of step j
+	uint64_t prev = __shfl_up(hits, 1, 64);
+	if (lane == 0) prev = 0ull;
+	const uint64_t word = sh ? (hits << sh) | (prev >> (64u - sh)) : hits;
+	if (lane < nwords && word != 0ull) {
+		if (lane == 0 || lane == nwords - 1u) {
+			atomicOr(bitmap + word0 + lane, (unsigned long long)word);
+		} else {
+			bitmap[word0 + lane] = word;
+		}
+	}
 }
 
 // rows of one staged piece: the whole group up to 16 bits, else the whole steps that fit kBpScanStageBytes

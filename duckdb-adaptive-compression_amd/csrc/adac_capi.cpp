@@ -1636,6 +1636,44 @@ extern "C" adac_status adac_bp_scan_group_sum(adac_bp_layout *values, const void
 	return ADAC_OK;
 }
 
+static adac_status bp_pair_compare(adac_bp_layout *a, const void *d_a_blocks, adac_bp_layout *b, const void *d_b_blocks,
+                                   const uint64_t *d_validity, uint32_t cmp, uint64_t *d_bitmap, uint64_t *d_counts,
+                                   bool want_bitmap) {
+	adac_status st = bp_pair_begin(a, d_a_blocks, b, d_b_blocks);
+	if (st != ADAC_OK) return st;
+	if (cmp == 0 || cmp > 6) return ADAC_ERR_INVALID_ARGUMENT;
+	if (a->nseg && !d_counts) return ADAC_ERR_INVALID_ARGUMENT;
+	if (want_bitmap && ((a->value_span && !d_bitmap) || (d_bitmap && d_bitmap == d_validity))) {
+		return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	if (a->nseg == 0) return ADAC_OK;
+	ADAC_HIP(hipSetDevice(a->ctx->device));
+	if ((st = bp_pair_bind(a, d_a_blocks, b, d_b_blocks)) != ADAC_OK) return st;
+	// every wave adds its part and ORs the words it shares: both start from zero (this also writes the segments
+	// without rows and the bits no segment covers)
+	if (want_bitmap && a->value_span) {
+		ADAC_HIP(hipMemsetAsync(d_bitmap, 0, ((a->value_span + 63) / 64) * sizeof(uint64_t), a->ctx->stream));
+	}
+	ADAC_HIP(hipMemsetAsync(d_counts, 0, a->nseg * sizeof(uint64_t), a->ctx->stream));
+	const adac::BpPairColumn ca {a->d_groups, d_a_blocks, a->type_size, a->is_signed};
+	const adac::BpPairColumn cb {b->d_groups, d_b_blocks, b->type_size, b->is_signed};
+	ADAC_HIP(adac::launch_bp_scan_pair_cmp(a->ctx->stream, ca, cb, a->d_group_seg, a->ngroups, d_validity, cmp, d_counts,
+	                                       want_bitmap ? d_bitmap : nullptr));
+	return ADAC_OK;
+}
+
+extern "C" adac_status adac_bp_scan_select_compare(adac_bp_layout *a, const void *d_a_blocks, adac_bp_layout *b,
+                                                   const void *d_b_blocks, const uint64_t *d_validity, uint32_t cmp,
+                                                   uint64_t *d_bitmap, uint64_t *d_counts) {
+	return bp_pair_compare(a, d_a_blocks, b, d_b_blocks, d_validity, cmp, d_bitmap, d_counts, true);
+}
+
+extern "C" adac_status adac_bp_scan_count_compare(adac_bp_layout *a, const void *d_a_blocks, adac_bp_layout *b,
+                                                  const void *d_b_blocks, const uint64_t *d_validity, uint32_t cmp,
+                                                  uint64_t *d_counts) {
+	return bp_pair_compare(a, d_a_blocks, b, d_b_blocks, d_validity, cmp, nullptr, d_counts, false);
+}
+
 // ---- BITPACKING compress: device statistics + host decisions (BitpackingState::Flush) + device group writes ----
 
 namespace {

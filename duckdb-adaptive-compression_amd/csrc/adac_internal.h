@@ -303,6 +303,11 @@ hipError_t launch_bp_scan_pair_sum(hipStream_t s, const BpPairColumn &a, const B
                                    uint64_t *d_sums);
 hipError_t launch_bp_scan_pair_gsum(hipStream_t s, const BpPairColumn &v, const BpPairColumn &k, uint64_t ngroups,
                                     const uint64_t *d_validity, uint32_t nkeys, uint64_t *d_sums, uint64_t *d_counts);
+// rows where value(a) <cmp> value(b), cmp an OR of ADAC_CMP_*: d_counts per segment of a and, unless nullptr, d_bitmap
+// in a's element space; the caller has zeroed both
+hipError_t launch_bp_scan_pair_cmp(hipStream_t s, const BpPairColumn &a, const BpPairColumn &b,
+                                   const uint32_t *d_group_seg, uint64_t ngroups, const uint64_t *d_validity,
+                                   uint32_t cmp, uint64_t *d_counts, uint64_t *d_bitmap);
 // scan with selection on the block images (adac_bp_select_gather.inl).  d_group_cnt / d_group_off: ngroups entries of
 // scratch, d_block_tot: ceil(ngroups / 1024) words; *d_total = rows written
 hipError_t launch_bp_gather_selected(hipStream_t s, uint32_t type_size, const void *d_groups, uint64_t ngroups,

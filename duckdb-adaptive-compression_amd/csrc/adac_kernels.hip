@@ -2656,6 +2656,22 @@ hipError_t launch_bp_scan_pair_gsum(hipStream_t st, const BpPairColumn &v, const
 	return hipGetLastError();
 }
 
+hipError_t launch_bp_scan_pair_cmp(hipStream_t st, const BpPairColumn &a, const BpPairColumn &b,
+                                   const uint32_t *d_group_seg, uint64_t ngroups, const uint64_t *d_validity,
+                                   uint32_t cmp, uint64_t *d_counts, uint64_t *d_bitmap) {
+	static_assert(kBpCmpLt == ADAC_CMP_LT && kBpCmpEq == ADAC_CMP_EQ && kBpCmpGt == ADAC_CMP_GT, "cmp bits");
+	if (ngroups == 0) return hipSuccess;
+	dim3 grid;
+	BpPairCmpArgs c;
+	c.p = bp_pair_args(a, b, ngroups, 4, d_validity, d_counts, grid);
+	c.bitmap = reinterpret_cast<unsigned long long *>(d_bitmap);
+	c.cmp = cmp;
+	const BpGroup *ga = static_cast<const BpGroup *>(a.d_groups), *gb = static_cast<const BpGroup *>(b.d_groups);
+	if (d_validity) hipLaunchKernelGGL(k_bp_scan_pair_cmp<true>, grid, dim3(kWorkgroup), 0, st, ga, gb, d_group_seg, c);
+	else hipLaunchKernelGGL(k_bp_scan_pair_cmp<false>, grid, dim3(kWorkgroup), 0, st, ga, gb, d_group_seg, c);
+	return hipGetLastError();
+}
+
 // Scan with selection on BITPACKING blocks (adac_bp_select_gather.inl): counts per metadata group, their exclusive
 // prefix, then the gather at launch_bp_scan's 8 workgroups = 32 waves per CU.
 hipError_t launch_bp_gather_selected(hipStream_t s, uint32_t type_size, const void *d_groups, uint64_t ngroups,

@@ -608,6 +608,33 @@ adac_status adac_bp_scan_group_sum(adac_bp_layout *values, const void *d_value_b
                                    const void *d_key_blocks, const uint64_t *d_validity, uint32_t ngroups,
                                    uint64_t *d_sums, uint64_t *d_counts);
 
+/* Select the rows where value(a) <cmp> value(b): a predicate between two columns of a row (TPC-H Q12's
+ * l_commitdate < l_receiptdate, Q4, Q21, or a = b), evaluated on the block images.  The pair scans' rules above hold:
+ * one context, group tables that agree, blocks pointers, binding, enqueue without synchronising.  A row is selected
+ * iff its bit is set in d_validity (a's element space, out_offs[seg] + row; NULL: every row) and the comparison holds
+ * for the values adac_bp_unpack would write for the two buffers.  The values are compared as mathematical integers,
+ * whatever the two types are: each is widened by its own column's signedness, and a negative value of a signed column
+ * is smaller than every value of an unsigned one — int32 against int32, uint8 against uint64 and int64 against uint64
+ * are all exact.  cmp: an OR of the three bits below, 1 ... 6; 0 or more than 6 is ADAC_ERR_INVALID_ARGUMENT.
+ * d_counts[seg] = rows selected, over a's segments (a's nseg words, written for segments without rows too).
+ * d_bitmap: ceil(value_span(a) / 64) words, fully written by the call, bits of elements no segment covers zero; must
+ * not alias d_validity; usable as the d_validity of any other adac_bp_scan_* call, exactly like
+ * adac_bp_scan_select_between's result.  Nothing is pre-cleared by the caller.  a == b with one buffer is legal: EQ
+ * then selects every wanted row, LT and GT none.  ADAC_ERR_INVALID_ARGUMENT, on the host before anything is
+ * enqueued, beyond the pair scans' checks: cmp out of range; NULL d_counts while a has segments; for the select form
+ * NULL d_bitmap while value_span(a) != 0, or d_bitmap == d_validity.
+ * A group without a wanted row reads nothing.  A group in which both columns are CONSTANT is decided by one
+ * comparison, and one in which each column is CONSTANT or a FOR group whose [frame, frame + 2^width) does not wrap,
+ * and the two intervals are disjoint, from the two headers: no payload byte of either column is read. */
+enum { ADAC_CMP_LT = 1, ADAC_CMP_EQ = 2, ADAC_CMP_GT = 4 }; /* or-able: LE = 3, NE = 5, GE = 6 */
+adac_status adac_bp_scan_select_compare(adac_bp_layout *a, const void *d_a_blocks, adac_bp_layout *b,
+                                        const void *d_b_blocks, const uint64_t *d_validity, uint32_t cmp,
+                                        uint64_t *d_bitmap, uint64_t *d_counts);
+/* the counts alone: no bitmap is written */
+adac_status adac_bp_scan_count_compare(adac_bp_layout *a, const void *d_a_blocks, adac_bp_layout *b,
+                                       const void *d_b_blocks, const uint64_t *d_validity, uint32_t cmp,
+                                       uint64_t *d_counts);
+
 /* Scan with selection on the block images — adac_unpack_selected for BITPACKING, the scan-with-selection half of
  * ColumnSegment::FilterSelection (column_segment.cpp:575-844): d_out receives, densely, as values of the layout's
  * type, the rows whose bit is set in d_bitmap, in group-table order (segment by segment, row order inside a segment);
