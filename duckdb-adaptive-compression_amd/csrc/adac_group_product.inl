@@ -1,8 +1,9 @@
 // adac_group_product.inl — Q1's remaining aggregate: SUM(a * b) GROUP BY key over THREE packed columns of the same table
 // under a selection bitmap (SUM(l_extendedprice * (1 - l_discount)) = 100 SUM(price) - SUM(price * disc) per group with
 // integer decimals).  Included into adac_kernels.hip inside namespace adac::{anonymous}, after adac_sum_product.inl: the
-// chunk walk (adac_chunk_walk.inl), the staging of a second column per wave and product_fast_eligible
-// (adac_sum_product.inl), the key bytes, the bin geometry and the stage structure (adac_group_sum.inl) are shared.
+// chunk walk (adac_chunk_walk.inl), the key reader RwKeys and the fast kernel's shell (adac_group_rw_walk.inl), the staging
+// of a second column per wave and product_fast_eligible (adac_sum_product.inl), the bin geometry and the stage structure
+// (adac_group_sum.inl) are shared.
 //
 // Semantics: each value is widened to 64 bits by its own column's signedness, the product and the sums are taken mod
 // 2^64 (adac_scan_sum_product's rule); key = the key column's value as an unsigned number of its own width, rows whose
@@ -21,7 +22,7 @@
 //                segment fit a byte or all of them are >= ngroups.
 //            A wave walks a quarter of the scan group on its own: `a` on the width-templated register walk (a lane owns
 //            whole 16-byte chunks, the next chunk and its mask words requested a round ahead), the chunks of `b` that
-//            hold the same row run staged in a wave-private LDS buffer as in product_walk, the keys as in group_rw_walk
+//            hold the same row run staged in a wave-private LDS buffer as in product_walk, the keys through RwKeys
 //            (DIRECT out of two dwords, or bytes staged per wave).  No barrier in the loop.  A row costs one exact
 //            32 x 32 -> 64 multiply of (fa + ma) and (fb + mb) and one ds_add_u64 without return into one of 32 bin
 //            sets per wave (+ one ds_add_u32 when counts are wanted: template parameter C).  A masked row adds zero.
@@ -314,29 +315,25 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_product(
 // One QUARTER of a scan group, rows [r0, r1) (r0 a multiple of 128 rows: its bits start a chunk of `a`), walked by ONE
 // wave.  `keys`: the wave's kGroupRwWaveKeyBytes of key bytes (staged form), `bstage`: its kProdWaveChunks chunks of b,
 // `wsum` / `wcnt`: its kGroupPrivateBins x kGroupRwCopies bin words, carried across the quarters the wave walks.
-// Lanes per round: as many as keep the round's key rows inside `keys` (group_rw_walk's LANES) AND its rows of b inside
+// Lanes per round: as many as keep the round's key rows inside `keys` (RwKeys::LANES) AND its rows of b inside
 // `bstage` (product_walk's bound).
 template <int W, bool DIRECT, bool V, bool C>
 __device__ __forceinline__ void group_product_walk(uint32_t r0, uint32_t r1, const adac_segment_desc &ad,
-                                                   const adac_segment_desc &bd, const GroupProductPlan &plan, uint32_t wk,
+                                                   const adac_segment_desc &bd, const GroupProductPlan &plan,
                                                    const uint4 *__restrict__ aseg16, const uint4 *__restrict__ bseg16,
-                                                   const uint32_t *__restrict__ kw32, uint32_t k_last_dword,
+                                                   const RwKeyStream &ks,
                                                    uint32_t ngroups, uint8_t *keys, uint4 *bstage,
                                                    unsigned long long *wsum, uint32_t *wcnt,
                                                    const uint64_t *__restrict__ validity) {
 	constexpr int MAXV = ChunkWindow<W>::MAXV;
-	constexpr int KD = (MAXV + 3 + 3) / 4; // dwords holding MAXV bytes from any byte offset
-	constexpr uint32_t LANES = (kGroupRwWaveRows * W / 128) < 64u ? (kGroupRwWaveRows * W / 128) : 64u;
-	constexpr uint32_t PASSES = ((LANES * 128u / W + 8u + 7u) / 8u + 63u) / 64u; // staged keys: 8-row blocks per round / 64 lanes
 	const uint32_t wb = bd.width, bmask = mask32(wb);
 	uint32_t lanes = ((kProdWaveData - 2u) * 128u) / ((uint32_t)MAXV * wb); // >= 15: MAXV <= 32, wb <= 32
-	lanes = lanes < LANES ? lanes : LANES;
+	lanes = lanes < RwKeys<W, DIRECT>::LANES ? lanes : RwKeys<W, DIRECT>::LANES;
 	const ChunkRange<W> run(r0, r1, ad.count);
 	const uint32_t c0 = run.c0, c1 = run.c1;
 	const uint32_t bclast = (uint32_t)(((uint64_t)bd.count * wb + 127) >> 7) - 1; // last chunk holding data bits of b
 	const uint32_t lane = threadIdx.x & 63u;
 	const bool walker = lane < lanes;
-	const uint32_t kadd4 = plan.keys_overflow ? 0u : plan.kadd_byte * 0x01010101u;
 	unsigned long long *const my_sum = wsum + (lane & (kGroupRwCopies - 1u));
 	uint32_t *const my_cnt = wcnt + (lane & (kGroupRwCopies - 1u));
 	uint32_t L = c0 + lane;
@@ -369,42 +366,14 @@ __device__ __forceinline__ void group_product_walk(uint32_t r0, uint32_t r1, con
 			if (lane + 64u * p < nb) bstage[lane + 64u * p] = bq[p];
 		}
 	};
-	// keys, DIRECT: the two dwords of the key stream holding the keys of the rows that start in chunk Lx
-	auto direct_keys = [&](uint32_t Lx) {
-		uint32_t dw = (chunk_first_row<W>(Lx) * wk) >> 5;
-		dw = dw < k_last_dword ? dw : k_last_dword; // (chunks past the run: any data will do)
-		return make_uint2(kw32[dw], kw32[dw + 1]);   // dw + 1 <= last data dword + 1: inside the padding word
-	};
-	// keys, staged: from the 8-row block the round starts in
-	auto round_keys = [&](uint32_t rc, uint32_t &kb0, uint32_t &nblocks) {
-		const uint32_t rows_lo = chunk_first_row<W>(rc);
-		kb0 = rows_lo & ~7u;
-		uint32_t rows_hi = chunk_first_row<W>(rc + lanes);
-		rows_hi = rows_hi < r1 ? rows_hi : r1;
-		nblocks = rows_hi > kb0 ? (rows_hi - kb0 + 7u) >> 3 : 0u;
-	};
 	const uint32_t *b32 = reinterpret_cast<const uint32_t *>(bstage);
 	uint32_t bc0 = 0, nb = 0;
 	uint4 bq[2];
 	round_b(c0, bc0, nb);
 	load_b(bc0, bq);
 	store_b(bq, nb);
-	uint2 kq = make_uint2(0u, 0u);
-	uint32_t kb0 = 0, nblocks = 0;
-	uint32_t kd[PASSES][3], ksh[PASSES];
-	if (DIRECT) {
-		kq = direct_keys(run.clamp(L));
-	} else { // prologue: the first round's key bytes
-		round_keys(c0, kb0, nblocks);
-#pragma unroll
-		for (uint32_t p = 0; p < PASSES; p++) group_rw_key_load(kw32, (kb0 >> 3) + lane + 64u * p, wk, k_last_dword, kd[p], ksh[p]);
-#pragma unroll
-		for (uint32_t p = 0; p < PASSES; p++) {
-			if (lane + 64u * p < nblocks) {
-				group_rw_key_store(kd[p], ksh[p], wk, kadd4, plan.keys_overflow, reinterpret_cast<uint2 *>(keys) + lane + 64u * p);
-			}
-		}
-	}
+	RwKeys<W, DIRECT> k(ks, plan.kadd_byte, plan.keys_overflow, keys, r1, lanes);
+	k.first(c0, run.clamp(L));
 	for (uint32_t round0 = c0; round0 < c1; round0 += lanes, L += lanes) { // uniform trip count
 		// requested before this round is walked: the next chunk of a, its mask words, the next round's chunks of b and keys
 		uint4 qn;
@@ -415,15 +384,7 @@ __device__ __forceinline__ void group_product_walk(uint32_t r0, uint32_t r1, con
 		uint32_t bc0n = 0, nbn = 0;
 		round_b(round0 + lanes, bc0n, nbn);
 		load_b(bc0n, bq);
-		uint2 kqn = make_uint2(0u, 0u);
-		uint32_t kb0n = 0, nblocksn = 0;
-		if (DIRECT) {
-			kqn = direct_keys(run.clamp(L + lanes));
-		} else {
-			round_keys(round0 + lanes, kb0n, nblocksn);
-#pragma unroll
-			for (uint32_t p = 0; p < PASSES; p++) group_rw_key_load(kw32, (kb0n >> 3) + lane + 64u * p, wk, k_last_dword, kd[p], ksh[p]);
-		}
+		k.request(round0 + lanes, run.clamp(L + lanes));
 		if (walker && L < c1) {
 			const ChunkWindow<W> cw(q, e, L, r1);
 			const uint32_t have = cw.have();
@@ -431,20 +392,8 @@ __device__ __forceinline__ void group_product_walk(uint32_t r0, uint32_t r1, con
 			uint32_t vb = have >= 32u ? 0xffffffffu : ((1u << have) - 1u);
 			if (V) vb &= (uint32_t)vmask.window(vm0, vm1, cw.i0 < r1 ? cw.i0 : r1);
 			const uint32_t bbit = cw.i0 * wb - 128u * bc0; // row i0 of b inside the staged chunks
-			uint32_t kwin = 0;  // DIRECT: the keys of rows i0 .. from bit 0
-			uint32_t kn[KD];    // staged: their bytes
-			if (DIRECT) {
-				kwin = __builtin_amdgcn_alignbit(kq.y, kq.x, (cw.i0 * wk) & 31u);
-			} else {
-				// the key bytes of rows [i0, i0 + MAXV): dword reads from the byte offset rounded down, one v_alignbyte each
-				const uint32_t kofs = cw.i0 - kb0;
-				const uint32_t *k32 = reinterpret_cast<const uint32_t *>(keys) + (kofs >> 2);
-				uint32_t raw[KD + 1];
-#pragma unroll
-				for (int i = 0; i <= KD; i++) raw[i] = k32[i];
-#pragma unroll
-				for (int i = 0; i < KD; i++) kn[i] = __builtin_amdgcn_alignbyte(raw[i + 1], raw[i], kofs & 3u);
-			}
+			uint32_t kwin, kn[RwKeys<W, DIRECT>::KD]; // DIRECT: the keys of rows i0 .. from bit 0; staged: their bytes
+			k.window(cw.i0, kwin, kn);
 			// eight rows at a time: their fields of b are read together (eight LDS round trips in flight), then consumed
 #pragma unroll
 			for (int j0 = 0; j0 < MAXV; j0 += 8) {
@@ -458,13 +407,7 @@ __device__ __forceinline__ void group_product_walk(uint32_t r0, uint32_t r1, con
 					if (j0 + u < MAXV) {
 						const int j = j0 + u;
 						const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)vb, (uint32_t)j, 1u); // 0 / -1
-						uint32_t key;
-						if (DIRECT) {
-							key = plan.keys_overflow ? 255u : __builtin_amdgcn_ubfe(kwin, (uint32_t)j * wk, wk) + plan.kadd_byte;
-						} else {
-							key = (kn[j >> 2] >> (8 * (j & 3))) & 0xffu;
-						}
-						const uint32_t bin = key < ngroups ? key : ngroups;
+						const uint32_t bin = k.bin(kwin, kn, j, ngroups);
 						const uint32_t x = (field_of<W>(cw.nrm, j) + plan.ma) & m; // a masked row: 0 x y = 0
 						const uint32_t y = fb[u] + plan.mb;
 						atomicAdd(my_sum + bin * kGroupRwCopies, (unsigned long long)x * y); // exact 32 x 32 -> 64; ds_add_u64, no return
@@ -477,19 +420,9 @@ __device__ __forceinline__ void group_product_walk(uint32_t r0, uint32_t r1, con
 		e = en;
 		vm0 = vn0;
 		vm1 = vn1;
-		kq = kqn;
 		store_b(bq, nbn); // after this round's reads of the buffer (LDS operations of one wave execute in order)
 		bc0 = bc0n;
-		if (!DIRECT) {
-#pragma unroll
-			for (uint32_t p = 0; p < PASSES; p++) {
-				if (lane + 64u * p < nblocksn) {
-					group_rw_key_store(kd[p], ksh[p], wk, kadd4, plan.keys_overflow,
-					                   reinterpret_cast<uint2 *>(keys) + lane + 64u * p);
-				}
-			}
-			kb0 = kb0n;
-		}
+		k.commit();
 	}
 }
 
@@ -527,47 +460,18 @@ __global__ __launch_bounds__(kWorkgroup, kGroupProductRwResident) void k_group_p
 			skipped++;
 			continue;
 		}
-		// the group in four contiguous quarters of whole 128-row units (a quarter's bits start a chunk of a), one per wave
-		const uint32_t per = (((g.n + kWaves - 1u) / kWaves) + 127u) & ~127u;
-		const uint32_t q0 = wave * per;
-		if (q0 >= g.n) continue; // uniform per wave
-		const uint32_t r0 = g.first + q0, r1 = g.first + (q0 + per < g.n ? q0 + per : g.n);
+		const RwQuarter qr(g, wave);
+		if (qr.empty()) continue; // uniform per wave
 		const uint4 *aseg16 = reinterpret_cast<const uint4 *>(awords + g.d.word_off);
 		const uint4 *bseg16 = reinterpret_cast<const uint4 *>(bwords + bd.word_off);
-		const uint32_t *kw32 = reinterpret_cast<const uint32_t *>(kwords + kd.word_off);
-		const uint32_t wk = kd.width;
-		const uint32_t k_last = (uint32_t)(((uint64_t)kd.count * wk + 31) >> 5) - 1u;
-		const uint32_t maxv = (128u + g.d.width - 1u) / g.d.width;
-		if (maxv * wk <= 32u) { // uniform: the keys of a chunk's rows fit one dword
-			dispatch_width_4_32(g.d.width, [&](auto wc) __attribute__((always_inline)) {
-				group_product_walk<decltype(wc)::value, true, V, C>(r0, r1, g.d, bd, plan, wk, aseg16, bseg16, kw32, k_last, ngroups,
-				                                                    keys[wave], bstage[wave], sums + wave * kSlots,
-				                                                    cnts + (C ? wave * kSlots : 0u), validity);
-			});
-		} else {
-			dispatch_width_4_32(g.d.width, [&](auto wc) __attribute__((always_inline)) {
-				group_product_walk<decltype(wc)::value, false, V, C>(r0, r1, g.d, bd, plan, wk, aseg16, bseg16, kw32, k_last, ngroups,
-				                                                     keys[wave], bstage[wave], sums + wave * kSlots,
-				                                                     cnts + (C ? wave * kSlots : 0u), validity);
-			});
-		}
+		const RwKeyStream ks(kwords, kd);
+		group_rw_dispatch(g.d.width, ks.direct(g.d.width), [&](auto wc, auto direct) __attribute__((always_inline)) {
+			group_product_walk<decltype(wc)::value, decltype(direct)::value, V, C>(
+			    qr.r0, qr.r1, g.d, bd, plan, aseg16, bseg16, ks, ngroups, keys[wave], bstage[wave],
+			    sums + wave * kSlots, cnts + (C ? wave * kSlots : 0u), validity);
+		});
 	}
 	if (skipped && tid == 0u) atomicAdd(fallback, (unsigned long long)skipped);
-	__syncthreads();
-	// one partial per bin and workgroup: kWaves x kGroupRwCopies bin words per bin, one per lane of the first two waves
-	static_assert(kWaves * kGroupRwCopies == 128u, "two waves read a bin's words");
-	if (tid < 128u) { // uniform per wave
-		const uint32_t w = tid >> 5, set = tid & 31u;
-		for (uint32_t b = 0; b < nbins; b++) { // uniform
-			const uint64_t s = wave_sum((uint64_t)sums[w * kSlots + b * kGroupRwCopies + set]);
-			const uint64_t c = C ? wave_sum((uint64_t)cnts[w * kSlots + b * kGroupRwCopies + set]) : 0ull;
-			if (lane == 0u) {
-				red[wave][2u * b] = s;
-				red[wave][2u * b + 1u] = c;
-			}
-		}
-	}
-	__syncthreads();
-	unsigned long long *__restrict__ mine = partial + (uint64_t)blockIdx.x * 2u * nbins;
-	if (tid < 2u * nbins) mine[tid] = red[0][tid] + red[1][tid];
+	// one partial {sum, count} per bin and workgroup
+	group_rw_pairs_out<C>(sums, cnts, red, nbins, partial + (uint64_t)blockIdx.x * 2u * nbins);
 }

@@ -4,7 +4,8 @@
 // the first term is adac_scan_group_sum_valid's, the next two are adac_scan_group_sum_product's, the fourth is this
 // file's.  Included into adac_kernels.hip inside namespace adac::{anonymous}, after adac_group_product.inl: the chunk
 // walk (adac_chunk_walk.inl), product_frame (adac_sum_product.inl), the a / b / key part of the eligibility rule
-// (group_product_rw_eligible), the key bytes, the bin geometry and the stage structure (adac_group_sum.inl) are shared;
+// (group_product_rw_eligible), the key reader RwKeys and the fast kernel's shell (adac_group_rw_walk.inl), the bin geometry
+// and the stage structure (adac_group_sum.inl) are shared;
 // no existing kernel calls into this file.
 //
 // Semantics: adac_scan_group_sum_product's with one more factor.  Each value is widened to 64 bits by its own column's
@@ -24,9 +25,10 @@
 //                0 <= frame and frame + 2^wc - 1 <= 2^32 - 1.
 //            So all three widened values are unsigned 32-bit numbers for EVERY field of the segment.  (Q1: price at
 //            frame + 24 bits, discount 0..10 in 4 bits, tax 0..8 in 4 bits, six groups in 3 bits: fast.)
-//            group_product_walk with a second staged column: `a` on the width-templated register walk, the chunks of
+//            group_product_walk's structure with a second staged column: `a` on the width-templated register walk,
+//            the chunks of
 //            b AND of c that hold the round's rows each staged in a wave-private LDS buffer (requested a round ahead,
-//            stored after the round's reads: no barrier in the loop), keys DIRECT out of two dwords or as staged
+//            stored after the round's reads: no barrier in the loop), keys through RwKeys: DIRECT or staged
 //            bytes.  Lanes per round: as many as keep the round's key rows inside the key bytes and its rows of BOTH
 //            staged columns inside their buffers — the bound of group_product_walk taken at the wider of wb and wc.
 //            A row costs x = (fa + ma) & m, y = fb + mb, z = fc + mc as 32-bit numbers, the exact 64-bit x y, then
@@ -327,35 +329,31 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_product3(
 // wave: group_product_walk with a second staged column.  `keys`: the wave's kGroupRwWaveKeyBytes of key bytes (staged
 // form), `bstage` / `cstage`: its kProdWaveChunks chunks of b and of c, `wsum` / `wcnt`: its kGroupPrivateBins x
 // kGroupRwCopies bin words, carried across the quarters the wave walks.
-// Lanes per round: as many as keep the round's key rows inside `keys` (group_rw_walk's LANES) AND its rows of b inside
+// Lanes per round: as many as keep the round's key rows inside `keys` (RwKeys::LANES) AND its rows of b inside
 // `bstage` AND its rows of c inside `cstage`: product_walk's bound at wmax = the wider of wb and wc (rows <= lanes *
 // MAXV, so the bits of either column are <= 126 chunks, which from any bit offset of the first chunk lie in 128).
 template <int W, bool DIRECT, bool V, bool C>
 __device__ __forceinline__ void group_product3_walk(uint32_t r0, uint32_t r1, const adac_segment_desc &ad,
                                                     const adac_segment_desc &bd, const adac_segment_desc &cd,
-                                                    const GroupProduct3Plan &plan, uint32_t wk,
+                                                    const GroupProduct3Plan &plan,
                                                     const uint4 *__restrict__ aseg16, const uint4 *__restrict__ bseg16,
-                                                    const uint4 *__restrict__ cseg16, const uint32_t *__restrict__ kw32,
-                                                    uint32_t k_last_dword, uint32_t ngroups, uint8_t *keys, uint4 *bstage,
+                                                    const uint4 *__restrict__ cseg16, const RwKeyStream &ks,
+                                                    uint32_t ngroups, uint8_t *keys, uint4 *bstage,
                                                     uint4 *cstage, unsigned long long *wsum, uint32_t *wcnt,
                                                     const uint64_t *__restrict__ validity) {
 	constexpr int MAXV = ChunkWindow<W>::MAXV;
-	constexpr int KD = (MAXV + 3 + 3) / 4; // dwords holding MAXV bytes from any byte offset
-	constexpr uint32_t LANES = (kGroupRwWaveRows * W / 128) < 64u ? (kGroupRwWaveRows * W / 128) : 64u;
-	constexpr uint32_t PASSES = ((LANES * 128u / W + 8u + 7u) / 8u + 63u) / 64u; // staged keys: 8-row blocks per round / 64 lanes
 	constexpr int BATCH = 4;               // rows whose fields of b and c are read together (2 x BATCH LDS reads in flight)
 	const uint32_t wb = bd.width, bmask = mask32(wb);
 	const uint32_t wc = cd.width, cmask = mask32(wc);
 	const uint32_t wmax = wb > wc ? wb : wc;
 	uint32_t lanes = ((kProdWaveData - 2u) * 128u) / ((uint32_t)MAXV * wmax); // >= 15: MAXV <= 32, wmax <= 32
-	lanes = lanes < LANES ? lanes : LANES;
+	lanes = lanes < RwKeys<W, DIRECT>::LANES ? lanes : RwKeys<W, DIRECT>::LANES;
 	const ChunkRange<W> run(r0, r1, ad.count);
 	const uint32_t c0 = run.c0, c1 = run.c1;
 	const uint32_t bclast = (uint32_t)(((uint64_t)bd.count * wb + 127) >> 7) - 1; // last chunk holding data bits of b
 	const uint32_t cclast = (uint32_t)(((uint64_t)cd.count * wc + 127) >> 7) - 1; // ... of c
 	const uint32_t lane = threadIdx.x & 63u;
 	const bool walker = lane < lanes;
-	const uint32_t kadd4 = plan.g.keys_overflow ? 0u : plan.g.kadd_byte * 0x01010101u;
 	unsigned long long *const my_sum = wsum + (lane & (kGroupRwCopies - 1u));
 	uint32_t *const my_cnt = wcnt + (lane & (kGroupRwCopies - 1u));
 	uint32_t L = c0 + lane;
@@ -388,20 +386,6 @@ __device__ __forceinline__ void group_product3_walk(uint32_t r0, uint32_t r1, co
 			if (lane + 64u * p < ns) stage[lane + 64u * p] = sq[p];
 		}
 	};
-	// keys, DIRECT: the two dwords of the key stream holding the keys of the rows that start in chunk Lx
-	auto direct_keys = [&](uint32_t Lx) {
-		uint32_t dw = (chunk_first_row<W>(Lx) * wk) >> 5;
-		dw = dw < k_last_dword ? dw : k_last_dword; // (chunks past the run: any data will do)
-		return make_uint2(kw32[dw], kw32[dw + 1]);   // dw + 1 <= last data dword + 1: inside the padding word
-	};
-	// keys, staged: from the 8-row block the round starts in
-	auto round_keys = [&](uint32_t rc, uint32_t &kb0, uint32_t &nblocks) {
-		const uint32_t rows_lo = chunk_first_row<W>(rc);
-		kb0 = rows_lo & ~7u;
-		uint32_t rows_hi = chunk_first_row<W>(rc + lanes);
-		rows_hi = rows_hi < r1 ? rows_hi : r1;
-		nblocks = rows_hi > kb0 ? (rows_hi - kb0 + 7u) >> 3 : 0u;
-	};
 	const uint32_t *b32 = reinterpret_cast<const uint32_t *>(bstage);
 	const uint32_t *c32 = reinterpret_cast<const uint32_t *>(cstage);
 	uint32_t bc0 = 0, nb = 0, cc0 = 0, nc = 0;
@@ -412,22 +396,8 @@ __device__ __forceinline__ void group_product3_walk(uint32_t r0, uint32_t r1, co
 	load_s(cseg16, cc0, cclast, cq);
 	store_s(bstage, bq, nb);
 	store_s(cstage, cq, nc);
-	uint2 kq = make_uint2(0u, 0u);
-	uint32_t kb0 = 0, nblocks = 0;
-	uint32_t kd[PASSES][3], ksh[PASSES];
-	if (DIRECT) {
-		kq = direct_keys(run.clamp(L));
-	} else { // prologue: the first round's key bytes
-		round_keys(c0, kb0, nblocks);
-#pragma unroll
-		for (uint32_t p = 0; p < PASSES; p++) group_rw_key_load(kw32, (kb0 >> 3) + lane + 64u * p, wk, k_last_dword, kd[p], ksh[p]);
-#pragma unroll
-		for (uint32_t p = 0; p < PASSES; p++) {
-			if (lane + 64u * p < nblocks) {
-				group_rw_key_store(kd[p], ksh[p], wk, kadd4, plan.g.keys_overflow, reinterpret_cast<uint2 *>(keys) + lane + 64u * p);
-			}
-		}
-	}
+	RwKeys<W, DIRECT> k(ks, plan.g.kadd_byte, plan.g.keys_overflow, keys, r1, lanes);
+	k.first(c0, run.clamp(L));
 	for (uint32_t round0 = c0; round0 < c1; round0 += lanes, L += lanes) { // uniform trip count
 		// requested before this round is walked: the next chunk of a, its mask words, the next round's chunks of b, c and keys
 		uint4 qn;
@@ -440,15 +410,7 @@ __device__ __forceinline__ void group_product3_walk(uint32_t r0, uint32_t r1, co
 		round_s(round0 + lanes, wc, cc0n, ncn);
 		load_s(bseg16, bc0n, bclast, bq);
 		load_s(cseg16, cc0n, cclast, cq);
-		uint2 kqn = make_uint2(0u, 0u);
-		uint32_t kb0n = 0, nblocksn = 0;
-		if (DIRECT) {
-			kqn = direct_keys(run.clamp(L + lanes));
-		} else {
-			round_keys(round0 + lanes, kb0n, nblocksn);
-#pragma unroll
-			for (uint32_t p = 0; p < PASSES; p++) group_rw_key_load(kw32, (kb0n >> 3) + lane + 64u * p, wk, k_last_dword, kd[p], ksh[p]);
-		}
+		k.request(round0 + lanes, run.clamp(L + lanes));
 		if (walker && L < c1) {
 			const ChunkWindow<W> cw(q, e, L, r1);
 			const uint32_t have = cw.have();
@@ -457,20 +419,8 @@ __device__ __forceinline__ void group_product3_walk(uint32_t r0, uint32_t r1, co
 			if (V) vb &= (uint32_t)vmask.window(vm0, vm1, cw.i0 < r1 ? cw.i0 : r1);
 			const uint32_t bbit = cw.i0 * wb - 128u * bc0; // row i0 of b inside its staged chunks
 			const uint32_t cbit = cw.i0 * wc - 128u * cc0; // ... of c
-			uint32_t kwin = 0;  // DIRECT: the keys of rows i0 .. from bit 0
-			uint32_t kn[KD];    // staged: their bytes
-			if (DIRECT) {
-				kwin = __builtin_amdgcn_alignbit(kq.y, kq.x, (cw.i0 * wk) & 31u);
-			} else {
-				// the key bytes of rows [i0, i0 + MAXV): dword reads from the byte offset rounded down, one v_alignbyte each
-				const uint32_t kofs = cw.i0 - kb0;
-				const uint32_t *k32 = reinterpret_cast<const uint32_t *>(keys) + (kofs >> 2);
-				uint32_t raw[KD + 1];
-#pragma unroll
-				for (int i = 0; i <= KD; i++) raw[i] = k32[i];
-#pragma unroll
-				for (int i = 0; i < KD; i++) kn[i] = __builtin_amdgcn_alignbyte(raw[i + 1], raw[i], kofs & 3u);
-			}
+			uint32_t kwin, kn[RwKeys<W, DIRECT>::KD]; // DIRECT: the keys of rows i0 .. from bit 0; staged: their bytes
+			k.window(cw.i0, kwin, kn);
 			// BATCH rows at a time: their fields of b and c are read together, then consumed
 #pragma unroll
 			for (int j0 = 0; j0 < MAXV; j0 += BATCH) {
@@ -487,13 +437,7 @@ __device__ __forceinline__ void group_product3_walk(uint32_t r0, uint32_t r1, co
 					if (j0 + u < MAXV) {
 						const int j = j0 + u;
 						const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)vb, (uint32_t)j, 1u); // 0 / -1
-						uint32_t key;
-						if (DIRECT) {
-							key = plan.g.keys_overflow ? 255u : __builtin_amdgcn_ubfe(kwin, (uint32_t)j * wk, wk) + plan.g.kadd_byte;
-						} else {
-							key = (kn[j >> 2] >> (8 * (j & 3))) & 0xffu;
-						}
-						const uint32_t bin = key < ngroups ? key : ngroups;
+						const uint32_t bin = k.bin(kwin, kn, j, ngroups);
 						const uint32_t x = (field_of<W>(cw.nrm, j) + plan.g.ma) & m; // a masked row: 0 x y z = 0
 						const uint32_t y = fb[u] + plan.g.mb;
 						const uint32_t z = fc[u] + plan.mc;
@@ -509,21 +453,11 @@ __device__ __forceinline__ void group_product3_walk(uint32_t r0, uint32_t r1, co
 		e = en;
 		vm0 = vn0;
 		vm1 = vn1;
-		kq = kqn;
+		k.commit(); // before the columns' stores (after them the unmasked kernels spill one SGPR more: DESIGN.md §7)
 		store_s(bstage, bq, nbn); // after this round's reads of the buffers (LDS operations of one wave execute in order)
 		store_s(cstage, cq, ncn);
 		bc0 = bc0n;
 		cc0 = cc0n;
-		if (!DIRECT) {
-#pragma unroll
-			for (uint32_t p = 0; p < PASSES; p++) {
-				if (lane + 64u * p < nblocksn) {
-					group_rw_key_store(kd[p], ksh[p], wk, kadd4, plan.g.keys_overflow,
-					                   reinterpret_cast<uint2 *>(keys) + lane + 64u * p);
-				}
-			}
-			kb0 = kb0n;
-		}
 	}
 }
 
@@ -566,50 +500,19 @@ __global__ __launch_bounds__(kWorkgroup, kGroupProduct3RwResident) void k_group_
 			skipped++;
 			continue;
 		}
-		// the group in four contiguous quarters of whole 128-row units (a quarter's bits start a chunk of a), one per wave
-		const uint32_t per = (((g.n + kWaves - 1u) / kWaves) + 127u) & ~127u;
-		const uint32_t q0 = wave * per;
-		if (q0 >= g.n) continue; // uniform per wave
-		const uint32_t r0 = g.first + q0, r1 = g.first + (q0 + per < g.n ? q0 + per : g.n);
+		const RwQuarter qr(g, wave);
+		if (qr.empty()) continue; // uniform per wave
 		const uint4 *aseg16 = reinterpret_cast<const uint4 *>(awords + g.d.word_off);
 		const uint4 *bseg16 = reinterpret_cast<const uint4 *>(bwords + bd.word_off);
 		const uint4 *cseg16 = reinterpret_cast<const uint4 *>(cwords + cd.word_off);
-		const uint32_t *kw32 = reinterpret_cast<const uint32_t *>(kwords + kd.word_off);
-		const uint32_t wk = kd.width;
-		const uint32_t k_last = (uint32_t)(((uint64_t)kd.count * wk + 31) >> 5) - 1u;
-		const uint32_t maxv = (128u + g.d.width - 1u) / g.d.width;
-		if (maxv * wk <= 32u) { // uniform: the keys of a chunk's rows fit one dword
-			dispatch_width_4_32(g.d.width, [&](auto wt) __attribute__((always_inline)) {
-				group_product3_walk<decltype(wt)::value, true, V, C>(r0, r1, g.d, bd, cd, plan, wk, aseg16, bseg16, cseg16, kw32,
-				                                                     k_last, ngroups, keys[wave], bstage[wave], cstage[wave],
-				                                                     sums + wave * kSlots, cnts + (C ? wave * kSlots : 0u),
-				                                                     validity);
-			});
-		} else {
-			dispatch_width_4_32(g.d.width, [&](auto wt) __attribute__((always_inline)) {
-				group_product3_walk<decltype(wt)::value, false, V, C>(r0, r1, g.d, bd, cd, plan, wk, aseg16, bseg16, cseg16, kw32,
-				                                                      k_last, ngroups, keys[wave], bstage[wave], cstage[wave],
-				                                                      sums + wave * kSlots, cnts + (C ? wave * kSlots : 0u),
-				                                                      validity);
-			});
-		}
+		const RwKeyStream ks(kwords, kd);
+		group_rw_dispatch(g.d.width, ks.direct(g.d.width), [&](auto wt, auto direct) __attribute__((always_inline)) {
+			group_product3_walk<decltype(wt)::value, decltype(direct)::value, V, C>(
+			    qr.r0, qr.r1, g.d, bd, cd, plan, aseg16, bseg16, cseg16, ks, ngroups, keys[wave],
+			    bstage[wave], cstage[wave], sums + wave * kSlots, cnts + (C ? wave * kSlots : 0u), validity);
+		});
 	}
 	if (skipped && tid == 0u) atomicAdd(fallback, (unsigned long long)skipped);
-	__syncthreads();
-	// one partial per bin and workgroup: kWaves x kGroupRwCopies bin words per bin, one per lane of the first two waves
-	static_assert(kWaves * kGroupRwCopies == 128u, "two waves read a bin's words");
-	if (tid < 128u) { // uniform per wave
-		const uint32_t w = tid >> 5, set = tid & 31u;
-		for (uint32_t b = 0; b < nbins; b++) { // uniform
-			const uint64_t s = wave_sum((uint64_t)sums[w * kSlots + b * kGroupRwCopies + set]);
-			const uint64_t c = C ? wave_sum((uint64_t)cnts[w * kSlots + b * kGroupRwCopies + set]) : 0ull;
-			if (lane == 0u) {
-				red[wave][2u * b] = s;
-				red[wave][2u * b + 1u] = c;
-			}
-		}
-	}
-	__syncthreads();
-	unsigned long long *__restrict__ mine = partial + (uint64_t)blockIdx.x * 2u * nbins;
-	if (tid < 2u * nbins) mine[tid] = red[0][tid] + red[1][tid];
+	// one partial {sum, count} per bin and workgroup
+	group_rw_pairs_out<C>(sums, cnts, red, nbins, partial + (uint64_t)blockIdx.x * 2u * nbins);
 }

@@ -4,8 +4,8 @@
 // price, the keys and the mask once each: 146 packed bits per row at Q1's widths against 42 here.
 // Included into adac_kernels.hip inside namespace adac::{anonymous}, after adac_group_product3.inl: the chunk walk
 // (adac_chunk_walk.inl), product_frame (adac_sum_product.inl), the a / b / c / key part of the eligibility rule
-// (group_product3_rw_eligible), the key bytes and the stage structure (adac_group_sum.inl) are shared as they are; no
-// existing kernel calls into this file.
+// (group_product3_rw_eligible), the key reader RwKeys and the fast kernel's shell (adac_group_rw_walk.inl) and the stage
+// structure (adac_group_sum.inl) are shared as they are; no existing kernel calls into this file.
 //
 // Semantics, term by term those of the calls it replaces: each value is widened to 64 bits by its own column's
 // signedness, products and sums are taken mod 2^64; key = the key column's value as an unsigned number of its own
@@ -16,10 +16,12 @@
 // five types and ngroups alone, so both kernels (and the host mirror, bench_configs.group_q1_form_groups) agree:
 //   fast     (k_group_q1_rw)  group_product3_rw_eligible(a, b, c, keys) AND the same for q as for c: linear (or raw and
 //            unsigned), 1 <= wq <= 32, below 2^31 bits, 0 <= frame and frame + 2^wq - 1 <= 2^32 - 1.  So all four values
-//            are unsigned 32-bit numbers for EVERY field of the segment.  group_product3_walk with a third staged
+//            are unsigned 32-bit numbers for EVERY field of the segment.  group_product3_walk's structure with a third
+//            staged
 //            column: `a` on the width-templated register walk, the chunks of b, c AND q that hold the round's rows each
 //            staged in a wave-private LDS buffer (requested a round ahead, stored after the round's reads: no barrier
-//            in the loop), keys DIRECT or as staged bytes.  Lanes per round: group_product3_walk's bound at the widest
+//            in the loop), keys through RwKeys (DIRECT or staged bytes).  Lanes per round: group_product3_walk's bound
+//            at the widest
 //            of wb, wc and wq.  A row costs x, y, z, v as 32-bit numbers, x, y and v ANDed with the row's 0 / -1 mask
 //            (masking x alone would leave SUM(b), SUM(q) and COUNT standing; z meets x only), the exact x y and x z, (x y) z as
 //            product3 makes it, and six ds_add_u64 + one ds_add_u32 without return.
@@ -356,17 +358,14 @@ constexpr uint32_t kGroupQ1RwResident = 2;
 template <int W, bool DIRECT, bool V>
 __device__ __forceinline__ void group_q1_walk(uint32_t r0, uint32_t r1, const adac_segment_desc &ad,
                                               const adac_segment_desc &bd, const adac_segment_desc &cd,
-                                              const adac_segment_desc &qd, const GroupQ1Plan &plan, uint32_t wk,
+                                              const adac_segment_desc &qd, const GroupQ1Plan &plan,
                                               const uint4 *__restrict__ aseg16, const uint4 *__restrict__ bseg16,
                                               const uint4 *__restrict__ cseg16, const uint4 *__restrict__ qseg16,
-                                              const uint32_t *__restrict__ kw32, uint32_t k_last_dword, uint32_t ngroups,
+                                              const RwKeyStream &ks, uint32_t ngroups,
                                               uint8_t *keys, uint4 *bstage, uint4 *cstage, uint4 *qstage,
                                               unsigned long long *wsum, uint32_t *wcnt,
                                               const uint64_t *__restrict__ validity) {
 	constexpr int MAXV = ChunkWindow<W>::MAXV;
-	constexpr int KD = (MAXV + 3 + 3) / 4; // dwords holding MAXV bytes from any byte offset
-	constexpr uint32_t LANES = (kGroupRwWaveRows * W / 128) < 64u ? (kGroupRwWaveRows * W / 128) : 64u;
-	constexpr uint32_t PASSES = ((LANES * 128u / W + 8u + 7u) / 8u + 63u) / 64u; // staged keys: 8-row blocks per round / 64 lanes
 	constexpr int BATCH = 4;               // rows whose fields of b, c and q are read together (3 x BATCH LDS reads in flight)
 	constexpr uint32_t kSlots = kGroupPrivateBins * kGroupQ1RwCopies;
 	const GroupProductPlan &kp = plan.g.g;
@@ -376,7 +375,7 @@ __device__ __forceinline__ void group_q1_walk(uint32_t r0, uint32_t r1, const ad
 	uint32_t wmax = wb > wc ? wb : wc;
 	wmax = wmax > wq ? wmax : wq;
 	uint32_t lanes = ((kProdWaveData - 2u) * 128u) / ((uint32_t)MAXV * wmax); // >= 15: MAXV <= 32, wmax <= 32
-	lanes = lanes < LANES ? lanes : LANES;
+	lanes = lanes < RwKeys<W, DIRECT>::LANES ? lanes : RwKeys<W, DIRECT>::LANES;
 	const ChunkRange<W> run(r0, r1, ad.count);
 	const uint32_t c0 = run.c0, c1 = run.c1;
 	const uint32_t bclast = (uint32_t)(((uint64_t)bd.count * wb + 127) >> 7) - 1; // last chunk holding data bits of b
@@ -384,7 +383,6 @@ __device__ __forceinline__ void group_q1_walk(uint32_t r0, uint32_t r1, const ad
 	const uint32_t qclast = (uint32_t)(((uint64_t)qd.count * wq + 127) >> 7) - 1; // ... of q
 	const uint32_t lane = threadIdx.x & 63u;
 	const bool walker = lane < lanes;
-	const uint32_t kadd4 = kp.keys_overflow ? 0u : kp.kadd_byte * 0x01010101u;
 	unsigned long long *const my_sum = wsum + (lane & (kGroupQ1RwCopies - 1u));
 	uint32_t *const my_cnt = wcnt + (lane & (kGroupQ1RwCopies - 1u));
 	uint32_t L = c0 + lane;
@@ -414,20 +412,6 @@ __device__ __forceinline__ void group_q1_walk(uint32_t r0, uint32_t r1, const ad
 		if (lane < ns) stage[lane] = s_lo;
 		if (lane + 64u < ns) stage[lane + 64u] = s_hi;
 	};
-	// keys, DIRECT: the two dwords of the key stream holding the keys of the rows that start in chunk Lx
-	auto direct_keys = [&](uint32_t Lx) {
-		uint32_t dw = (chunk_first_row<W>(Lx) * wk) >> 5;
-		dw = dw < k_last_dword ? dw : k_last_dword; // (chunks past the run: any data will do)
-		return make_uint2(kw32[dw], kw32[dw + 1]);   // dw + 1 <= last data dword + 1: inside the padding word
-	};
-	// keys, staged: from the 8-row block the round starts in
-	auto round_keys = [&](uint32_t rc, uint32_t &kb0, uint32_t &nblocks) {
-		const uint32_t rows_lo = chunk_first_row<W>(rc);
-		kb0 = rows_lo & ~7u;
-		uint32_t rows_hi = chunk_first_row<W>(rc + lanes);
-		rows_hi = rows_hi < r1 ? rows_hi : r1;
-		nblocks = rows_hi > kb0 ? (rows_hi - kb0 + 7u) >> 3 : 0u;
-	};
 	const uint32_t *b32 = reinterpret_cast<const uint32_t *>(bstage);
 	const uint32_t *c32 = reinterpret_cast<const uint32_t *>(cstage);
 	const uint32_t *q32 = reinterpret_cast<const uint32_t *>(qstage);
@@ -442,22 +426,8 @@ __device__ __forceinline__ void group_q1_walk(uint32_t r0, uint32_t r1, const ad
 	store_s(bstage, bq0, bq1, nb);
 	store_s(cstage, cq0, cq1, nc);
 	store_s(qstage, qq0, qq1, nq);
-	uint2 kq = make_uint2(0u, 0u);
-	uint32_t kb0 = 0, nblocks = 0;
-	uint32_t kd[PASSES][3], ksh[PASSES];
-	if (DIRECT) {
-		kq = direct_keys(run.clamp(L));
-	} else { // prologue: the first round's key bytes
-		round_keys(c0, kb0, nblocks);
-#pragma unroll
-		for (uint32_t p = 0; p < PASSES; p++) group_rw_key_load(kw32, (kb0 >> 3) + lane + 64u * p, wk, k_last_dword, kd[p], ksh[p]);
-#pragma unroll
-		for (uint32_t p = 0; p < PASSES; p++) {
-			if (lane + 64u * p < nblocks) {
-				group_rw_key_store(kd[p], ksh[p], wk, kadd4, kp.keys_overflow, reinterpret_cast<uint2 *>(keys) + lane + 64u * p);
-			}
-		}
-	}
+	RwKeys<W, DIRECT> k(ks, kp.kadd_byte, kp.keys_overflow, keys, r1, lanes);
+	k.first(c0, run.clamp(L));
 	for (uint32_t round0 = c0; round0 < c1; round0 += lanes, L += lanes) { // uniform trip count
 		// requested before this round is walked: the next chunk of a, its mask words, the next round's chunks of b, c, q and keys
 		uint4 qn;
@@ -472,15 +442,7 @@ __device__ __forceinline__ void group_q1_walk(uint32_t r0, uint32_t r1, const ad
 		load_s(bseg16, bc0n, bclast, bq0, bq1);
 		load_s(cseg16, cc0n, cclast, cq0, cq1);
 		load_s(qseg16, qc0n, qclast, qq0, qq1);
-		uint2 kqn = make_uint2(0u, 0u);
-		uint32_t kb0n = 0, nblocksn = 0;
-		if (DIRECT) {
-			kqn = direct_keys(run.clamp(L + lanes));
-		} else {
-			round_keys(round0 + lanes, kb0n, nblocksn);
-#pragma unroll
-			for (uint32_t p = 0; p < PASSES; p++) group_rw_key_load(kw32, (kb0n >> 3) + lane + 64u * p, wk, k_last_dword, kd[p], ksh[p]);
-		}
+		k.request(round0 + lanes, run.clamp(L + lanes));
 		if (walker && L < c1) {
 			const ChunkWindow<W> cw(q, e, L, r1);
 			const uint32_t have = cw.have();
@@ -490,20 +452,8 @@ __device__ __forceinline__ void group_q1_walk(uint32_t r0, uint32_t r1, const ad
 			const uint32_t bbit = cw.i0 * wb - 128u * bc0; // row i0 of b inside its staged chunks
 			const uint32_t cbit = cw.i0 * wc - 128u * cc0; // ... of c
 			const uint32_t qbit = cw.i0 * wq - 128u * qc0; // ... of q
-			uint32_t kwin = 0;  // DIRECT: the keys of rows i0 .. from bit 0
-			uint32_t kn[KD];    // staged: their bytes
-			if (DIRECT) {
-				kwin = __builtin_amdgcn_alignbit(kq.y, kq.x, (cw.i0 * wk) & 31u);
-			} else {
-				// the key bytes of rows [i0, i0 + MAXV): dword reads from the byte offset rounded down, one v_alignbyte each
-				const uint32_t kofs = cw.i0 - kb0;
-				const uint32_t *k32 = reinterpret_cast<const uint32_t *>(keys) + (kofs >> 2);
-				uint32_t raw[KD + 1];
-#pragma unroll
-				for (int i = 0; i <= KD; i++) raw[i] = k32[i];
-#pragma unroll
-				for (int i = 0; i < KD; i++) kn[i] = __builtin_amdgcn_alignbyte(raw[i + 1], raw[i], kofs & 3u);
-			}
+			uint32_t kwin, kn[RwKeys<W, DIRECT>::KD]; // DIRECT: the keys of rows i0 .. from bit 0; staged: their bytes
+			k.window(cw.i0, kwin, kn);
 			// BATCH rows at a time: their fields of b, c and q are read together, then consumed
 #pragma unroll
 			for (int j0 = 0; j0 < MAXV; j0 += BATCH) {
@@ -521,13 +471,7 @@ __device__ __forceinline__ void group_q1_walk(uint32_t r0, uint32_t r1, const ad
 					if (j0 + u < MAXV) {
 						const int j = j0 + u;
 						const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)vb, (uint32_t)j, 1u); // 0 / -1
-						uint32_t key;
-						if (DIRECT) {
-							key = kp.keys_overflow ? 255u : __builtin_amdgcn_ubfe(kwin, (uint32_t)j * wk, wk) + kp.kadd_byte;
-						} else {
-							key = (kn[j >> 2] >> (8 * (j & 3))) & 0xffu;
-						}
-						const uint32_t bin = key < ngroups ? key : ngroups;
+						const uint32_t bin = k.bin(kwin, kn, j, ngroups);
 						// a masked row (or one past the run): every term adds zero, so x, y and v carry the mask (z meets x only)
 						const uint32_t x = (field_of<W>(cw.nrm, j) + kp.ma) & m;
 						const uint32_t y = (fb[u] + kp.mb) & m;
@@ -552,23 +496,13 @@ __device__ __forceinline__ void group_q1_walk(uint32_t r0, uint32_t r1, const ad
 		e = en;
 		vm0 = vn0;
 		vm1 = vn1;
-		kq = kqn;
 		store_s(bstage, bq0, bq1, nbn); // after this round's reads of the buffers (LDS operations of one wave execute in order)
 		store_s(cstage, cq0, cq1, ncn);
 		store_s(qstage, qq0, qq1, nqn);
 		bc0 = bc0n;
 		cc0 = cc0n;
 		qc0 = qc0n;
-		if (!DIRECT) {
-#pragma unroll
-			for (uint32_t p = 0; p < PASSES; p++) {
-				if (lane + 64u * p < nblocksn) {
-					group_rw_key_store(kd[p], ksh[p], wk, kadd4, kp.keys_overflow,
-					                   reinterpret_cast<uint2 *>(keys) + lane + 64u * p);
-				}
-			}
-			kb0 = kb0n;
-		}
+		k.commit();
 	}
 }
 
@@ -606,32 +540,18 @@ __global__ __launch_bounds__(kWorkgroup, kGroupQ1RwResident) void k_group_q1_rw(
 			skipped++;
 			continue;
 		}
-		// the group in four contiguous quarters of whole 128-row units (a quarter's bits start a chunk of a), one per wave
-		const uint32_t per = (((g.n + kWaves - 1u) / kWaves) + 127u) & ~127u;
-		const uint32_t q0 = wave * per;
-		if (q0 >= g.n) continue; // uniform per wave
-		const uint32_t r0 = g.first + q0, r1 = g.first + (q0 + per < g.n ? q0 + per : g.n);
+		const RwQuarter qr(g, wave);
+		if (qr.empty()) continue; // uniform per wave
 		const uint4 *aseg16 = reinterpret_cast<const uint4 *>(awords + g.d.word_off);
 		const uint4 *bseg16 = reinterpret_cast<const uint4 *>(bwords + bd.word_off);
 		const uint4 *cseg16 = reinterpret_cast<const uint4 *>(cwords + cd.word_off);
 		const uint4 *qseg16 = reinterpret_cast<const uint4 *>(qwords + qd.word_off);
-		const uint32_t *kw32 = reinterpret_cast<const uint32_t *>(kwords + kd.word_off);
-		const uint32_t wk = kd.width;
-		const uint32_t k_last = (uint32_t)(((uint64_t)kd.count * wk + 31) >> 5) - 1u;
-		const uint32_t maxv = (128u + g.d.width - 1u) / g.d.width;
-		if (maxv * wk <= 32u) { // uniform: the keys of a chunk's rows fit one dword
-			dispatch_width_4_32(g.d.width, [&](auto wt) __attribute__((always_inline)) {
-				group_q1_walk<decltype(wt)::value, true, V>(r0, r1, g.d, bd, cd, qd, plan, wk, aseg16, bseg16, cseg16, qseg16,
-				                                            kw32, k_last, ngroups, keys[wave], bstage[wave], cstage[wave],
-				                                            qstage[wave], sums[wave], cnts[wave], validity);
-			});
-		} else {
-			dispatch_width_4_32(g.d.width, [&](auto wt) __attribute__((always_inline)) {
-				group_q1_walk<decltype(wt)::value, false, V>(r0, r1, g.d, bd, cd, qd, plan, wk, aseg16, bseg16, cseg16, qseg16,
-				                                             kw32, k_last, ngroups, keys[wave], bstage[wave], cstage[wave],
-				                                             qstage[wave], sums[wave], cnts[wave], validity);
-			});
-		}
+		const RwKeyStream ks(kwords, kd);
+		group_rw_dispatch(g.d.width, ks.direct(g.d.width), [&](auto wt, auto direct) __attribute__((always_inline)) {
+			group_q1_walk<decltype(wt)::value, decltype(direct)::value, V>(
+			    qr.r0, qr.r1, g.d, bd, cd, qd, plan, aseg16, bseg16, cseg16, qseg16, ks, ngroups,
+			    keys[wave], bstage[wave], cstage[wave], qstage[wave], sums[wave], cnts[wave], validity);
+		});
 	}
 	if (skipped && tid == 0u) atomicAdd(fallback, (unsigned long long)skipped);
 	// the wave's own total per (term, bin): its kGroupQ1RwCopies copies added by one lane each (7 x nbins <= 56 lanes;

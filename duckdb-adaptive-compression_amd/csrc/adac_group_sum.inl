@@ -22,7 +22,7 @@
 constexpr uint32_t kGroupStageBytes = 3584;   // packed bytes of one column per stage
 constexpr uint32_t kGroupChunksPerThread = (kGroupStageBytes / 16 + 1 + kWorkgroup - 1) / kWorkgroup;
 constexpr uint32_t kGroupCopies = 16;         // bin sets per wave (lane & 15 picks one): 4 lanes share a set (8 sets: slower)
-constexpr uint32_t kGroupPrivateBins = 8;     // bins held per thread
+// (kGroupPrivateBins = 8, the bins held per thread: adac_group_rw_walk.inl, which is included first)
 constexpr uint32_t kGroupMaxBins = 257;       // 256 groups + overflow
 // masked form of k_group_sum: a stage's mask words travel with it (one word per thread, two LDS buffers).  A stage is
 // capped at this many rows (it only binds below 4 bits: (3584 * 8 - 256) / 4 = 7104) so that the 2 KiB of mask words
@@ -87,8 +87,7 @@ struct GroupStageMask {
 struct GroupStageNoMask {};
 
 // ---- shared with k_group_sum_rw (below): who takes which segment pair
-constexpr uint32_t kGroupRwCopies = 32;                      // bin sets per wave (two lanes share a set)
-
+// (kGroupRwCopies = 32, its bin sets per wave: adac_group_rw_walk.inl)
 struct GroupRwPlan {
 	bool ok;
 	uint64_t vadd;      // added to every value field: the widened frame of reference (0 for raw segments)
@@ -389,70 +388,13 @@ __global__ __launch_bounds__(kWorkgroup) void k_group_sum(const adac_segment_des
 // Taken for a scan group when: nbins <= 8, value segment linear (or raw unsigned) at 4 <= w <= 32, key segment at
 // w <= 8 whose keys all fit a byte (or all land in the overflow bin).  Every other group is counted in *fallback and
 // left to k_group_sum, which runs after this kernel and skips the groups taken here (group_rw_eligible is shared).
+// The key reader (RwKeys) and the kernel's shell — quartering, key stream, width x key-form dispatch — are
+// adac_group_rw_walk.inl's, shared with the three grouped product kernels.
 // ------------------------------------------------------------------------------------------------------------------
-// Key staging (the form for value widths whose chunk holds many rows): the keys of an 8-row block `q` are the wk BYTES
-// [q * wk, (q + 1) * wk) of the key stream.  A lane loads the three dwords that hold them (the last one may be the
-// segment's padding word: every segment owns at least one 64-bit word past its data) ...
-__device__ __forceinline__ void group_rw_key_load(const uint32_t *__restrict__ kw32, uint32_t q, uint32_t wk,
-                                                  uint32_t last_dword, uint32_t (&d)[3], uint32_t &byte_sh) {
-	const uint32_t byte0 = q * wk;
-	uint32_t dw = byte0 >> 2;
-	dw = dw < last_dword ? dw : last_dword; // blocks past the segment's end are never read: any data will do
-	byte_sh = byte0 & 3u;
-	d[0] = kw32[dw];
-	d[1] = kw32[dw + 1];                     // <= last_dword + 1: inside the padding word
-	d[2] = kw32[dw + 2 <= last_dword + 1u ? dw + 2 : dw + 1];
-}
-
-// ... and takes them apart at a compile-time key width: 8 keys -> 8 bytes, the frame of reference added to four at a time
-template <int WK>
-__device__ __forceinline__ uint2 group_rw_key_decode(const uint32_t (&d)[3], uint32_t byte_sh, uint32_t kadd4) {
-	const uint32_t w0 = __builtin_amdgcn_alignbyte(d[1], d[0], byte_sh), w1 = __builtin_amdgcn_alignbyte(d[2], d[1], byte_sh);
-	constexpr uint32_t mask = (1u << WK) - 1u;
-	uint32_t out[2];
-#pragma unroll
-	for (int g = 0; g < 2; g++) {
-		uint32_t acc = 0;
-#pragma unroll
-		for (int b = 0; b < 4; b++) {
-			const int pos = (4 * g + b) * WK, dw = pos >> 5, sh = pos & 31; // pos + WK <= 64
-			const uint32_t lo = dw ? w1 : w0;
-			const uint32_t f = sh + WK <= 32 ? ((lo >> sh) & mask) : (__builtin_amdgcn_alignbit(w1, w0, sh) & mask);
-			acc |= f << (8 * b);
-		}
-		out[g] = acc + kadd4; // four keys at once: no byte carries (field + kadd <= 255)
-	}
-	return make_uint2(out[0], out[1]);
-}
-
-__device__ __forceinline__ void group_rw_key_store(const uint32_t (&d)[3], uint32_t byte_sh, uint32_t wk, uint32_t kadd4,
-                                                   bool overflow, uint2 *dst) {
-	if (overflow) {
-		*dst = make_uint2(~0u, ~0u);
-		return;
-	}
-	switch (wk) { // uniform
-	case 1: *dst = group_rw_key_decode<1>(d, byte_sh, kadd4); break;
-	case 2: *dst = group_rw_key_decode<2>(d, byte_sh, kadd4); break;
-	case 3: *dst = group_rw_key_decode<3>(d, byte_sh, kadd4); break;
-	case 4: *dst = group_rw_key_decode<4>(d, byte_sh, kadd4); break;
-	case 5: *dst = group_rw_key_decode<5>(d, byte_sh, kadd4); break;
-	case 6: *dst = group_rw_key_decode<6>(d, byte_sh, kadd4); break;
-	case 7: *dst = group_rw_key_decode<7>(d, byte_sh, kadd4); break;
-	default: *dst = group_rw_key_decode<8>(d, byte_sh, kadd4); break;
-	}
-}
-
 // One QUARTER of a scan group, walked by ONE WAVE on its own: the 64 lanes of a wave own consecutive chunks, i.e. one
 // contiguous run of rows per round, so nothing is shared between the waves of a workgroup and no barrier is left in the
 // loop (with a barrier per round the four waves advanced at the pace of the slowest: profiles/r03_group_sum_rw.json).
-// Keys, two forms (uniform per segment pair):
-//   DIRECT   the keys of a chunk's rows fit one dword (MAXV * wk <= 32: every value width >= 11 at wk = 3): a lane
-//            loads the two dwords of the key stream that hold them (prefetched a round ahead like its value chunk),
-//            shifts once, and finds key j with one v_bfe at the wave-uniform position j * wk.  No LDS for the keys.
-//   staged   otherwise: the wave stages the key BYTES of the round's rows in a buffer of its own (8 rows per lane,
-//            compile-time key width), and a lane fetches the bytes of its rows with dword reads + v_alignbyte.  LDS
-//            operations of one wave are executed in order, so no barrier is needed here either.
+// Keys: RwKeys (adac_group_rw_walk.inl), DIRECT or staged; its window is written out below.
 // `wbins`: the wave's 8 x 32 bin words for the CURRENT quarter: rows << 44 | sum of their FIELDS (a word takes the rows
 // of two lanes: a few hundred rows of at most 32 bits, far below 2^44 / 2^20), so a row costs ONE ds_add_u64 whose
 // operand is {field, 0x1000}: no widening arithmetic, no second LDS add.  group_rw_fold turns the words into the
@@ -462,8 +404,7 @@ constexpr uint32_t kGroupRwCountShift = 44;
 // 2 x 16384 / 31 rows of a quarter, their fields sum to less than 2^20)
 constexpr uint32_t kGroupRwNarrowShift = 20;
 template <int W> constexpr bool kGroupRwNarrow = W <= 8;
-constexpr uint32_t kGroupRwWaveRows = 1008;                    // key rows a wave stages per round: two 8-row blocks per lane
-constexpr uint32_t kGroupRwWaveKeyBytes = kGroupRwWaveRows + 16 + 64; // + the block the round starts in + read slack
+// (kGroupRwWaveRows, kGroupRwWaveKeyBytes: with the key reader, adac_group_rw_walk.inl)
 // V (the masked form): the two mask words of a chunk's rows travel with the chunk (ChunkMask, as in product_walk); one
 // 64-bit window from row i0 on covers the chunk (MAXV <= 32 rows).  A row whose bit is clear adds ZERO to its bin word:
 // the ds_add stays where it is and the loop stays free of branches (a test per row would put a compare, an exec-mask
@@ -473,20 +414,16 @@ constexpr uint32_t kGroupRwWaveKeyBytes = kGroupRwWaveRows + 16 + 64; // + the b
 template <bool V> constexpr uint32_t kGroupRwResident = V ? 6u : 7u;
 template <int W, bool DIRECT, bool V>
 __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t count, const GroupRwPlan &plan,
-                                              uint32_t wk, const uint4 *__restrict__ seg16,
-                                              const uint32_t *__restrict__ kw32, uint32_t k_last_dword, uint32_t ngroups,
+                                              const uint4 *__restrict__ seg16, const RwKeyStream &ks, uint32_t ngroups,
                                               uint8_t *keys, unsigned long long *wbins,
                                               const uint64_t *__restrict__ validity, uint64_t val_off) {
 	constexpr int MAXV = ChunkWindow<W>::MAXV;
-	constexpr int KD = (MAXV + 3 + 3) / 4;                         // dwords holding MAXV bytes from any byte offset
-	constexpr uint32_t LANES = (kGroupRwWaveRows * W / 128) < 64u ? (kGroupRwWaveRows * W / 128) : 64u; // chunks per round
-	constexpr uint32_t PASSES = ((LANES * 128u / W + 8u + 7u) / 8u + 63u) / 64u; // staged: 8-row blocks per round / 64 lanes
+	constexpr uint32_t LANES = RwKeys<W, DIRECT>::LANES; // chunks per round
 	// r0 is a multiple of 128 rows: its bits start a chunk
 	const ChunkRange<W> run(r0, r1, count);
 	const uint32_t c0 = run.c0, c1 = run.c1;
 	const uint32_t lane = threadIdx.x & 63u;
 	const bool walker = lane < LANES;
-	const uint32_t kadd4 = plan.keys_overflow ? 0u : plan.kadd_byte * 0x01010101u;
 	unsigned char *const my_bins = reinterpret_cast<unsigned char *>(wbins + (lane & (kGroupRwCopies - 1u)));
 	unsigned char *const my_bins32 = reinterpret_cast<unsigned char *>(reinterpret_cast<uint32_t *>(wbins) + (lane & (kGroupRwCopies - 1u)));
 	uint32_t L = c0 + lane;
@@ -496,37 +433,8 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 	const ChunkMask<W, V> vmask(validity, val_off, r1); // the value layout's element space
 	uint64_t vm0 = 0, vm1 = 0;
 	if (V) vmask.words(run.clamp(L), vm0, vm1);
-	// DIRECT: the two dwords of the key stream holding the keys of the rows that start in chunk Lx
-	auto direct_keys = [&](uint32_t Lx) {
-		uint32_t dw = (chunk_first_row<W>(Lx) * wk) >> 5;
-		dw = dw < k_last_dword ? dw : k_last_dword; // (chunks past the run: any data will do)
-		return make_uint2(kw32[dw], kw32[dw + 1]);   // dw + 1 <= last data dword + 1: inside the padding word
-	};
-	// staged: the key rows of the round that starts at chunk `rc` = [first row starting in chunk rc, first row starting
-	// in chunk rc + LANES), from the 8-row block the round starts in
-	auto round_keys = [&](uint32_t rc, uint32_t &kb0, uint32_t &nblocks) {
-		const uint32_t rows_lo = chunk_first_row<W>(rc);
-		kb0 = rows_lo & ~7u;
-		uint32_t rows_hi = chunk_first_row<W>(rc + LANES);
-		rows_hi = rows_hi < r1 ? rows_hi : r1;
-		nblocks = rows_hi > kb0 ? (rows_hi - kb0 + 7u) >> 3 : 0u;
-	};
-	uint2 kq = make_uint2(0u, 0u);
-	uint32_t kb0 = 0, nblocks = 0;
-	uint32_t kd[PASSES][3], ksh[PASSES];
-	if (DIRECT) {
-		kq = direct_keys(run.clamp(L));
-	} else { // prologue: the first round's key bytes
-		round_keys(c0, kb0, nblocks);
-#pragma unroll
-		for (uint32_t p = 0; p < PASSES; p++) group_rw_key_load(kw32, (kb0 >> 3) + lane + 64u * p, wk, k_last_dword, kd[p], ksh[p]);
-#pragma unroll
-		for (uint32_t p = 0; p < PASSES; p++) {
-			if (lane + 64u * p < nblocks) {
-				group_rw_key_store(kd[p], ksh[p], wk, kadd4, plan.keys_overflow, reinterpret_cast<uint2 *>(keys) + lane + 64u * p);
-			}
-		}
-	}
+	RwKeys<W, DIRECT> k(ks, plan.kadd_byte, plan.keys_overflow, keys, r1, LANES);
+	k.first(c0, run.clamp(L));
 	for (uint32_t round0 = c0; round0 < c1; round0 += LANES, L += LANES) { // uniform trip count
 		// requested before this round is walked: the next chunk of the value stream and its keys
 		uint4 qn;
@@ -534,28 +442,23 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 		run.load(seg16, L + LANES, qn, en);
 		uint64_t vn0 = 0, vn1 = 0;
 		if (V) vmask.words(run.clamp(L + LANES), vn0, vn1);
-		uint2 kqn = make_uint2(0u, 0u);
-		uint32_t kb0n = 0, nblocksn = 0;
-		if (DIRECT) {
-			kqn = direct_keys(run.clamp(L + LANES));
-		} else {
-			round_keys(round0 + LANES, kb0n, nblocksn);
-#pragma unroll
-			for (uint32_t p = 0; p < PASSES; p++) group_rw_key_load(kw32, (kb0n >> 3) + lane + 64u * p, wk, k_last_dword, kd[p], ksh[p]);
-		}
+		k.request(round0 + LANES, run.clamp(L + LANES));
 		if (walker && L < c1) {
 			const ChunkWindow<W> cw(q, e, L, r1);
 			// MAXV - 1 rows start in every chunk, the MAXV-th one if its first bit still lies inside.  (cw.last_starts() /
 			// cw.starting say the same; spelled from them this kernel came out with 8 bytes of scratch per lane.)
 			const bool last_starts = 128 % W == 0 || cw.o0 + (uint32_t)(MAXV - 1) * W < 128u;
 			const uint32_t starting = (uint32_t)(MAXV - 1) + (last_starts ? 1u : 0u);
+			// RwKeys::window, written out: called as a function it costs this kernel 3 VGPR spills and 16 bytes of
+			// scratch per lane at its seven waves per SIMD
+			constexpr int KD = RwKeys<W, DIRECT>::KD;
 			uint32_t kwin = 0;       // DIRECT: the keys of rows i0 .. from bit 0
 			uint32_t kn[KD];         // staged: their bytes
 			if (DIRECT) {
-				kwin = __builtin_amdgcn_alignbit(kq.y, kq.x, (cw.i0 * wk) & 31u);
+				kwin = __builtin_amdgcn_alignbit(k.kq.y, k.kq.x, (cw.i0 * ks.wk) & 31u);
 			} else {
 				// the key bytes of rows [i0, i0 + MAXV): dword reads from the byte offset rounded down, one v_alignbyte each
-				const uint32_t kofs = cw.i0 - kb0;
+				const uint32_t kofs = cw.i0 - k.kb0;
 				const uint32_t *k32 = reinterpret_cast<const uint32_t *>(keys) + (kofs >> 2);
 				uint32_t raw[KD + 1];
 #pragma unroll
@@ -568,13 +471,7 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 			const uint32_t vb = V ? (uint32_t)vmask.window(vm0, vm1, cw.i0) : 0xffffffffu;
 			auto add_row = [&](int j) {
 				const uint32_t m = V ? (uint32_t)__builtin_amdgcn_sbfe((int)vb, (uint32_t)j, 1u) : 0xffffffffu; // 0 / -1
-				uint32_t key;
-				if (DIRECT) {
-					key = plan.keys_overflow ? 255u : __builtin_amdgcn_ubfe(kwin, (uint32_t)j * wk, wk) + plan.kadd_byte;
-				} else {
-					key = (kn[j >> 2] >> (8 * (j & 3))) & 0xffu;
-				}
-				const uint32_t bin = key < ngroups ? key : ngroups;
+				const uint32_t bin = k.bin(kwin, kn, j, ngroups);
 				if (kGroupRwNarrow<W>) { // fields of at most 8 bits: rows << 20 | sum fits 32 bits, a ds_add_u32 is half the LDS work
 					uint32_t *slot = reinterpret_cast<uint32_t *>(my_bins32 + bin * (kGroupRwCopies * 4u));
 					atomicAdd(slot, ((1u << kGroupRwNarrowShift) | field_of<W>(cw.nrm, j)) & m);
@@ -599,17 +496,7 @@ __device__ __forceinline__ void group_rw_walk(uint32_t r0, uint32_t r1, uint32_t
 		e = en;
 		vm0 = vn0;
 		vm1 = vn1;
-		kq = kqn;
-		if (!DIRECT) { // the next round's key bytes (issued after this round's reads of the buffer)
-#pragma unroll
-			for (uint32_t p = 0; p < PASSES; p++) {
-				if (lane + 64u * p < nblocksn) {
-					group_rw_key_store(kd[p], ksh[p], wk, kadd4, plan.keys_overflow,
-					                   reinterpret_cast<uint2 *>(keys) + lane + 64u * p);
-				}
-			}
-			kb0 = kb0n;
-		}
+		k.commit();
 	}
 }
 
@@ -664,27 +551,14 @@ __global__ __launch_bounds__(kWorkgroup, kGroupRwResident<V>) void k_group_sum_r
 			skipped++;
 			continue;
 		}
-		// the group in four contiguous quarters of whole 128-row units (a quarter's bits start a 16-byte chunk), one per wave
-		const uint32_t per = (((g.n + kWaves - 1u) / kWaves) + 127u) & ~127u;
-		const uint32_t q0 = wave * per;
-		if (q0 >= g.n) continue; // uniform per wave
-		const uint32_t r0 = g.first + q0, r1 = g.first + (q0 + per < g.n ? q0 + per : g.n);
+		const RwQuarter qr(g, wave);
+		if (qr.empty()) continue; // uniform per wave
 		const uint4 *seg16 = reinterpret_cast<const uint4 *>(vwords + g.d.word_off);
-		const uint32_t *kw32 = reinterpret_cast<const uint32_t *>(kwords + kd.word_off);
-		const uint32_t wk = kd.width;
-		const uint32_t k_last = (uint32_t)(((uint64_t)kd.count * wk + 31) >> 5) - 1u;
-		const uint32_t maxv = (128u + g.d.width - 1u) / g.d.width;
-		if (maxv * wk <= 32u) { // uniform: the keys of a chunk's rows fit one dword
-			dispatch_width_4_32(g.d.width, [&](auto wc) __attribute__((always_inline)) {
-				group_rw_walk<decltype(wc)::value, true, V>(r0, r1, g.d.count, plan, wk, seg16, kw32, k_last, ngroups, keys[wave],
-				                                            bins[wave], validity, g.d.val_off);
-			});
-		} else {
-			dispatch_width_4_32(g.d.width, [&](auto wc) __attribute__((always_inline)) {
-				group_rw_walk<decltype(wc)::value, false, V>(r0, r1, g.d.count, plan, wk, seg16, kw32, k_last, ngroups, keys[wave],
-				                                             bins[wave], validity, g.d.val_off);
-			});
-		}
+		const RwKeyStream ks(kwords, kd);
+		group_rw_dispatch(g.d.width, ks.direct(g.d.width), [&](auto wc, auto direct) __attribute__((always_inline)) {
+			group_rw_walk<decltype(wc)::value, decltype(direct)::value, V>(qr.r0, qr.r1, g.d.count, plan, seg16, ks, ngroups,
+			                                                              keys[wave], bins[wave], validity, g.d.val_off);
+		});
 		group_rw_fold(bins[wave], tot[wave], plan.vadd, g.d.width <= 8u);
 	}
 	if (skipped && tid == 0u) atomicAdd(fallback, (unsigned long long)skipped);

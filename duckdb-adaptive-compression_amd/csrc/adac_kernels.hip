@@ -1953,6 +1953,7 @@ hipError_t dispatch_size(uint32_t type_size, F &&f) {
 #include "adac_select_gather.inl"
 #include "adac_block_image.inl"
 #include "adac_encode_1p.inl"
+#include "adac_group_rw_walk.inl"
 #include "adac_group_sum.inl"
 #include "adac_sum_product.inl"
 #include "adac_group_product.inl"

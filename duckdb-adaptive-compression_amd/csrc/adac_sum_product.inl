@@ -7,7 +7,8 @@
 // and the sum are taken mod 2^64, rows whose bit is clear in the mask (indexed in a's element space) take no part.
 // Two forms, chosen per group from the two descriptors and the types alone (product_fast_eligible):
 //   fast     both segments linear (or raw and unsigned), 4 <= wa <= 32, wb <= 32: a wave walks a quarter of the group
-//            on its own.  `a` on the fused scans' width-templated register walk (a lane owns whole 16-byte chunks, the
+//            (RwQuarter, adac_group_rw_walk.inl) on its own.  `a` on the fused scans' width-templated register walk (a
+//            lane owns whole 16-byte chunks, the
 //            next chunk and its mask words requested a round ahead, every field at a compile-time position); the
 //            16-byte chunks of `b` that hold the same contiguous row run are staged in a wave-private LDS buffer (the
 //            next round's chunks are loaded before this round is walked and stored after it: LDS operations of one
@@ -291,21 +292,17 @@ __global__ __launch_bounds__(kWorkgroup) void k_scan_product(const ScanGroup *__
                                                              const uint64_t *__restrict__ bwords, ProductTypes ty,
                                                              const uint64_t *__restrict__ validity,
                                                              unsigned long long *__restrict__ sums) {
-	constexpr uint32_t kWaves = kWorkgroup / 64;
 	__shared__ uint4 lds[4 * kProdStageChunks];
 	const ScanGroup g = load_scan_group(agroups, blockIdx.x);
 	const adac_segment_desc bd = load_desc_scalar(bdescs, g.seg);
 	const ProductPlan plan = product_fast_eligible(g.d, bd, ty);
 	uint64_t tot;
 	if (plan.ok) { // uniform
-		// the group in four contiguous quarters of whole 128-row units (a quarter's bits start a chunk of a), one per wave
 		const uint32_t wave = threadIdx.x >> 6;
-		const uint32_t per = (((g.n + kWaves - 1u) / kWaves) + 127u) & ~127u;
-		const uint32_t q0 = wave * per;
-		if (q0 >= g.n) return; // uniform per wave; no barrier follows
-		const uint32_t r0 = g.first + q0, r1 = g.first + (q0 + per < g.n ? q0 + per : g.n);
+		const RwQuarter qr(g, wave);
+		if (qr.empty()) return; // uniform per wave; no barrier follows
 		ProductAcc acc;
-		product_walk_dispatch<V>(r0, r1, g.d, bd, reinterpret_cast<const uint4 *>(awords + g.d.word_off),
+		product_walk_dispatch<V>(qr.r0, qr.r1, g.d, bd, reinterpret_cast<const uint4 *>(awords + g.d.word_off),
 		                         reinterpret_cast<const uint4 *>(bwords + bd.word_off), validity,
 		                         lds + wave * kProdWaveChunks, acc);
 		const uint64_t pp = wave_sum(acc.pp), pa = wave_sum(acc.pa), pb = wave_sum(acc.pb);
