@@ -848,6 +848,137 @@ def q12_bitpacking(adac, n=59_986_052):
     return out
 
 
+def q12_packed(adac, n=59_986_052):
+    """TPC-H Q12's WHERE clause on columns packed by adac_encode — q12_bitpacking's table (same seed, same three int32
+    day columns) on the succinct codec: l_receiptdate BETWEEN one year (adac_scan_select_between), then l_commitdate <
+    l_receiptdate under that bitmap and l_shipdate < l_commitdate under that one (adac_scan_select_compare); the final
+    counts checked against numpy before and after the timing.  Interleaved in the same process, for commit < receipt:
+    the compare alone and in the chain, adac_scan_count_compare, adac_unpack of the same two columns,
+    adac_scan_sum_product on the same pair, and adac_bp_scan_select_compare on the same two columns as BITPACKING
+    blocks.  A second cell, "sorted": the table sorted by l_receiptdate with l_commitdate = l_receiptdate - U[70, 100]
+    days (clustered with the sort key), so that the two segments' value intervals are disjoint in most scan groups and
+    the compare is answered from the descriptors (the header form)."""
+    from oracle import bitpacking as bp
+    ctx = adac.Context(0)
+    cols = lineitem(np.random.default_rng(1994), n, ("l_shipdate", "l_commitdate", "l_receiptdate"))
+    counts = adac.appender_segment_counts(n, 4)
+    nseg, nw = len(counts), (n + 63) // 64
+    LT = adac.CMP_LT
+    bm = [ctx.alloc(nw * 8 + 8) for _ in range(3)]
+    d_alone = ctx.alloc(nw * 8 + 8)
+    d_cnt, d_final, d_sum = ctx.alloc(nseg * 8), ctx.alloc(nseg * 8), ctx.alloc(nseg * 8)
+    d_out = ctx.alloc(n * 4 + 64)
+    starts = np.concatenate([[0], np.cumsum(counts[:-1], dtype=np.int64)])
+
+    def select(a, b, d_bitmap, d_counts, d_valid=None):
+        a.lay.scan_select_compare(a.words, b.lay, b.words, LT, d_bitmap, d_counts, d_valid)
+
+    # ---- the table as drawn
+    enc = {name: encode_column(adac, ctx, v, counts) for name, v in cols.items()}
+    ship, commit, receipt = (enc[k] for k in ("l_shipdate", "l_commitdate", "l_receiptdate"))
+
+    def between():
+        receipt.lay.scan_select_between(receipt.words, *Q12_RECEIPT_DATES, bm[0], d_cnt)
+
+    def chain():
+        between()
+        select(commit, receipt, bm[1], d_cnt, bm[0])
+        select(ship, commit, bm[2], d_final, bm[1])
+
+    def unpack_two():
+        commit.lay.unpack(commit.words, d_out)
+        receipt.lay.unpack(receipt.words, d_out)
+
+    m1 = (cols["l_receiptdate"] >= Q12_RECEIPT_DATES[0]) & (cols["l_receiptdate"] <= Q12_RECEIPT_DATES[1])
+    m2 = m1 & (cols["l_commitdate"] < cols["l_receiptdate"])
+    m3 = m2 & (cols["l_shipdate"] < cols["l_commitdate"])
+    want_counts = np.add.reduceat(m3.astype(np.uint64), starts)
+
+    def parity(when):
+        chain()
+        ctx.sync()
+        assert np.array_equal(d_final.download(np.uint64, nseg), want_counts), "Q12 counts parity (%s)" % when
+        full = np.zeros(nw * 64, dtype=bool)
+        full[:n] = m3
+        assert np.array_equal(bm[2].download(np.uint64, nw), np.packbits(full, bitorder="little").view(np.uint64)), \
+            "Q12 bitmap parity (%s)" % when
+
+    parity("before timing")
+    blocks = {k: bitpacking_blocks(adac, ctx, bp.Compressed(cols[k]), cols[k].dtype) for k in ("l_commitdate", "l_receiptdate")}
+    bc, br = blocks["l_commitdate"], blocks["l_receiptdate"]
+    d_bcnt = ctx.alloc(max(bc.nseg, br.nseg) * 8)
+
+    # ---- the sorted table
+    order = np.argsort(cols["l_receiptdate"], kind="stable")
+    s_receipt = cols["l_receiptdate"][order]
+    s_commit = (s_receipt - np.random.default_rng(1995).integers(70, 101, size=n)).astype(np.int32)
+    del order
+    srt = {"l_commitdate": encode_column(adac, ctx, s_commit, counts), "l_receiptdate": encode_column(adac, ctx, s_receipt, counts)}
+    sc, sr = srt["l_commitdate"], srt["l_receiptdate"]
+    select(sc, sr, d_alone, d_cnt)
+    ctx.sync()
+    assert int(d_cnt.download(np.uint64, nseg).sum()) == n, "sorted cell: every commit date is before its receipt date"
+    select(sr, sc, d_alone, d_cnt)
+    ctx.sync()
+    assert int(d_cnt.download(np.uint64, nseg).sum()) == 0
+
+    def census(a, b):
+        fs = forms.compare_form_groups(a.descs, b.descs)
+        return {f: fs.count(f) for f in ("header", "fast", "generic")}
+
+    entries = [("q12_where_chain", chain), ("select_between_receiptdate", between),
+               ("compare_alone", lambda: select(commit, receipt, d_alone, d_cnt)),
+               ("compare_in_chain", lambda: select(commit, receipt, bm[1], d_cnt, bm[0])),
+               ("count_compare", lambda: commit.lay.scan_count_compare(commit.words, receipt.lay, receipt.words, LT, d_cnt)),
+               ("unpack_two_columns", unpack_two),
+               ("sum_product", lambda: commit.lay.scan_sum_product(commit.words, receipt.lay, receipt.words, d_sum)),
+               ("bp_select_compare", lambda: bc.lay.scan_select_compare(bc.words, br.lay, br.words, LT, d_alone, d_bcnt)),
+               ("sorted_compare_alone", lambda: select(sc, sr, d_alone, d_cnt)),
+               ("sorted_count_compare", lambda: sc.lay.scan_count_compare(sc.words, sr.lay, sr.words, LT, d_cnt)),
+               ("sorted_sum_product", lambda: sc.lay.scan_sum_product(sc.words, sr.lay, sr.words, d_sum))]
+    samples = timed_interleaved(ctx, entries)
+    parity("after timing")
+    med = {k: float(np.median(x)) for k, x in samples.items()}
+    two, stwo = commit.nbytes + receipt.nbytes, sc.nbytes + sr.nbytes
+    out = {"rows": n, "segments": nseg,
+           "selected_rows": {"receiptdate_in_year": int(m1.sum()), "and_commit_lt_receipt": int(m2.sum()),
+                             "and_ship_lt_commit": int(m3.sum())},
+           "widths": {k: e.widths for k, e in enc.items()}, "packed_bytes": {k: e.nbytes for k, e in enc.items()},
+           "bitpacking_bytes": {k: e.nbytes for k, e in blocks.items()},
+           "segment_pairs_by_form": census(commit, receipt),
+           "ms": med, "q12_where_chain_ms": med["q12_where_chain"],
+           "commit_lt_receipt": {
+               "select_alone_ms": med["compare_alone"], "select_in_chain_ms": med["compare_in_chain"],
+               "count_ms": med["count_compare"], "unpack_two_columns_ms": med["unpack_two_columns"],
+               "sum_product_ms": med["sum_product"], "bp_select_compare_ms": med["bp_select_compare"],
+               "select_over_decode": med["compare_alone"] / med["unpack_two_columns"],
+               "select_over_sum_product": med["compare_alone"] / med["sum_product"],
+               "count_over_sum_product": med["count_compare"] / med["sum_product"],
+               "select_over_bp_select": med["compare_alone"] / med["bp_select_compare"],
+               "select_packed_read_GBps": two / (med["compare_alone"] * 1e-3) / 1e9, "bitmap_bytes_written": nw * 8,
+               "sum_product_packed_read_GBps": two / (med["sum_product"] * 1e-3) / 1e9},
+           "sorted": {"widths": {k: e.widths for k, e in srt.items()}, "packed_bytes": {k: e.nbytes for k, e in srt.items()},
+                      "segment_pairs_by_form": census(sc, sr), "select_alone_ms": med["sorted_compare_alone"],
+                      "count_ms": med["sorted_count_compare"], "sum_product_ms": med["sorted_sum_product"],
+                      "select_over_sum_product": med["sorted_compare_alone"] / med["sorted_sum_product"],
+                      "packed_bytes_not_read": stwo},
+           "samples_ms": {k: [round(t, 5) for t in x] for k, x in samples.items()},
+           "note": ("l_commitdate and l_receiptdate are independent uniform draws in l_shipdate's range (dbgen's dates are "
+                    "correlated and select fewer rows).  compare_alone = adac_scan_select_compare(LT) with d_validity NULL, "
+                    "compare_in_chain = the same call under the BETWEEN's bitmap, count_compare = adac_scan_count_compare, "
+                    "unpack_two_columns = adac_unpack of the two columns, sum_product = adac_scan_sum_product on the same "
+                    "pair without a mask, bp_select_compare = adac_bp_scan_select_compare on the same two columns as "
+                    "BITPACKING blocks.  sorted: the table sorted by l_receiptdate, l_commitdate = l_receiptdate - U[70, 100] "
+                    "days.  Medians of %d interleaved rounds of %d calls each" % (ROUNDS, INNER))}
+    print("q12_packed commit<receipt: select %.4f ms (in chain %.4f, count %.4f), decode of both %.4f, sum_product %.4f, "
+          "bp select %.4f; sorted: select %.4f, sum_product %.4f" %
+          (med["compare_alone"], med["compare_in_chain"], med["count_compare"], med["unpack_two_columns"],
+           med["sum_product"], med["bp_select_compare"], med["sorted_compare_alone"], med["sorted_sum_product"]),
+          file=sys.stderr, flush=True)
+    ctx.close()
+    return out
+
+
 def bitpacking_select_gather(adac, n=59_986_052):
     """Filter -> project on DuckDB's own BITPACKING blocks: adac_bp_unpack_selected (values only, then values + ids) of
     l_extendedprice (int32, FOR), the 6-valued uint8 code and a sorted copy of l_partkey (DELTA_FOR) under five bitmaps
@@ -1260,6 +1391,7 @@ def main():
             "bitpacking_fused_scans": lambda: bitpacking_fused_scans(adac),
             "q6_bitpacking": lambda: q6_bitpacking(adac),
             "q12_bitpacking": lambda: q12_bitpacking(adac),
+            "q12_packed": lambda: q12_packed(adac),
             "bitpacking_select_gather": lambda: bitpacking_select_gather(adac),
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "q1_filtered_packed": lambda: q1_filtered_packed(adac),

@@ -179,6 +179,8 @@ SIGNATURES = {
     "adac_scan_count_between": (_int, [_vp, _vp, _u64, _u64, _vp]),
     "adac_scan_sum_valid": (_int, [_vp, _vp, _vp, _vp]),
     "adac_scan_select_between": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "adac_scan_select_compare": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "adac_scan_count_compare": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "adac_unpack_selected": (_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "adac_scan_count_between_valid": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "adac_bp_layout_create": (_int, [_vp, _int, _vp, _vp, _vp, _u64, _P(_vp)]),
@@ -607,6 +609,19 @@ class Layout:
         """Selection bitmap over the element index space (ceil(value_span / 64) words) + per-segment hit counts."""
         _check(lib().adac_scan_select_between(self._h, _dptr(d_words), _dptr(d_validity), lo & NO_MIN, hi & NO_MIN,
                                               _dptr(d_bitmap), _dptr(d_counts)), "adac_scan_select_between")
+
+    def scan_select_compare(self, d_words, other, d_other_words, cmp, d_bitmap, d_counts, d_validity=None):
+        """Selection bitmap (this layout's element space, ceil(value_span / 64) words) + per-segment counts of the rows
+        where self <cmp> other, cmp one of CMP_LT ... CMP_GE; the values compare as mathematical integers whatever the
+        two types are.  `other`: a Layout over the same rows.  d_validity: a mask in THIS layout's element space."""
+        _check(lib().adac_scan_select_compare(self._h, _dptr(d_words), other._h, _dptr(d_other_words),
+                                              _dptr(d_validity), int(cmp), _dptr(d_bitmap), _dptr(d_counts)),
+               "adac_scan_select_compare")
+
+    def scan_count_compare(self, d_words, other, d_other_words, cmp, d_counts, d_validity=None):
+        """The counts of scan_select_compare alone."""
+        _check(lib().adac_scan_count_compare(self._h, _dptr(d_words), other._h, _dptr(d_other_words),
+                                             _dptr(d_validity), int(cmp), _dptr(d_counts)), "adac_scan_count_compare")
 
     def unpack_selected(self, d_words, d_bitmap, d_out, d_out_ids=None, want_total=True):
         """Values (and optionally element indices) of the rows whose bitmap bit is set, dense, in row order.

@@ -1107,6 +1107,48 @@ extern "C" adac_status adac_scan_sum_product(adac_layout *a, const uint64_t *d_a
 	return ADAC_OK;
 }
 
+// Rows where value(a) <cmp> value(b): what adac_scan_select_compare and adac_scan_count_compare share.  Checks the
+// arguments, makes sure `a` has its scan groups, clears the counts (every wave adds its part; this also writes the
+// segments without rows) and, for the select form, the bitmap (plain write-out: groups OR into the words they share).
+static adac_status scan_compare(adac_layout *a, const uint64_t *d_a_words, adac_layout *b, const uint64_t *d_b_words,
+                                const uint64_t *d_validity, uint32_t cmp, bool want_bitmap, uint64_t *d_bitmap,
+                                uint64_t *d_counts) {
+	if (!a || !b || a->ctx != b->ctx) return ADAC_ERR_INVALID_ARGUMENT;
+	if (a->counts != b->counts) return ADAC_ERR_INVALID_ARGUMENT; // the same rows, segment by segment
+	if (cmp < 1u || cmp > 6u) return ADAC_ERR_INVALID_ARGUMENT;
+	if (a->nseg && !d_counts) return ADAC_ERR_INVALID_ARGUMENT;
+	if (a->total_values && (!d_a_words || !d_b_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (!aligned16(d_a_words) || !aligned16(d_b_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (want_bitmap && ((a->value_span && !d_bitmap) || (d_bitmap && d_bitmap == d_validity))) {
+		return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	if (a->nseg == 0) return ADAC_OK; // no counts, no elements
+	ADAC_HIP(hipSetDevice(a->ctx->device));
+	adac_status gst = ensure_scan_groups(a);
+	if (gst != ADAC_OK) return gst;
+	ADAC_HIP(hipMemsetAsync(d_counts, 0, a->nseg * sizeof(uint64_t), a->ctx->stream));
+	if (want_bitmap && a->value_span) {
+		ADAC_HIP(hipMemsetAsync(d_bitmap, 0, ((a->value_span + 63) / 64) * sizeof(uint64_t), a->ctx->stream));
+	}
+	if (want_bitmap && !d_bitmap) return ADAC_OK; // no element, so no row
+	ADAC_HIP(adac::launch_scan_compare(a->ctx->stream, a->type_size, a->is_signed, b->type_size, b->is_signed, a->d_groups,
+	                                   a->ngroups, d_a_words, b->d_descs, d_b_words, d_validity, cmp,
+	                                   want_bitmap ? d_bitmap : nullptr, d_counts));
+	return ADAC_OK;
+}
+
+extern "C" adac_status adac_scan_select_compare(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
+                                                const uint64_t *d_b_words, const uint64_t *d_validity, uint32_t cmp,
+                                                uint64_t *d_bitmap, uint64_t *d_counts) {
+	return scan_compare(a, d_a_words, b, d_b_words, d_validity, cmp, true, d_bitmap, d_counts);
+}
+
+extern "C" adac_status adac_scan_count_compare(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
+                                               const uint64_t *d_b_words, const uint64_t *d_validity, uint32_t cmp,
+                                               uint64_t *d_counts) {
+	return scan_compare(a, d_a_words, b, d_b_words, d_validity, cmp, false, nullptr, d_counts);
+}
+
 // SUM(value), COUNT(*) GROUP BY key over two packed columns of one table (Q1's shape, TPCH_runtime.txt:2-6)
 extern "C" adac_status adac_scan_group_sum_valid(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
                                                  const uint64_t *d_key_words, const uint64_t *d_validity, uint32_t ngroups,

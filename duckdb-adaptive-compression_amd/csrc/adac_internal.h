@@ -195,6 +195,11 @@ hipError_t launch_scan_sum_product(hipStream_t s, uint32_t a_type_size, bool a_s
                                    const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,
                                    const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
                                    const uint64_t *d_validity, uint64_t *d_sums);
+// rows where value(a) <cmp> value(b) per segment, and their bitmap unless d_bitmap is null (adac_scan_compare.inl)
+hipError_t launch_scan_compare(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
+                               const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,
+                               const adac_segment_desc *d_bdescs, const uint64_t *d_bwords, const uint64_t *d_validity,
+                               uint32_t cmp, uint64_t *d_bitmap, uint64_t *d_counts);
 hipError_t launch_encode_1p(hipStream_t s, uint32_t type_size, bool sign_extend, uint64_t null_bits, int rule,
                             int pad_to_byte, adac_segment_desc *d_descs, uint64_t nseg, const void *d_vals,
                             const uint64_t *d_validity, uint64_t *d_minmax, void *d_scan_state, uint64_t *d_words);

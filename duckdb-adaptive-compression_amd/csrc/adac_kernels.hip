@@ -1956,6 +1956,7 @@ hipError_t dispatch_size(uint32_t type_size, F &&f) {
 #include "adac_group_rw_walk.inl"
 #include "adac_group_sum.inl"
 #include "adac_sum_product.inl"
+#include "adac_scan_compare.inl"
 #include "adac_group_product.inl"
 #include "adac_group_product3.inl"
 #include "adac_group_q1.inl"
@@ -2288,6 +2289,32 @@ hipError_t launch_scan_sum_product(hipStream_t s, uint32_t a_type_size, bool a_s
 	} else {
 		hipLaunchKernelGGL(k_scan_product<false>, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_agroups, d_awords,
 		                   d_bdescs, d_bwords, ty, d_validity, sums);
+	}
+	return hipGetLastError();
+}
+
+// Rows where value(a) <cmp> value(b), per segment, and their bitmap when d_bitmap is given (adac_scan_compare.inl): one
+// workgroup per scan group of `a`; the caller has cleared d_counts and the bitmap
+hipError_t launch_scan_compare(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
+                               const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,
+                               const adac_segment_desc *d_bdescs, const uint64_t *d_bwords, const uint64_t *d_validity,
+                               uint32_t cmp, uint64_t *d_bitmap, uint64_t *d_counts) {
+	if (ngroups == 0) return hipSuccess;
+	ProductTypes ty;
+	ty.a_tmask = type_mask(a_type_size);
+	ty.a_sbit = type_sign_bit(a_type_size, a_signed);
+	ty.b_tmask = type_mask(b_type_size);
+	ty.b_sbit = type_sign_bit(b_type_size, b_signed);
+	unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_counts);
+	uint32_t *bitmap32 = reinterpret_cast<uint32_t *>(d_bitmap);
+	auto launch = [&](auto kernel) {
+		hipLaunchKernelGGL(kernel, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_agroups, d_awords, d_bdescs, d_bwords,
+		                   ty, d_validity, cmp, bitmap32, counts);
+	};
+	if (d_bitmap) {
+		if (d_validity) launch(k_scan_compare<true, true>); else launch(k_scan_compare<false, true>);
+	} else {
+		if (d_validity) launch(k_scan_compare<true, false>); else launch(k_scan_compare<false, false>);
 	}
 	return hipGetLastError();
 }

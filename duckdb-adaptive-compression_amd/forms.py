@@ -11,6 +11,10 @@ scan group is fast when
     column passes keys_ok().
 Descriptors are rows of SEGMENT_DESC_DTYPE (Layout.get_descs()); a type is (size in bytes, signed).  Every function
 returns {"fast": scan groups of a, "generic": scan groups of a} with the default grouping of ensure_scan_groups.
+
+The compare scan (k_scan_compare, csrc/adac_scan_compare.inl) has a third form in front of the two: "header", when both
+columns have a frame() and the intervals [frame, frame + 2^w - 1] are disjoint as mathematical integers (or both are
+single values), so that the descriptors alone decide every row.  compare_form_groups names the form per segment pair.
 """
 from itertools import repeat
 
@@ -90,3 +94,23 @@ def group_q1_form_groups(descs_a, descs_b, descs_c, descs_q, descs_k, ngroups, a
                          c_type=(4, True), q_type=(4, True), k_size=1):
     """adac_scan_group_sum_q1: group_q1_rw_eligible (for q what holds for c)."""
     return form_groups((descs_a, descs_b, descs_c, descs_q), (a_type, b_type, c_type, q_type), descs_k, ngroups, k_size)
+
+
+def compare_form_groups(descs_a, descs_b, a_type=(4, True), b_type=(4, True)):
+    """adac_scan_select_compare / adac_scan_count_compare (k_scan_compare): compare_plan, per segment pair "header",
+    "fast" or "generic" (every scan group of a segment takes the same form); None for a segment without rows."""
+    out = []
+    for da, db in zip(descs_a, descs_b):
+        if int(da["count"]) == 0:
+            out.append(None)
+            continue
+        ma, mb = frame(da, *a_type), frame(db, *b_type)
+        form = "generic"
+        if ma is not None and mb is not None:
+            sa, sb = (1 << int(da["width"])) - 1, (1 << int(db["width"])) - 1
+            if ma + sa < mb or mb + sb < ma or (sa == 0 and sb == 0):
+                form = "header"
+            elif value_ok(da, a_type, 4, False) and value_ok(db, b_type, 1, False):
+                form = "fast"
+        out.append(form)
+    return out

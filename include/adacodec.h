@@ -494,6 +494,37 @@ adac_status adac_scan_count_between_valid(adac_layout *l, const uint64_t *d_word
 adac_status adac_scan_select_between(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity, uint64_t lo,
                                      uint64_t hi, uint64_t *d_bitmap, uint64_t *d_counts);
 
+/* Filter push-down with a predicate between TWO columns of a row — TPC-H Q12's `l_commitdate < l_receiptdate`, Q4,
+ * Q21, or a plain `a = b` — on the packed bytes of both: select the rows where value(a) <cmp> value(b).
+ * adac_scan_sum_product's pair rules hold: `a` and `b` are layouts on one context with the same row count per segment;
+ * types, widths, placements, encode rules and value offsets may differ.  a == b with the same words is legal: EQ then
+ * selects every wanted row, LT and GT none.
+ * cmp: an OR of ADAC_CMP_LT / ADAC_CMP_EQ / ADAC_CMP_GT (declared with adac_bp_scan_select_compare below), 1 ... 6.
+ * A row is selected iff its bit is set in d_validity (a's element space, a's val_off + row; NULL: every row) and the
+ * comparison holds for the values adac_unpack would write for the two columns.  The values compare as mathematical
+ * integers: each is widened by its own column's signedness, and a negative value of a signed column is smaller than
+ * every value of an unsigned one; int64 against uint64 is exact.
+ * d_counts[seg] = rows selected, over a's nseg words, written for segments without rows too.
+ * d_bitmap: ceil(value_span(a) / 64) words, fully written by the call: bits of elements that no segment covers are
+ * zero, nothing is pre-cleared by the caller.  It must not alias d_validity.  Like adac_scan_select_between's result
+ * it is usable as the d_validity of every other scan on a layout with a's value offsets.  No mask word outside
+ * ceil(value_span(a) / 64) is read.
+ * ADAC_ERR_INVALID_ARGUMENT, on the host before anything is enqueued: a NULL layout; layouts on different contexts;
+ * per-segment counts that differ; cmp 0 or above 6; NULL d_counts while a has segments; a NULL or not 16-byte aligned
+ * words pointer while there are rows; for the select form NULL d_bitmap while value_span(a) != 0, or
+ * d_bitmap == d_validity.
+ * Both calls enqueue on the context's stream and synchronise no more than adac_scan_sum_product does.
+ * A scan group (some consecutive tiles of one segment) in which both segments are packed against a frame of reference
+ * that stays inside the type, so that [frame, frame + 2^width - 1] is known for each, and the two intervals are
+ * disjoint, is decided from the two descriptors: no packed word of either column is read (sorted or clustered dates). */
+adac_status adac_scan_select_compare(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
+                                     const uint64_t *d_b_words, const uint64_t *d_validity, uint32_t cmp,
+                                     uint64_t *d_bitmap, uint64_t *d_counts);
+/* the counts alone: no bitmap is written */
+adac_status adac_scan_count_compare(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
+                                    const uint64_t *d_b_words, const uint64_t *d_validity, uint32_t cmp,
+                                    uint64_t *d_counts);
+
 /* Materialise only the selected rows: d_out receives, densely and in row order (segment by segment), the values of
  * the rows whose bit is set in d_bitmap (the result of adac_scan_select_between, or any mask over the element index
  * space); d_out_ids, if not NULL, receives their element indices (val_off + row).  *total_out, if not NULL, is set
