@@ -979,6 +979,145 @@ def q12_packed(adac, n=59_986_052):
     return out
 
 
+Q4_ORDER_DATES = (8582, 8673)   # o_orderdate in 1993-07-01 .. 1993-09-30, one quarter
+
+
+def q4_packed(adac, n_orders=15_000_000):
+    """TPC-H Q4 end to end on packed columns, a semi-join through a bit set indexed by the key: adac_scan_select_between
+    on o_orderdate for one quarter, adac_scan_select_compare on l_commitdate < l_receiptdate, adac_scan_build_member over
+    l_orderkey under that bitmap (the key set), adac_scan_select_member over o_orderkey under the date bitmap, and
+    adac_scan_group_sum_valid for the counts per o_orderpriority; the five counts checked against numpy (np.isin) before
+    and after the timing.  Synthetic orders at SF10 size: o_orderkey sparse-increasing as dbgen's (8 keys used of every
+    32), one to seven lineitems per order, o_orderpriority a 5-valued uint8 code, o_orderdate an int32 day.  Interleaved
+    in the same process, for the probe (o_orderkey) and for the build (l_orderkey): adac_scan_select_between on the same
+    column (the same packed bytes: the floor), adac_scan_sum of it (the key columns are sorted, so the BETWEEN skips the
+    segments that lie outside its range on their descriptors; the SUM reads every packed byte) and
+    adac_unpack of the column (what the call replaces).  A second cell,
+    "q12_shipmode": Q12's l_shipmode IN ('MAIL', 'SHIP') as a probe of a two-member set on a 7-valued uint8 code."""
+    ctx = adac.Context(0)
+    rng = np.random.default_rng(1993)
+    idx = np.arange(n_orders, dtype=np.int64)
+    o_orderkey = ((idx // 8) * 32 + idx % 8 + 1).astype(np.int32)
+    del idx
+    o_priority = rng.integers(0, 5, size=n_orders).astype(np.uint8)
+    o_orderdate = rng.integers(8036, 10562 - 151, size=n_orders).astype(np.int32)
+    l_orderkey = np.repeat(o_orderkey, rng.integers(1, 8, size=n_orders))
+    n = len(l_orderkey)
+    dates = lineitem(rng, n, ("l_commitdate", "l_receiptdate"))
+    oc, lc = adac.appender_segment_counts(n_orders, 4), adac.appender_segment_counts(n, 4)
+    oseg, lseg, ow, lw = len(oc), len(lc), (n_orders + 63) // 64, (n + 63) // 64
+    okey, odate = encode_column(adac, ctx, o_orderkey, oc), encode_column(adac, ctx, o_orderdate, oc)
+    oprio = encode_column(adac, ctx, o_priority, oc)
+    lkey = encode_column(adac, ctx, l_orderkey, lc)
+    commit, receipt = (encode_column(adac, ctx, dates[k], lc) for k in ("l_commitdate", "l_receiptdate"))
+    base, bits = 1, int(o_orderkey.max())
+    sw = (bits + 63) // 64
+    d_set, d_set2 = ctx.alloc(sw * 8 + 8), ctx.alloc(sw * 8 + 8)
+    bm_l, bm_od, bm_o, bm_x = ctx.alloc(lw * 8 + 8), ctx.alloc(ow * 8 + 8), ctx.alloc(ow * 8 + 8), ctx.alloc(lw * 8 + 8)
+    d_lcnt, d_ocnt = ctx.alloc(lseg * 8), ctx.alloc(oseg * 8)
+    d_lsum, d_osum = ctx.alloc(lseg * 8), ctx.alloc(oseg * 8)
+    d_sums, d_gcnt = ctx.alloc(6 * 8), ctx.alloc(6 * 8)
+    d_out = ctx.alloc(n * 4 + 64)
+
+    def chain():
+        odate.lay.scan_select_between(odate.words, *Q4_ORDER_DATES, bm_od, d_ocnt)
+        commit.lay.scan_select_compare(commit.words, receipt.lay, receipt.words, adac.CMP_LT, bm_l, d_lcnt)
+        lkey.lay.scan_build_member(lkey.words, base, bits, d_set, d_lcnt, bm_l)
+        okey.lay.scan_select_member(okey.words, d_set, base, bits, bm_o, d_ocnt, bm_od)
+        okey.lay.scan_group_sum_valid(okey.words, oprio.lay, oprio.words, bm_o, 5, d_sums, d_gcnt)
+
+    late = dates["l_commitdate"] < dates["l_receiptdate"]
+    in_quarter = (o_orderdate >= Q4_ORDER_DATES[0]) & (o_orderdate <= Q4_ORDER_DATES[1])
+    exists = np.isin(o_orderkey, l_orderkey[late])
+    want = np.bincount(o_priority[in_quarter & exists], minlength=5)
+
+    def parity(when):
+        chain()
+        ctx.sync()
+        got = d_gcnt.download(np.uint64, 6)
+        assert [int(x) for x in got] == [int(x) for x in want] + [0], "Q4 counts parity (%s): %s" % (when, got)
+
+    parity("before timing")
+    # Q12's ship mode: a 7-valued code, two members
+    shipmode = rng.integers(0, 7, size=n).astype(np.uint8)
+    mcounts = adac.appender_segment_counts(n, 1)
+    mode = encode_column(adac, ctx, shipmode, mcounts)
+    d_mcnt, d_msum = ctx.alloc(len(mcounts) * 8), ctx.alloc(len(mcounts) * 8)
+    d_inlist = ctx.upload(np.array([(1 << 2) | (1 << 5)], dtype=np.uint64))
+    mode.lay.scan_count_member(mode.words, d_inlist, 0, 7, d_mcnt)
+    ctx.sync()
+    in_list = int(np.isin(shipmode, [2, 5]).sum())
+    assert int(d_mcnt.download(np.uint64, len(mcounts)).sum()) == in_list, "Q12 ship mode parity"
+
+    key_lo, key_hi = 1, bits // 2
+    entries = [("q4_chain", chain),
+               ("probe_select_member", lambda: okey.lay.scan_select_member(okey.words, d_set, base, bits, bm_o, d_ocnt)),
+               ("probe_select_member_in_chain",
+                lambda: okey.lay.scan_select_member(okey.words, d_set, base, bits, bm_o, d_ocnt, bm_od)),
+               ("probe_count_member", lambda: okey.lay.scan_count_member(okey.words, d_set, base, bits, d_ocnt)),
+               ("probe_select_between", lambda: okey.lay.scan_select_between(okey.words, key_lo, key_hi, bm_o, d_ocnt)),
+               ("probe_scan_sum", lambda: okey.lay.scan_sum(okey.words, d_osum)),
+               ("probe_unpack", lambda: okey.lay.unpack(okey.words, d_out)),
+               ("build_member", lambda: lkey.lay.scan_build_member(lkey.words, base, bits, d_set2, d_lcnt)),
+               ("build_member_in_chain", lambda: lkey.lay.scan_build_member(lkey.words, base, bits, d_set2, d_lcnt, bm_l)),
+               ("build_select_between", lambda: lkey.lay.scan_select_between(lkey.words, key_lo, key_hi, bm_x, d_lcnt)),
+               ("build_scan_sum", lambda: lkey.lay.scan_sum(lkey.words, d_lsum)),
+               ("build_unpack", lambda: lkey.lay.unpack(lkey.words, d_out)),
+               ("shipmode_select_member", lambda: mode.lay.scan_select_member(mode.words, d_inlist, 0, 7, bm_x, d_mcnt)),
+               ("shipmode_count_member", lambda: mode.lay.scan_count_member(mode.words, d_inlist, 0, 7, d_mcnt)),
+               ("shipmode_select_between", lambda: mode.lay.scan_select_between(mode.words, 2, 5, bm_x, d_mcnt)),
+               ("shipmode_scan_sum", lambda: mode.lay.scan_sum(mode.words, d_msum)),
+               ("shipmode_unpack", lambda: mode.lay.unpack(mode.words, d_out))]
+    samples = timed_interleaved(ctx, entries)
+    parity("after timing")
+    med = {k: float(np.median(x)) for k, x in samples.items()}
+    kind32 = (4, True)
+
+    def census(e, kind, b, nb):
+        fs = forms.member_form_groups(e.descs, kind, b, nb)
+        return {f: fs.count(f) for f in sorted(set(fs) - {None})}
+
+    def cell(prefix, call, e):
+        return {"ms": med[call], "select_between_ms": med[prefix + "_select_between"],
+                "scan_sum_ms": med[prefix + "_scan_sum"], "unpack_ms": med[prefix + "_unpack"],
+                "over_select_between": med[call] / med[prefix + "_select_between"],
+                "over_scan_sum": med[call] / med[prefix + "_scan_sum"],
+                "over_unpack": med[call] / med[prefix + "_unpack"],
+                "packed_read_GBps": e.nbytes / (med[call] * 1e-3) / 1e9}
+
+    out = {"orders": n_orders, "lineitems": n, "set_bits": bits, "set_bytes": sw * 8,
+           "selected": {"lineitems_commit_lt_receipt": int(late.sum()), "orders_in_quarter": int(in_quarter.sum()),
+                        "orders_with_a_late_lineitem": int(exists.sum()), "orders_counted": int(want.sum())},
+           "counts_by_priority": [int(x) for x in want],
+           "widths": {"o_orderkey": okey.widths, "l_orderkey": lkey.widths, "o_orderdate": odate.widths,
+                      "o_orderpriority": oprio.widths, "l_shipmode": mode.widths},
+           "packed_bytes": {"o_orderkey": okey.nbytes, "l_orderkey": lkey.nbytes, "l_shipmode": mode.nbytes},
+           "segments_by_form": {"probe_o_orderkey": census(okey, kind32, base, bits),
+                                "build_l_orderkey": census(lkey, kind32, base, bits),
+                                "q12_shipmode": census(mode, (1, False), 0, 7)},
+           "ms": med, "q4_chain_ms": med["q4_chain"],
+           "probe": dict(cell("probe", "probe_select_member", okey), in_chain_ms=med["probe_select_member_in_chain"],
+                         count_ms=med["probe_count_member"]),
+           "build": dict(cell("build", "build_member", lkey), in_chain_ms=med["build_member_in_chain"]),
+           "q12_shipmode": dict(cell("shipmode", "shipmode_select_member", mode), count_ms=med["shipmode_count_member"],
+                                rows_in_list=in_list),
+           "samples_ms": {k: [round(t, 5) for t in x] for k, x in samples.items()},
+           "note": ("Synthetic orders / lineitem at SF10 size; l_commitdate and l_receiptdate are independent uniform draws. "
+                    "probe_* on o_orderkey, build_* on l_orderkey, shipmode_* on a 7-valued uint8 code over the lineitem "
+                    "rows; *_select_between = adac_scan_select_between on the same column (lower half of the keys; codes "
+                    "2 .. 5; on the sorted key columns it skips the segments outside the range on their "
+                    "descriptors), *_scan_sum = adac_scan_sum of the column (reads every packed byte), *_unpack = adac_unpack "
+                    "of the column; *_in_chain = the call under the chain's bitmap.  "
+                    "Medians of %d interleaved rounds of %d calls each" % (ROUNDS, INNER))}
+    print("q4_packed chain %.4f ms; " % med["q4_chain"] + "; ".join(
+        "%s %.4f (between %.4f, sum %.4f, unpack %.4f)" % (name, med[call], med[p + "_select_between"], med[p + "_scan_sum"],
+                                                          med[p + "_unpack"])
+        for name, call, p in (("probe", "probe_select_member", "probe"), ("build", "build_member", "build"),
+                              ("ship mode", "shipmode_select_member", "shipmode"))), file=sys.stderr, flush=True)
+    ctx.close()
+    return out
+
+
 def bitpacking_select_gather(adac, n=59_986_052):
     """Filter -> project on DuckDB's own BITPACKING blocks: adac_bp_unpack_selected (values only, then values + ids) of
     l_extendedprice (int32, FOR), the 6-valued uint8 code and a sorted copy of l_partkey (DELTA_FOR) under five bitmaps
@@ -1392,6 +1531,7 @@ def main():
             "q6_bitpacking": lambda: q6_bitpacking(adac),
             "q12_bitpacking": lambda: q12_bitpacking(adac),
             "q12_packed": lambda: q12_packed(adac),
+            "q4_packed": lambda: q4_packed(adac),
             "bitpacking_select_gather": lambda: bitpacking_select_gather(adac),
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "q1_filtered_packed": lambda: q1_filtered_packed(adac),

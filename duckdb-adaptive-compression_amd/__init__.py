@@ -181,6 +181,9 @@ SIGNATURES = {
     "adac_scan_select_between": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "adac_scan_select_compare": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "adac_scan_count_compare": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "adac_scan_select_member": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "adac_scan_count_member": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp]),
+    "adac_scan_build_member": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "adac_unpack_selected": (_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "adac_scan_count_between_valid": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "adac_bp_layout_create": (_int, [_vp, _int, _vp, _vp, _vp, _u64, _P(_vp)]),
@@ -622,6 +625,25 @@ class Layout:
         """The counts of scan_select_compare alone."""
         _check(lib().adac_scan_count_compare(self._h, _dptr(d_words), other._h, _dptr(d_other_words),
                                              _dptr(d_validity), int(cmp), _dptr(d_counts)), "adac_scan_count_compare")
+
+    def scan_select_member(self, d_words, d_set, set_base, set_bits, d_bitmap, d_counts, d_validity=None):
+        """Selection bitmap (ceil(value_span / 64) words) + per-segment counts of the rows whose value is a member of
+        d_set, a bit set over the values [set_base, set_base + set_bits - 1] in the column type's order (bit i of word
+        i / 64 = set_base + i; set_base a bit pattern of the type, as lo of scan_select_between): an IN list, or the
+        probe side of a semi-join.  d_validity: a mask in this layout's element space."""
+        _check(lib().adac_scan_select_member(self._h, _dptr(d_words), _dptr(d_validity), _dptr(d_set), set_base & NO_MIN,
+                                             int(set_bits), _dptr(d_bitmap), _dptr(d_counts)), "adac_scan_select_member")
+
+    def scan_count_member(self, d_words, d_set, set_base, set_bits, d_counts, d_validity=None):
+        """The counts of scan_select_member alone."""
+        _check(lib().adac_scan_count_member(self._h, _dptr(d_words), _dptr(d_validity), _dptr(d_set), set_base & NO_MIN,
+                                            int(set_bits), _dptr(d_counts)), "adac_scan_count_member")
+
+    def scan_build_member(self, d_words, set_base, set_bits, d_set, d_counts, d_validity=None):
+        """The build side: d_set (ceil(set_bits / 64) words, fully written) gets bit t set iff a row wanted by d_validity
+        holds the value set_base + t; d_counts: the wanted rows per segment whose value lies in the domain."""
+        _check(lib().adac_scan_build_member(self._h, _dptr(d_words), _dptr(d_validity), set_base & NO_MIN, int(set_bits),
+                                            _dptr(d_set), _dptr(d_counts)), "adac_scan_build_member")
 
     def unpack_selected(self, d_words, d_bitmap, d_out, d_out_ids=None, want_total=True):
         """Values (and optionally element indices) of the rows whose bitmap bit is set, dense, in row order.

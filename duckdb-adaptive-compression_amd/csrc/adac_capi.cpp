@@ -1149,6 +1149,73 @@ extern "C" adac_status adac_scan_count_compare(adac_layout *a, const uint64_t *d
 	return scan_compare(a, d_a_words, b, d_b_words, d_validity, cmp, false, nullptr, d_counts);
 }
 
+// Member scans: what adac_scan_select_member, adac_scan_count_member (probe) and adac_scan_build_member share.  Checks
+// the arguments, makes sure `l` has its scan groups, clears the counts (every wave adds its part; this also writes the
+// segments without rows), for the select form the bitmap, for the build the set (groups OR into the words they share).
+enum MemberCall { MEMBER_SELECT, MEMBER_COUNT, MEMBER_BUILD };
+
+static bool words_overlap(const uint64_t *p, uint64_t np, const uint64_t *q, uint64_t nq) {
+	return p && q && np && nq && p < q + nq && q < p + np;
+}
+
+static adac_status scan_member(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity, uint64_t *d_set,
+                               uint64_t set_base, uint64_t set_bits, MemberCall call, uint64_t *d_bitmap,
+                               uint64_t *d_counts) {
+	if (!l) return ADAC_ERR_INVALID_ARGUMENT;
+	if (set_bits < 1ull || set_bits > (1ull << 32)) return ADAC_ERR_INVALID_ARGUMENT;
+	// the domain stays inside the type: in T's order (bits ^ sign bit) its last value is at most the type's maximum
+	const uint64_t tmask = adac::type_mask(l->type_size), sbit = adac::type_sign_bit(l->type_size, l->is_signed);
+	if (set_base > tmask) return ADAC_ERR_INVALID_ARGUMENT;
+	const uint64_t bbase = set_base ^ sbit;
+	if (tmask - bbase < set_bits - 1ull) return ADAC_ERR_INVALID_ARGUMENT;
+	if ((l->nseg && !d_counts) || !d_set) return ADAC_ERR_INVALID_ARGUMENT;
+	if ((l->total_values && !d_words) || !aligned16(d_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	const uint64_t span_words = (l->value_span + 63) / 64, set_words = (set_bits + 63) / 64;
+	if (call == MEMBER_SELECT) {
+		if ((l->value_span && !d_bitmap) || (d_bitmap && d_bitmap == d_validity)) return ADAC_ERR_INVALID_ARGUMENT;
+		if (d_set == d_bitmap || words_overlap(d_set, set_words, d_bitmap, span_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	if (d_set == d_validity || words_overlap(d_set, set_words, d_validity, span_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (l->nseg == 0) return ADAC_OK; // no counts, no elements, no rows
+	ADAC_HIP(hipSetDevice(l->ctx->device));
+	adac_status gst = ensure_scan_groups(l);
+	if (gst != ADAC_OK) return gst;
+	ADAC_HIP(hipMemsetAsync(d_counts, 0, l->nseg * sizeof(uint64_t), l->ctx->stream));
+	if (call == MEMBER_BUILD) {
+		ADAC_HIP(hipMemsetAsync(d_set, 0, set_words * sizeof(uint64_t), l->ctx->stream));
+		ADAC_HIP(adac::launch_scan_member_build(l->ctx->stream, l->type_size, l->is_signed, l->d_groups, l->ngroups, d_words,
+		                                        d_validity, set_base, set_bits, d_set, d_counts));
+		return ADAC_OK;
+	}
+	if (call == MEMBER_SELECT && l->value_span) {
+		ADAC_HIP(hipMemsetAsync(d_bitmap, 0, span_words * sizeof(uint64_t), l->ctx->stream));
+	}
+	if (call == MEMBER_SELECT && !d_bitmap) return ADAC_OK; // no element, so no row
+	ADAC_HIP(adac::launch_scan_member(l->ctx->stream, l->type_size, l->is_signed, l->d_groups, l->ngroups, d_words,
+	                                  d_validity, d_set, set_base, set_bits, call == MEMBER_SELECT ? d_bitmap : nullptr,
+	                                  d_counts));
+	return ADAC_OK;
+}
+
+extern "C" adac_status adac_scan_select_member(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity,
+                                               const uint64_t *d_set, uint64_t set_base, uint64_t set_bits,
+                                               uint64_t *d_bitmap, uint64_t *d_counts) {
+	return scan_member(l, d_words, d_validity, const_cast<uint64_t *>(d_set), set_base, set_bits, MEMBER_SELECT, d_bitmap,
+	                   d_counts);
+}
+
+extern "C" adac_status adac_scan_count_member(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity,
+                                              const uint64_t *d_set, uint64_t set_base, uint64_t set_bits,
+                                              uint64_t *d_counts) {
+	return scan_member(l, d_words, d_validity, const_cast<uint64_t *>(d_set), set_base, set_bits, MEMBER_COUNT, nullptr,
+	                   d_counts);
+}
+
+extern "C" adac_status adac_scan_build_member(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity,
+                                              uint64_t set_base, uint64_t set_bits, uint64_t *d_set, uint64_t *d_counts) {
+	return scan_member(l, d_words, d_validity, d_set, set_base, set_bits, MEMBER_BUILD, nullptr, d_counts);
+}
+
 // SUM(value), COUNT(*) GROUP BY key over two packed columns of one table (Q1's shape, TPCH_runtime.txt:2-6)
 extern "C" adac_status adac_scan_group_sum_valid(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
                                                  const uint64_t *d_key_words, const uint64_t *d_validity, uint32_t ngroups,

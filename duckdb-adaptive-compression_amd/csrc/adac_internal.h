@@ -200,6 +200,14 @@ hipError_t launch_scan_compare(hipStream_t s, uint32_t a_type_size, bool a_signe
                                const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,
                                const adac_segment_desc *d_bdescs, const uint64_t *d_bwords, const uint64_t *d_validity,
                                uint32_t cmp, uint64_t *d_bitmap, uint64_t *d_counts);
+// rows whose value is a member of the bit set d_set over [set_base, set_base + set_bits - 1] per segment, and their bitmap
+// unless d_bitmap is null; the set built from the wanted rows of a column (adac_scan_member.inl)
+hipError_t launch_scan_member(hipStream_t s, uint32_t type_size, bool is_signed, const ScanGroup *d_groups,
+                              uint64_t ngroups, const uint64_t *d_words, const uint64_t *d_validity, const uint64_t *d_set,
+                              uint64_t set_base, uint64_t set_bits, uint64_t *d_bitmap, uint64_t *d_counts);
+hipError_t launch_scan_member_build(hipStream_t s, uint32_t type_size, bool is_signed, const ScanGroup *d_groups,
+                                    uint64_t ngroups, const uint64_t *d_words, const uint64_t *d_validity,
+                                    uint64_t set_base, uint64_t set_bits, uint64_t *d_set, uint64_t *d_counts);
 hipError_t launch_encode_1p(hipStream_t s, uint32_t type_size, bool sign_extend, uint64_t null_bits, int rule,
                             int pad_to_byte, adac_segment_desc *d_descs, uint64_t nseg, const void *d_vals,
                             const uint64_t *d_validity, uint64_t *d_minmax, void *d_scan_state, uint64_t *d_words);

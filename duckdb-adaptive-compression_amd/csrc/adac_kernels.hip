@@ -1957,6 +1957,7 @@ hipError_t dispatch_size(uint32_t type_size, F &&f) {
 #include "adac_group_sum.inl"
 #include "adac_sum_product.inl"
 #include "adac_scan_compare.inl"
+#include "adac_scan_member.inl"
 #include "adac_group_product.inl"
 #include "adac_group_product3.inl"
 #include "adac_group_q1.inl"
@@ -2315,6 +2316,58 @@ hipError_t launch_scan_compare(hipStream_t s, uint32_t a_type_size, bool a_signe
 		if (d_validity) launch(k_scan_compare<true, true>); else launch(k_scan_compare<false, true>);
 	} else {
 		if (d_validity) launch(k_scan_compare<true, false>); else launch(k_scan_compare<false, false>);
+	}
+	return hipGetLastError();
+}
+
+// the domain [set_base, set_base + set_bits - 1] of a member scan in the biased form the kernels work in
+static MemberDomain member_domain(uint32_t type_size, bool is_signed, uint64_t set_base, uint64_t set_bits) {
+	MemberDomain dom;
+	dom.tmask = type_mask(type_size);
+	dom.sbit = type_sign_bit(type_size, is_signed);
+	dom.bbase = set_base ^ dom.sbit;
+	dom.set_bits = set_bits;
+	return dom;
+}
+
+// Rows whose value is a member of the bit set d_set over [set_base, set_base + set_bits - 1], per segment, and their
+// bitmap when d_bitmap is given (adac_scan_member.inl): one workgroup per scan group; the caller has checked the domain
+// against the type and cleared d_counts and the bitmap
+hipError_t launch_scan_member(hipStream_t s, uint32_t type_size, bool is_signed, const ScanGroup *d_groups,
+                              uint64_t ngroups, const uint64_t *d_words, const uint64_t *d_validity, const uint64_t *d_set,
+                              uint64_t set_base, uint64_t set_bits, uint64_t *d_bitmap, uint64_t *d_counts) {
+	if (ngroups == 0) return hipSuccess;
+	const MemberDomain dom = member_domain(type_size, is_signed, set_base, set_bits);
+	unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_counts);
+	uint32_t *bitmap32 = reinterpret_cast<uint32_t *>(d_bitmap);
+	uint32_t *set32 = reinterpret_cast<uint32_t *>(const_cast<uint64_t *>(d_set)); // the probe only reads it
+	auto launch = [&](auto kernel) {
+		hipLaunchKernelGGL(kernel, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_groups, d_words, dom, d_validity,
+		                   set32, bitmap32, counts);
+	};
+	if (d_bitmap) {
+		if (d_validity) launch(k_scan_member<true, true>); else launch(k_scan_member<false, true>);
+	} else {
+		if (d_validity) launch(k_scan_member<true, false>); else launch(k_scan_member<false, false>);
+	}
+	return hipGetLastError();
+}
+
+// The set of the wanted rows' values and the rows inside the domain per segment; the caller has cleared d_set and
+// d_counts
+hipError_t launch_scan_member_build(hipStream_t s, uint32_t type_size, bool is_signed, const ScanGroup *d_groups,
+                                    uint64_t ngroups, const uint64_t *d_words, const uint64_t *d_validity,
+                                    uint64_t set_base, uint64_t set_bits, uint64_t *d_set, uint64_t *d_counts) {
+	if (ngroups == 0) return hipSuccess;
+	const MemberDomain dom = member_domain(type_size, is_signed, set_base, set_bits);
+	unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_counts);
+	uint32_t *set32 = reinterpret_cast<uint32_t *>(d_set);
+	if (d_validity) {
+		hipLaunchKernelGGL(k_scan_member_build<true>, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_groups, d_words,
+		                   dom, d_validity, set32, counts);
+	} else {
+		hipLaunchKernelGGL(k_scan_member_build<false>, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_groups, d_words,
+		                   dom, d_validity, set32, counts);
 	}
 	return hipGetLastError();
 }

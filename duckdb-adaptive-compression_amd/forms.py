@@ -15,6 +15,9 @@ returns {"fast": scan groups of a, "generic": scan groups of a} with the default
 The compare scan (k_scan_compare, csrc/adac_scan_compare.inl) has a third form in front of the two: "header", when both
 columns have a frame() and the intervals [frame, frame + 2^w - 1] are disjoint as mathematical integers (or both are
 single values), so that the descriptors alone decide every row.  compare_form_groups names the form per segment pair.
+
+The member scans (k_scan_member / k_scan_member_build, csrc/adac_scan_member.inl) choose a reader and a set access per
+segment from the descriptor, the type and the domain (set_base, set_bits): member_form_groups mirrors member_plan.
 """
 from itertools import repeat
 
@@ -113,4 +116,35 @@ def compare_form_groups(descs_a, descs_b, a_type=(4, True), b_type=(4, True)):
             elif value_ok(da, a_type, 4, False) and value_ok(db, b_type, 1, False):
                 form = "fast"
         out.append(form)
+    return out
+
+
+MEMBER_SLICE_BITS = 65536   # kMemberSliceBits
+
+
+def member_form_groups(descs, type, set_base, set_bits):
+    """adac_scan_select_member / adac_scan_count_member / adac_scan_build_member: member_plan, per segment "header",
+    "walk-slice", "walk-direct", "staged-slice" or "staged-direct" (every scan group of a segment takes the same form);
+    None for a segment without rows.  type: (size in bytes, signed); set_base: a bit pattern of the type."""
+    size, signed = type
+    sbit = (1 << (8 * size - 1)) if signed else 0
+    dlo = (int(set_base) ^ sbit)            # biased by the sign bit every interval is one of unsigned numbers
+    dhi = dlo + int(set_bits) - 1
+    out = []
+    for d in descs:
+        if int(d["count"]) == 0:
+            out.append(None)
+            continue
+        m = frame(d, size, signed)
+        if m is None:
+            out.append("staged-direct")
+            continue
+        bmin = m + sbit
+        btop = bmin + (1 << int(d["width"])) - 1
+        if btop < dlo or dhi < bmin:
+            out.append("header")
+            continue
+        lo, hi = max(bmin - dlo, 0), min(btop, dhi) - dlo + 1   # set bits [lo, hi) are what the segment can reach
+        reader = "walk" if value_ok(d, type, 4, False) else "staged"
+        out.append(reader + ("-slice" if hi - lo <= MEMBER_SLICE_BITS else "-direct"))
     return out

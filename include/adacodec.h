@@ -525,6 +525,42 @@ adac_status adac_scan_count_compare(adac_layout *a, const uint64_t *d_a_words, a
                                     const uint64_t *d_b_words, const uint64_t *d_validity, uint32_t cmp,
                                     uint64_t *d_counts);
 
+/* Filter push-down against a BIT SET INDEXED BY VALUE, and the scan that builds such a set: an IN list (TPC-H Q12's
+ * l_shipmode IN ('MAIL', 'SHIP'), Q16, Q19) and the two sides of a semi-join on a dense integer key (Q4's EXISTS:
+ * adac_scan_select_compare on the lineitem dates, adac_scan_build_member over l_orderkey under that bitmap,
+ * adac_scan_select_member over o_orderkey, adac_scan_group_sum_valid for the counts) on the packed bytes.
+ * The set covers the values [set_base, set_base + set_bits - 1] in T's own order; set_base is a bit pattern of T,
+ * zero-extended (adac_scan_select_between's convention for lo).  d_set has ceil(set_bits / 64) words; bit i of word
+ * i / 64 stands for the value set_base + i.  The index of a value v is t = (bits(v) ^ sbit) - (bits(set_base) ^ sbit) in
+ * 64-bit unsigned arithmetic, sbit the sign bit of a signed T and 0 otherwise; v is in the domain iff t < set_bits.
+ * Probe (select / count): a row is selected iff its bit is set in d_validity (element space, val_off + row; NULL: every
+ * row), its value — the one adac_unpack would write — is in the domain and its set bit is 1.  Bits of the last set word
+ * at positions >= set_bits are never treated as members, whatever they hold.  d_bitmap and d_counts follow
+ * adac_scan_select_compare's rules: both fully written by the call, bits of uncovered elements zero, the result usable
+ * as any other scan's d_validity, no mask word outside ceil(value_span / 64) read.
+ * Build: d_set is fully written by the call (the caller clears nothing; bits >= set_bits of the last word end up zero):
+ * bit t is set iff some wanted row (d_validity as above) has a value in the domain with index t; wanted rows outside the
+ * domain are ignored.  d_counts[seg] = the wanted rows of the segment whose value lies in the domain (rows, not distinct
+ * values); segments without rows get 0.
+ * ADAC_ERR_INVALID_ARGUMENT, on the host before anything is enqueued: set_bits outside 1 ... 2^32; a domain that leaves
+ * the type (set_base with bits above the type, or set_base + set_bits - 1 past T's maximum in T's order); a NULL layout;
+ * NULL d_counts while the layout has segments; NULL d_set; a NULL or not 16-byte aligned words pointer while there are
+ * rows; for the select form NULL d_bitmap while value_span != 0, or d_bitmap == d_validity; d_set overlapping d_bitmap
+ * or d_validity.  A layout without segments returns ADAC_OK without touching the device (the build then writes no set).
+ * All three calls enqueue on the context's stream and synchronise no more than adac_scan_select_compare does.
+ * A scan group whose segment is packed against a frame of reference that stays inside the type, with
+ * [frame, frame + 2^width - 1] apart from the domain, is decided from the descriptor: no packed word and no set word is
+ * read (the zonemap skip of a join filter).  A segment whose interval reaches at most 65536 bits of the set (every width
+ * up to 16) works on a copy of that window in on-chip memory. */
+adac_status adac_scan_select_member(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity,
+                                    const uint64_t *d_set, uint64_t set_base, uint64_t set_bits, uint64_t *d_bitmap,
+                                    uint64_t *d_counts);
+/* the counts alone: no bitmap is written */
+adac_status adac_scan_count_member(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity,
+                                   const uint64_t *d_set, uint64_t set_base, uint64_t set_bits, uint64_t *d_counts);
+adac_status adac_scan_build_member(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity,
+                                   uint64_t set_base, uint64_t set_bits, uint64_t *d_set, uint64_t *d_counts);
+
 /* Materialise only the selected rows: d_out receives, densely and in row order (segment by segment), the values of
  * the rows whose bit is set in d_bitmap (the result of adac_scan_select_between, or any mask over the element index
  * space); d_out_ids, if not NULL, receives their element indices (val_off + row).  *total_out, if not NULL, is set
