@@ -99,6 +99,13 @@ struct adac_layout {
 	uint32_t group_calls = 0;        // ... and how often it ran: its hand-over word alternates between two slots
 };
 
+// A column argument of an entry point: a layout and its packed words.  Converts to what the launchers take.
+struct ColumnArg {
+	adac_layout *l;
+	const uint64_t *d_words;
+	operator adac::Column() const { return {l->type_size, l->is_signed, l->d_descs, d_words}; }
+};
+
 static adac_status descs_changed(adac_layout *l);
 static void note_widths(adac_layout *l, const adac_segment_desc *descs);
 static adac_status ensure_scan_groups(adac_layout *l);
@@ -852,7 +859,7 @@ extern "C" adac_status adac_unpack(adac_layout *l, const uint64_t *d_words, void
 		adac_status st = tile_records(l, &recs);
 		if (st != ADAC_OK) return st;
 	}
-	ADAC_HIP(adac::launch_unpack(l->ctx->stream, l->type_size, l->d_descs, l->d_tiles, l->ntiles, d_words, d_out, recs));
+	ADAC_HIP(adac::launch_unpack(l->ctx->stream, ColumnArg {l, d_words}, l->d_tiles, l->ntiles, d_out, recs));
 	return ADAC_OK;
 }
 
@@ -864,7 +871,7 @@ extern "C" adac_status adac_unpack_range(adac_layout *l, const uint64_t *d_words
 	if (!d_words || !d_out || !aligned16(d_words) || !aligned16(d_out)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	RangeArgs r {(uint32_t)seg, (uint32_t)start, (uint32_t)count, out_off};
-	ADAC_HIP(adac::launch_unpack_range(l->ctx->stream, l->type_size, l->d_descs, r, d_words, d_out));
+	ADAC_HIP(adac::launch_unpack_range(l->ctx->stream, ColumnArg {l, d_words}, r, d_out));
 	return ADAC_OK;
 }
 
@@ -958,7 +965,7 @@ extern "C" adac_status adac_fetch_rows(adac_layout *l, const uint64_t *d_words, 
 	if (n == 0) return ADAC_OK;
 	if (!d_words || !d_segs || !d_rows || !d_out) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
-	ADAC_HIP(adac::launch_fetch(l->ctx->stream, l->type_size, l->d_descs, d_words, d_segs, d_rows, n, d_out));
+	ADAC_HIP(adac::launch_fetch(l->ctx->stream, ColumnArg {l, d_words}, d_segs, d_rows, n, d_out));
 	return ADAC_OK;
 }
 
@@ -1065,6 +1072,55 @@ static adac_status ensure_scan_groups(adac_layout *l) {
 	return ADAC_OK;
 }
 
+// the launchers' view of an entry point's columns, in the same order
+template <size_t N>
+struct LaunchColumns {
+	adac::Column c[N];
+	explicit LaunchColumns(const ColumnArg (&cols)[N]) {
+		for (size_t i = 0; i < N; i++) c[i] = cols[i];
+	}
+};
+static adac::ScanWork scan_work(const adac_layout *l) { return {l->d_tiles, l->ntiles, l->d_groups, l->ngroups}; }
+
+// Are these the columns of one table?  Layouts of one context over the same rows, segment by segment, and packed words
+// wherever there are rows, 16-byte aligned.
+template <size_t N>
+static bool same_rows(const ColumnArg (&cols)[N]) {
+	for (const ColumnArg &c : cols) {
+		if (!c.l || c.l->ctx != cols[0].l->ctx || c.l->counts != cols[0].l->counts) return false;
+		if ((c.l->total_values && !c.d_words) || !aligned16(c.d_words)) return false;
+	}
+	return true;
+}
+
+// The outputs of a select / count scan over a layout of nseg segments and value_span elements: rows per segment and,
+// for the select form, their bitmap.  ok(): counts where there are segments, a bitmap where there are elements, and not
+// the mask itself; clear_counts() / clear_bitmap(): both start from zero (every wave adds its part and ORs the words it
+// shares; this also writes the segments without rows and the bits no segment covers), in the order each scan has always
+// enqueued them.  bitmap(): what the launcher gets.
+// scan_range (adac_scan_select_between) keeps a check of its own, which differs in one corner: its test has no
+// `d_bitmap &&`, so with value_span == 0 and both d_bitmap and d_validity null it refuses the call these accept.
+struct SelectOutputs {
+	uint64_t nseg, value_span;
+	bool want_bitmap;
+	uint64_t *d_bitmap, *d_counts;
+	bool ok(const uint64_t *d_validity) const {
+		if (nseg && !d_counts) return false;
+		return !want_bitmap || !((value_span && !d_bitmap) || (d_bitmap && d_bitmap == d_validity));
+	}
+	adac_status clear_counts(hipStream_t stream) const {
+		ADAC_HIP(hipMemsetAsync(d_counts, 0, nseg * sizeof(uint64_t), stream));
+		return ADAC_OK;
+	}
+	adac_status clear_bitmap(hipStream_t stream) const {
+		if (want_bitmap && value_span) {
+			ADAC_HIP(hipMemsetAsync(d_bitmap, 0, ((value_span + 63) / 64) * sizeof(uint64_t), stream));
+		}
+		return ADAC_OK;
+	}
+	uint64_t *bitmap() const { return want_bitmap ? d_bitmap : nullptr; }
+};
+
 extern "C" adac_status adac_scan_sum_valid(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity,
                                            uint64_t *d_sums);
 extern "C" adac_status adac_scan_sum(adac_layout *l, const uint64_t *d_words, uint64_t *d_sums) {
@@ -1076,7 +1132,6 @@ extern "C" adac_status adac_scan_sum_valid(adac_layout *l, const uint64_t *d_wor
 	if (!l || (l->nseg && !d_sums) || (l->total_values && !d_words)) return ADAC_ERR_INVALID_ARGUMENT;
 	if (!aligned16(d_words)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
-	const uint64_t sbit = adac::type_sign_bit(l->type_size, l->is_signed);
 	adac::ScanGroupList gl;
 	adac_status gst = scan_group_list(l, &gl);
 	if (gst != ADAC_OK) return gst;
@@ -1085,55 +1140,42 @@ extern "C" adac_status adac_scan_sum_valid(adac_layout *l, const uint64_t *d_wor
 	if (l->nseg && (!gl.d_res_cells || l->has_empty_segments)) {
 		ADAC_HIP(hipMemsetAsync(d_sums, 0, l->nseg * sizeof(uint64_t), l->ctx->stream));
 	}
-	ADAC_HIP(adac::launch_scan_sum(l->ctx->stream, l->type_size, gl, d_words, d_validity, sbit, d_sums));
+	ADAC_HIP(adac::launch_scan_sum(l->ctx->stream, ColumnArg {l, d_words}, gl, d_validity, d_sums));
 	return ADAC_OK;
 }
 
 // SUM(a * b) per segment over two packed columns of one table under a selection bitmap (Q6's aggregate)
 extern "C" adac_status adac_scan_sum_product(adac_layout *a, const uint64_t *d_a_words, adac_layout *b,
                                              const uint64_t *d_b_words, const uint64_t *d_validity, uint64_t *d_sums) {
-	if (!a || !b || a->ctx != b->ctx) return ADAC_ERR_INVALID_ARGUMENT;
-	if (a->counts != b->counts) return ADAC_ERR_INVALID_ARGUMENT; // the same rows, segment by segment
-	if (a->nseg && !d_sums) return ADAC_ERR_INVALID_ARGUMENT;
-	if (a->total_values && (!d_a_words || !d_b_words)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (!aligned16(d_a_words) || !aligned16(d_b_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	const ColumnArg cols[] = {{a, d_a_words}, {b, d_b_words}};
+	if (!same_rows(cols) || (a->nseg && !d_sums)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(a->ctx->device));
 	adac_status gst = ensure_scan_groups(a);
 	if (gst != ADAC_OK) return gst;
 	// every wave adds its part: the sums start from zero (this also writes the segments without rows)
 	if (a->nseg) ADAC_HIP(hipMemsetAsync(d_sums, 0, a->nseg * sizeof(uint64_t), a->ctx->stream));
-	ADAC_HIP(adac::launch_scan_sum_product(a->ctx->stream, a->type_size, a->is_signed, b->type_size, b->is_signed,
-	                                       a->d_groups, a->ngroups, d_a_words, b->d_descs, d_b_words, d_validity, d_sums));
+	ADAC_HIP(adac::launch_scan_sum_product(a->ctx->stream, cols[0], cols[1], scan_work(a), d_validity,
+	                                       d_sums));
 	return ADAC_OK;
 }
 
 // Rows where value(a) <cmp> value(b): what adac_scan_select_compare and adac_scan_count_compare share.  Checks the
-// arguments, makes sure `a` has its scan groups, clears the counts (every wave adds its part; this also writes the
-// segments without rows) and, for the select form, the bitmap (plain write-out: groups OR into the words they share).
+// arguments, makes sure `a` has its scan groups and clears the outputs.
 static adac_status scan_compare(adac_layout *a, const uint64_t *d_a_words, adac_layout *b, const uint64_t *d_b_words,
                                 const uint64_t *d_validity, uint32_t cmp, bool want_bitmap, uint64_t *d_bitmap,
                                 uint64_t *d_counts) {
-	if (!a || !b || a->ctx != b->ctx) return ADAC_ERR_INVALID_ARGUMENT;
-	if (a->counts != b->counts) return ADAC_ERR_INVALID_ARGUMENT; // the same rows, segment by segment
-	if (cmp < 1u || cmp > 6u) return ADAC_ERR_INVALID_ARGUMENT;
-	if (a->nseg && !d_counts) return ADAC_ERR_INVALID_ARGUMENT;
-	if (a->total_values && (!d_a_words || !d_b_words)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (!aligned16(d_a_words) || !aligned16(d_b_words)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (want_bitmap && ((a->value_span && !d_bitmap) || (d_bitmap && d_bitmap == d_validity))) {
-		return ADAC_ERR_INVALID_ARGUMENT;
-	}
+	const ColumnArg cols[] = {{a, d_a_words}, {b, d_b_words}};
+	if (!same_rows(cols) || cmp < 1u || cmp > 6u) return ADAC_ERR_INVALID_ARGUMENT;
+	const SelectOutputs out {a->nseg, a->value_span, want_bitmap, d_bitmap, d_counts};
+	if (!out.ok(d_validity)) return ADAC_ERR_INVALID_ARGUMENT;
 	if (a->nseg == 0) return ADAC_OK; // no counts, no elements
 	ADAC_HIP(hipSetDevice(a->ctx->device));
-	adac_status gst = ensure_scan_groups(a);
-	if (gst != ADAC_OK) return gst;
-	ADAC_HIP(hipMemsetAsync(d_counts, 0, a->nseg * sizeof(uint64_t), a->ctx->stream));
-	if (want_bitmap && a->value_span) {
-		ADAC_HIP(hipMemsetAsync(d_bitmap, 0, ((a->value_span + 63) / 64) * sizeof(uint64_t), a->ctx->stream));
-	}
+	adac_status st = ensure_scan_groups(a);
+	if (st != ADAC_OK || (st = out.clear_counts(a->ctx->stream)) != ADAC_OK) return st;
+	if ((st = out.clear_bitmap(a->ctx->stream)) != ADAC_OK) return st;
 	if (want_bitmap && !d_bitmap) return ADAC_OK; // no element, so no row
-	ADAC_HIP(adac::launch_scan_compare(a->ctx->stream, a->type_size, a->is_signed, b->type_size, b->is_signed, a->d_groups,
-	                                   a->ngroups, d_a_words, b->d_descs, d_b_words, d_validity, cmp,
-	                                   want_bitmap ? d_bitmap : nullptr, d_counts));
+	ADAC_HIP(adac::launch_scan_compare(a->ctx->stream, cols[0], cols[1], scan_work(a), d_validity, cmp,
+	                                   out.bitmap(), d_counts));
 	return ADAC_OK;
 }
 
@@ -1150,8 +1192,8 @@ extern "C" adac_status adac_scan_count_compare(adac_layout *a, const uint64_t *d
 }
 
 // Member scans: what adac_scan_select_member, adac_scan_count_member (probe) and adac_scan_build_member share.  Checks
-// the arguments, makes sure `l` has its scan groups, clears the counts (every wave adds its part; this also writes the
-// segments without rows), for the select form the bitmap, for the build the set (groups OR into the words they share).
+// the arguments, makes sure `l` has its scan groups, clears the outputs and, for the build, the set (groups OR into the
+// words they share).
 enum MemberCall { MEMBER_SELECT, MEMBER_COUNT, MEMBER_BUILD };
 
 static bool words_overlap(const uint64_t *p, uint64_t np, const uint64_t *q, uint64_t nq) {
@@ -1164,36 +1206,33 @@ static adac_status scan_member(adac_layout *l, const uint64_t *d_words, const ui
 	if (!l) return ADAC_ERR_INVALID_ARGUMENT;
 	if (set_bits < 1ull || set_bits > (1ull << 32)) return ADAC_ERR_INVALID_ARGUMENT;
 	// the domain stays inside the type: in T's order (bits ^ sign bit) its last value is at most the type's maximum
-	const uint64_t tmask = adac::type_mask(l->type_size), sbit = adac::type_sign_bit(l->type_size, l->is_signed);
-	if (set_base > tmask) return ADAC_ERR_INVALID_ARGUMENT;
-	const uint64_t bbase = set_base ^ sbit;
-	if (tmask - bbase < set_bits - 1ull) return ADAC_ERR_INVALID_ARGUMENT;
-	if ((l->nseg && !d_counts) || !d_set) return ADAC_ERR_INVALID_ARGUMENT;
+	const adac::TypeWords t = adac::type_words(*l);
+	if (set_base > t.tmask) return ADAC_ERR_INVALID_ARGUMENT;
+	const uint64_t bbase = set_base ^ t.sbit;
+	if (t.tmask - bbase < set_bits - 1ull) return ADAC_ERR_INVALID_ARGUMENT;
+	const SelectOutputs out {l->nseg, l->value_span, call == MEMBER_SELECT, d_bitmap, d_counts};
+	if (!out.ok(d_validity) || !d_set) return ADAC_ERR_INVALID_ARGUMENT;
 	if ((l->total_values && !d_words) || !aligned16(d_words)) return ADAC_ERR_INVALID_ARGUMENT;
 	const uint64_t span_words = (l->value_span + 63) / 64, set_words = (set_bits + 63) / 64;
-	if (call == MEMBER_SELECT) {
-		if ((l->value_span && !d_bitmap) || (d_bitmap && d_bitmap == d_validity)) return ADAC_ERR_INVALID_ARGUMENT;
-		if (d_set == d_bitmap || words_overlap(d_set, set_words, d_bitmap, span_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (call == MEMBER_SELECT && (d_set == d_bitmap || words_overlap(d_set, set_words, d_bitmap, span_words))) {
+		return ADAC_ERR_INVALID_ARGUMENT;
 	}
 	if (d_set == d_validity || words_overlap(d_set, set_words, d_validity, span_words)) return ADAC_ERR_INVALID_ARGUMENT;
 	if (l->nseg == 0) return ADAC_OK; // no counts, no elements, no rows
 	ADAC_HIP(hipSetDevice(l->ctx->device));
-	adac_status gst = ensure_scan_groups(l);
-	if (gst != ADAC_OK) return gst;
-	ADAC_HIP(hipMemsetAsync(d_counts, 0, l->nseg * sizeof(uint64_t), l->ctx->stream));
+	adac_status st = ensure_scan_groups(l);
+	if (st != ADAC_OK || (st = out.clear_counts(l->ctx->stream)) != ADAC_OK) return st;
+	if ((st = out.clear_bitmap(l->ctx->stream)) != ADAC_OK) return st;
+	const adac::Column col = ColumnArg {l, d_words};
 	if (call == MEMBER_BUILD) {
 		ADAC_HIP(hipMemsetAsync(d_set, 0, set_words * sizeof(uint64_t), l->ctx->stream));
-		ADAC_HIP(adac::launch_scan_member_build(l->ctx->stream, l->type_size, l->is_signed, l->d_groups, l->ngroups, d_words,
-		                                        d_validity, set_base, set_bits, d_set, d_counts));
+		ADAC_HIP(adac::launch_scan_member_build(l->ctx->stream, col, scan_work(l), d_validity, set_base, set_bits, d_set,
+		                                        d_counts));
 		return ADAC_OK;
 	}
-	if (call == MEMBER_SELECT && l->value_span) {
-		ADAC_HIP(hipMemsetAsync(d_bitmap, 0, span_words * sizeof(uint64_t), l->ctx->stream));
-	}
 	if (call == MEMBER_SELECT && !d_bitmap) return ADAC_OK; // no element, so no row
-	ADAC_HIP(adac::launch_scan_member(l->ctx->stream, l->type_size, l->is_signed, l->d_groups, l->ngroups, d_words,
-	                                  d_validity, d_set, set_base, set_bits, call == MEMBER_SELECT ? d_bitmap : nullptr,
-	                                  d_counts));
+	ADAC_HIP(adac::launch_scan_member(l->ctx->stream, col, scan_work(l), d_validity, d_set, set_base, set_bits,
+	                                  out.bitmap(), d_counts));
 	return ADAC_OK;
 }
 
@@ -1226,29 +1265,17 @@ extern "C" adac_status adac_scan_group_sum(adac_layout *values, const uint64_t *
 	return adac_scan_group_sum_valid(values, d_value_words, keys, d_key_words, nullptr, ngroups, d_sums, d_counts);
 }
 
-// What the grouped scans share.  cols: the call's layouts with their packed words, `a` / the value layout first; required:
-// the output pointers the call cannot do without.  Checks the arguments (all layouts of one context and over the same
-// rows, segment by segment; 1 <= ngroups <= the bins the kernels hold; words wherever there are values, 16-byte
-// aligned), selects the device and makes sure `a` has its partial buffer (with the hand-over slots and the call counter
+// What the grouped scans share.  cols: the call's columns, `a` / the value column first; required: the output pointers
+// the call cannot do without.  Checks the arguments (the columns of one table; 1 <= ngroups <= the bins the kernels
+// hold), selects the device and makes sure `a` has its partial buffer (with the hand-over slots and the call counter
 // shared by all grouped entry points, cleared once) and its scan groups, the register-walk kernel's work items.
-struct GroupColumn {
-	adac_layout *l;
-	const uint64_t *d_words;
-};
 template <size_t N, size_t M>
-static adac_status group_scan_setup(const GroupColumn (&cols)[N], uint32_t ngroups, const void *const (&required)[M]) {
-	for (const GroupColumn &c : cols) {
-		if (!c.l) return ADAC_ERR_INVALID_ARGUMENT;
-	}
+static adac_status group_scan_setup(const ColumnArg (&cols)[N], uint32_t ngroups, const void *const (&required)[M]) {
 	for (const void *out : required) {
 		if (!out) return ADAC_ERR_INVALID_ARGUMENT;
 	}
+	if (!same_rows(cols) || ngroups == 0 || ngroups > adac::group_sum_max_groups()) return ADAC_ERR_INVALID_ARGUMENT;
 	adac_layout *a = cols[0].l;
-	if (ngroups == 0 || ngroups > adac::group_sum_max_groups()) return ADAC_ERR_INVALID_ARGUMENT;
-	for (const GroupColumn &c : cols) {
-		if (c.l->ctx != a->ctx || c.l->counts != a->counts) return ADAC_ERR_INVALID_ARGUMENT;
-		if ((a->total_values && !c.d_words) || !aligned16(c.d_words)) return ADAC_ERR_INVALID_ARGUMENT;
-	}
 	ADAC_HIP(hipSetDevice(a->ctx->device));
 	if (!a->d_group_partial) {
 		ADAC_HIP(hipMalloc(&a->d_group_partial, adac::group_sum_partial_bytes()));
@@ -1256,19 +1283,19 @@ static adac_status group_scan_setup(const GroupColumn (&cols)[N], uint32_t ngrou
 	}
 	return ensure_scan_groups(a);
 }
+// the state of a's next grouped scan
+static adac::GroupScanState next_group_call(adac_layout *a) { return {a->d_group_partial, a->group_calls++}; }
 
 // ... restricted to the rows whose bit is set in d_validity (the value layout's element space; NULL = every row)
 extern "C" adac_status adac_scan_group_sum_valid(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
                                                  const uint64_t *d_key_words, const uint64_t *d_validity, uint32_t ngroups,
                                                  uint64_t *d_sums, uint64_t *d_counts) {
-	const GroupColumn cols[] = {{values, d_value_words}, {keys, d_key_words}};
+	const ColumnArg cols[] = {{values, d_value_words}, {keys, d_key_words}};
 	const void *const required[] = {d_sums, d_counts};
 	adac_status st = group_scan_setup(cols, ngroups, required);
 	if (st != ADAC_OK) return st;
-	ADAC_HIP(adac::launch_group_sum(values->ctx->stream, values->type_size, values->is_signed, keys->type_size,
-	                                values->d_descs, values->d_tiles, values->ntiles, values->d_groups, values->ngroups,
-	                                d_value_words, keys->d_descs, d_key_words, ngroups, values->d_group_partial,
-	                                values->group_calls++, d_validity, d_sums, d_counts));
+	ADAC_HIP(adac::launch_group_sum(values->ctx->stream, cols[0], cols[1], scan_work(values), ngroups,
+	                                next_group_call(values), d_validity, d_sums, d_counts));
 	return ADAC_OK;
 }
 
@@ -1278,14 +1305,12 @@ extern "C" adac_status adac_scan_group_sum_product(adac_layout *a, const uint64_
                                                    const uint64_t *d_b_words, adac_layout *keys,
                                                    const uint64_t *d_key_words, const uint64_t *d_validity,
                                                    uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts) {
-	const GroupColumn cols[] = {{a, d_a_words}, {b, d_b_words}, {keys, d_key_words}};
+	const ColumnArg cols[] = {{a, d_a_words}, {b, d_b_words}, {keys, d_key_words}};
 	const void *const required[] = {d_sums};
 	adac_status st = group_scan_setup(cols, ngroups, required);
 	if (st != ADAC_OK) return st;
-	ADAC_HIP(adac::launch_group_product(a->ctx->stream, a->type_size, a->is_signed, b->type_size, b->is_signed,
-	                                    keys->type_size, a->d_descs, a->d_tiles, a->ntiles, a->d_groups, a->ngroups,
-	                                    d_a_words, b->d_descs, d_b_words, keys->d_descs, d_key_words, ngroups,
-	                                    a->d_group_partial, a->group_calls++, d_validity, d_sums, d_counts));
+	ADAC_HIP(adac::launch_group_product(a->ctx->stream, cols[0], cols[1], cols[2], scan_work(a),
+	                                    ngroups, next_group_call(a), d_validity, d_sums, d_counts));
 	return ADAC_OK;
 }
 
@@ -1296,15 +1321,13 @@ extern "C" adac_status adac_scan_group_sum_product3(adac_layout *a, const uint64
                                                     adac_layout *keys, const uint64_t *d_key_words,
                                                     const uint64_t *d_validity, uint32_t ngroups, uint64_t *d_sums,
                                                     uint64_t *d_counts) {
-	const GroupColumn cols[] = {{a, d_a_words}, {b, d_b_words}, {c, d_c_words}, {keys, d_key_words}};
+	const ColumnArg cols[] = {{a, d_a_words}, {b, d_b_words}, {c, d_c_words}, {keys, d_key_words}};
 	const void *const required[] = {d_sums};
 	adac_status st = group_scan_setup(cols, ngroups, required);
 	if (st != ADAC_OK) return st;
-	ADAC_HIP(adac::launch_group_product3(a->ctx->stream, a->type_size, a->is_signed, b->type_size, b->is_signed,
-	                                     c->type_size, c->is_signed, keys->type_size, a->d_descs, a->d_tiles, a->ntiles,
-	                                     a->d_groups, a->ngroups, d_a_words, b->d_descs, d_b_words, c->d_descs, d_c_words,
-	                                     keys->d_descs, d_key_words, ngroups, a->d_group_partial, a->group_calls++,
-	                                     d_validity, d_sums, d_counts));
+	ADAC_HIP(adac::launch_group_product3(a->ctx->stream, cols[0], cols[1], cols[2],
+	                                     cols[3], scan_work(a), ngroups, next_group_call(a), d_validity, d_sums,
+	                                     d_counts));
 	return ADAC_OK;
 }
 
@@ -1315,16 +1338,12 @@ extern "C" adac_status adac_scan_group_sum_q1(adac_layout *a, const uint64_t *d_
                                               adac_layout *q, const uint64_t *d_q_words, adac_layout *keys,
                                               const uint64_t *d_key_words, const uint64_t *d_validity, uint32_t ngroups,
                                               uint64_t *d_out) {
-	const GroupColumn cols[] = {{a, d_a_words}, {b, d_b_words}, {c, d_c_words}, {q, d_q_words}, {keys, d_key_words}};
+	const ColumnArg cols[] = {{a, d_a_words}, {b, d_b_words}, {c, d_c_words}, {q, d_q_words}, {keys, d_key_words}};
 	const void *const required[] = {d_out};
 	adac_status st = group_scan_setup(cols, ngroups, required);
 	if (st != ADAC_OK) return st;
-	const uint32_t type_size[5] = {a->type_size, b->type_size, c->type_size, q->type_size, keys->type_size};
-	const bool is_signed[5] = {a->is_signed, b->is_signed, c->is_signed, q->is_signed, keys->is_signed};
-	ADAC_HIP(adac::launch_group_q1(a->ctx->stream, type_size, is_signed, a->d_descs, a->d_tiles, a->ntiles, a->d_groups,
-	                               a->ngroups, d_a_words, b->d_descs, d_b_words, c->d_descs, d_c_words, q->d_descs,
-	                               d_q_words, keys->d_descs, d_key_words, ngroups, a->d_group_partial, a->group_calls++,
-	                               d_validity, d_out));
+	ADAC_HIP(adac::launch_group_q1(a->ctx->stream, LaunchColumns<5>(cols).c, scan_work(a), ngroups, next_group_call(a), d_validity,
+	                               d_out));
 	return ADAC_OK;
 }
 
@@ -1352,13 +1371,14 @@ extern "C" adac_status adac_scan_count_between(adac_layout *l, const uint64_t *d
 static adac_status scan_range(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity, uint64_t lo,
                               uint64_t hi, uint64_t *d_counts, uint64_t *d_bitmap, bool want_bitmap) {
 	if (!l || (l->nseg && !d_counts) || (l->total_values && !d_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	// (not SelectOutputs::ok: no `d_bitmap &&` here, so a null bitmap with a null mask is refused even without elements;
+	// the other select scans accept that call.  Known, and left as it is.)
 	if (want_bitmap && ((l->value_span && !d_bitmap) || d_bitmap == d_validity)) return ADAC_ERR_INVALID_ARGUMENT;
 	if (!aligned16(d_words)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	// order-preserving map of T onto unsigned numbers: flip the sign bit of the signed types
-	const uint64_t umask = adac::type_mask(l->type_size);
-	const uint64_t sbit = adac::type_sign_bit(l->type_size, l->is_signed);
-	const uint64_t blo = (lo & umask) ^ sbit, bhi = (hi & umask) ^ sbit;
+	const adac::TypeWords t = adac::type_words(*l);
+	const uint64_t blo = (lo & t.tmask) ^ t.sbit, bhi = (hi & t.tmask) ^ t.sbit;
 	// The scan writes every bitmap word that lies inside a group whole (zero words included).  With the segments back
 	// to back in the value space the words two groups share are all that is left: every group leaves its bits of
 	// them in a record, and a tiny kernel ORs the records of a word and stores it afterwards — no clearing pass
@@ -1393,7 +1413,7 @@ static adac_status scan_range(adac_layout *l, const uint64_t *d_words, const uin
 		ADAC_HIP(hipMalloc(&l->d_sel_edges, adac::sel_edge_bytes(l->ngroups)));
 		l->sel_edges_groups = l->ngroups;
 	}
-	ADAC_HIP(adac::launch_scan_count_range(l->ctx->stream, l->type_size, gl, d_words, d_validity, blo, bhi - blo, sbit,
+	ADAC_HIP(adac::launch_scan_count_range(l->ctx->stream, ColumnArg {l, d_words}, gl, d_validity, blo, bhi - blo,
 	                                       d_counts, want_bitmap ? d_bitmap : nullptr,
 	                                       edges_only && !edge_cells ? l->d_sel_edges : nullptr, edge_cells, tail_word));
 	if (edges_only && !edge_cells) {
@@ -1429,7 +1449,7 @@ extern "C" adac_status adac_unpack_selected(adac_layout *l, const uint64_t *d_wo
 	const adac::TileRec *recs = nullptr;
 	adac_status rst = tile_records(l, &recs);
 	if (rst != ADAC_OK) return rst;
-	ADAC_HIP(adac::launch_gather_selected(l->ctx->stream, l->type_size, l->d_descs, l->d_tiles, l->ntiles, d_words, recs,
+	ADAC_HIP(adac::launch_gather_selected(l->ctx->stream, ColumnArg {l, d_words}, l->d_tiles, l->ntiles, recs,
 	                                      d_bitmap, (l->value_span + 63) / 64, l->d_tile_cnt, l->d_tile_off, l->d_block_tot,
 	                                      d_out, d_out_ids, d_total));
 	if (total_out) return adac_memcpy_d2h(l->ctx, total_out, d_total, sizeof(uint64_t));
@@ -1558,6 +1578,10 @@ extern "C" adac_status adac_bp_bind(adac_bp_layout *l, const void *d_blocks) {
 static adac_status bp_ensure_bound(adac_bp_layout *l, const void *d_blocks) {
 	return l->bound_blocks == d_blocks ? ADAC_OK : adac_bp_bind(l, d_blocks);
 }
+// a layout and the blocks it is bound to as the launchers take them
+static adac::BpColumn bp_column(const adac_bp_layout *l, const void *d_blocks) {
+	return {l->d_groups, d_blocks, l->type_size, l->is_signed};
+}
 
 extern "C" adac_status adac_bp_unpack(adac_bp_layout *l, const void *d_blocks, void *d_out) {
 	if (!l || ((!d_blocks || !d_out) && l->total_values)) return ADAC_ERR_INVALID_ARGUMENT;
@@ -1565,7 +1589,7 @@ extern "C" adac_status adac_bp_unpack(adac_bp_layout *l, const void *d_blocks, v
 	adac_status st = bp_ensure_bound(l, d_blocks);
 	if (st != ADAC_OK) return st;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
-	ADAC_HIP(adac::launch_bp_unpack(l->ctx->stream, l->type_size, l->d_groups, l->ngroups, d_blocks, d_out));
+	ADAC_HIP(adac::launch_bp_unpack(l->ctx->stream, bp_column(l, d_blocks), l->ngroups, d_out));
 	return ADAC_OK;
 }
 
@@ -1579,8 +1603,8 @@ extern "C" adac_status adac_bp_unpack_range(adac_bp_layout *l, const void *d_blo
 	if (st != ADAC_OK) return st;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	const uint64_t g0 = l->seg_first_group[seg] + start / 2048;
-	ADAC_HIP(adac::launch_bp_unpack_range(l->ctx->stream, l->type_size, l->d_groups, (uint32_t)g0,
-	                                      (uint32_t)(start % 2048), count, out_off, d_blocks, d_out));
+	ADAC_HIP(adac::launch_bp_unpack_range(l->ctx->stream, bp_column(l, d_blocks), (uint32_t)g0, (uint32_t)(start % 2048),
+	                                      count, out_off, d_out));
 	return ADAC_OK;
 }
 
@@ -1612,8 +1636,8 @@ extern "C" adac_status adac_bp_unpack_selected(adac_bp_layout *l, const void *d_
 	if (!l->d_group_off) ADAC_HIP(hipMalloc((void **)&l->d_group_off, l->ngroups * sizeof(uint64_t)));
 	if (!l->d_block_tot) ADAC_HIP(hipMalloc((void **)&l->d_block_tot, (nblocks + 1) * sizeof(uint64_t)));
 	uint64_t *d_total = l->d_block_tot + nblocks; // the spare slot after the block totals
-	ADAC_HIP(adac::launch_bp_gather_selected(l->ctx->stream, l->type_size, l->d_groups, l->ngroups, d_blocks, d_bitmap,
-	                                         l->d_group_cnt, l->d_group_off, l->d_block_tot, d_out, d_out_ids, d_total));
+	ADAC_HIP(adac::launch_bp_gather_selected(l->ctx->stream, bp_column(l, d_blocks), l->ngroups, d_bitmap, l->d_group_cnt,
+	                                         l->d_group_off, l->d_block_tot, d_out, d_out_ids, d_total));
 	if (total_out) return adac_memcpy_d2h(l->ctx, total_out, d_total, sizeof(uint64_t));
 	return ADAC_OK;
 }
@@ -1635,8 +1659,8 @@ extern "C" adac_status adac_bp_scan_sum(adac_bp_layout *l, const void *d_blocks,
 	if ((st = bp_ensure_bound(l, d_blocks)) != ADAC_OK) return st;
 	// every wave adds its part: the sums start from zero (this also writes the segments without rows)
 	ADAC_HIP(hipMemsetAsync(d_sums, 0, l->nseg * sizeof(uint64_t), l->ctx->stream));
-	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, l->type_size, l->is_signed, adac::kBpScanOpSum, l->d_groups,
-	                              l->d_group_seg, l->ngroups, d_blocks, d_validity, 0, 0, d_sums, nullptr));
+	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, bp_column(l, d_blocks), adac::kBpScanOpSum, l->d_group_seg, l->ngroups,
+	                              d_validity, 0, 0, d_sums, nullptr));
 	return ADAC_OK;
 }
 
@@ -1644,23 +1668,18 @@ static adac_status bp_scan_range(adac_bp_layout *l, const void *d_blocks, const 
                                  uint64_t hi, uint64_t *d_counts, uint64_t *d_bitmap, bool want_bitmap) {
 	adac_status st = bp_scan_begin(l, d_blocks, d_counts);
 	if (st != ADAC_OK) return st;
-	if (want_bitmap && ((l->value_span && !d_bitmap) || (d_bitmap && d_bitmap == d_validity))) {
-		return ADAC_ERR_INVALID_ARGUMENT;
-	}
+	const SelectOutputs out {l->nseg, l->value_span, want_bitmap, d_bitmap, d_counts};
+	if (!out.ok(d_validity)) return ADAC_ERR_INVALID_ARGUMENT;
 	if (l->nseg == 0) return ADAC_OK;
 	// order-preserving map of T onto unsigned numbers: flip the sign bit of the signed types
-	const uint64_t umask = adac::type_mask(l->type_size);
-	const uint64_t sbit = adac::type_sign_bit(l->type_size, l->is_signed);
-	const uint64_t blo = (lo & umask) ^ sbit, bhi = (hi & umask) ^ sbit;
-	if (want_bitmap && l->value_span) {
-		ADAC_HIP(hipMemsetAsync(d_bitmap, 0, ((l->value_span + 63) / 64) * sizeof(uint64_t), l->ctx->stream));
-	}
-	ADAC_HIP(hipMemsetAsync(d_counts, 0, l->nseg * sizeof(uint64_t), l->ctx->stream));
+	const adac::TypeWords t = adac::type_words(*l);
+	const uint64_t blo = (lo & t.tmask) ^ t.sbit, bhi = (hi & t.tmask) ^ t.sbit;
+	if ((st = out.clear_bitmap(l->ctx->stream)) != ADAC_OK) return st;
+	if ((st = out.clear_counts(l->ctx->stream)) != ADAC_OK) return st;
 	if (bhi < blo) return ADAC_OK; // empty range: all counts (and bits) are zero
 	if ((st = bp_ensure_bound(l, d_blocks)) != ADAC_OK) return st;
-	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, l->type_size, l->is_signed, adac::kBpScanOpRange, l->d_groups,
-	                              l->d_group_seg, l->ngroups, d_blocks, d_validity, blo, bhi - blo, d_counts,
-	                              want_bitmap ? d_bitmap : nullptr));
+	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, bp_column(l, d_blocks), adac::kBpScanOpRange, l->d_group_seg, l->ngroups,
+	                              d_validity, blo, bhi - blo, d_counts, out.bitmap()));
 	return ADAC_OK;
 }
 
@@ -1682,8 +1701,8 @@ extern "C" adac_status adac_bp_scan_min_max(adac_bp_layout *l, const void *d_blo
 	// the scan works in the ordered domain bits ^ signbit from the empty interval [all-ones, 0]; a kernel over the
 	// segments maps the cells back to T's bits
 	ADAC_HIP(adac::launch_minmax_init(l->ctx->stream, d_minmax, l->nseg));
-	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, l->type_size, l->is_signed, adac::kBpScanOpMinMax, l->d_groups,
-	                              l->d_group_seg, l->ngroups, d_blocks, d_validity, 0, 0, d_minmax, nullptr));
+	ADAC_HIP(adac::launch_bp_scan(l->ctx->stream, bp_column(l, d_blocks), adac::kBpScanOpMinMax, l->d_group_seg,
+	                              l->ngroups, d_validity, 0, 0, d_minmax, nullptr));
 	ADAC_HIP(adac::launch_bp_scan_minmax_finish(l->ctx->stream, l->type_size, l->is_signed, d_minmax, l->nseg));
 	return ADAC_OK;
 }
@@ -1722,9 +1741,8 @@ extern "C" adac_status adac_bp_scan_sum_product(adac_bp_layout *a, const void *d
 	if ((st = bp_pair_bind(a, d_a_blocks, b, d_b_blocks)) != ADAC_OK) return st;
 	// every wave adds its part: the sums start from zero (this also writes the segments without rows)
 	ADAC_HIP(hipMemsetAsync(d_sums, 0, a->nseg * sizeof(uint64_t), a->ctx->stream));
-	const adac::BpPairColumn ca {a->d_groups, d_a_blocks, a->type_size, a->is_signed};
-	const adac::BpPairColumn cb {b->d_groups, d_b_blocks, b->type_size, b->is_signed};
-	ADAC_HIP(adac::launch_bp_scan_pair_sum(a->ctx->stream, ca, cb, a->d_group_seg, a->ngroups, d_validity, d_sums));
+	ADAC_HIP(adac::launch_bp_scan_pair_sum(a->ctx->stream, bp_column(a, d_a_blocks), bp_column(b, d_b_blocks),
+	                                       a->d_group_seg, a->ngroups, d_validity, d_sums));
 	return ADAC_OK;
 }
 
@@ -1738,9 +1756,8 @@ extern "C" adac_status adac_bp_scan_group_sum(adac_bp_layout *values, const void
 	if ((st = bp_pair_bind(values, d_value_blocks, keys, d_key_blocks)) != ADAC_OK) return st;
 	ADAC_HIP(hipMemsetAsync(d_sums, 0, (ngroups + 1ull) * sizeof(uint64_t), values->ctx->stream));
 	if (d_counts) ADAC_HIP(hipMemsetAsync(d_counts, 0, (ngroups + 1ull) * sizeof(uint64_t), values->ctx->stream));
-	const adac::BpPairColumn cv {values->d_groups, d_value_blocks, values->type_size, values->is_signed};
-	const adac::BpPairColumn ck {keys->d_groups, d_key_blocks, keys->type_size, keys->is_signed};
-	ADAC_HIP(adac::launch_bp_scan_pair_gsum(values->ctx->stream, cv, ck, values->ngroups, d_validity, ngroups, d_sums,
+	ADAC_HIP(adac::launch_bp_scan_pair_gsum(values->ctx->stream, bp_column(values, d_value_blocks),
+	                                        bp_column(keys, d_key_blocks), values->ngroups, d_validity, ngroups, d_sums,
 	                                        d_counts));
 	return ADAC_OK;
 }
@@ -1751,23 +1768,15 @@ static adac_status bp_pair_compare(adac_bp_layout *a, const void *d_a_blocks, ad
 	adac_status st = bp_pair_begin(a, d_a_blocks, b, d_b_blocks);
 	if (st != ADAC_OK) return st;
 	if (cmp == 0 || cmp > 6) return ADAC_ERR_INVALID_ARGUMENT;
-	if (a->nseg && !d_counts) return ADAC_ERR_INVALID_ARGUMENT;
-	if (want_bitmap && ((a->value_span && !d_bitmap) || (d_bitmap && d_bitmap == d_validity))) {
-		return ADAC_ERR_INVALID_ARGUMENT;
-	}
+	const SelectOutputs out {a->nseg, a->value_span, want_bitmap, d_bitmap, d_counts};
+	if (!out.ok(d_validity)) return ADAC_ERR_INVALID_ARGUMENT;
 	if (a->nseg == 0) return ADAC_OK;
 	ADAC_HIP(hipSetDevice(a->ctx->device));
 	if ((st = bp_pair_bind(a, d_a_blocks, b, d_b_blocks)) != ADAC_OK) return st;
-	// every wave adds its part and ORs the words it shares: both start from zero (this also writes the segments
-	// without rows and the bits no segment covers)
-	if (want_bitmap && a->value_span) {
-		ADAC_HIP(hipMemsetAsync(d_bitmap, 0, ((a->value_span + 63) / 64) * sizeof(uint64_t), a->ctx->stream));
-	}
-	ADAC_HIP(hipMemsetAsync(d_counts, 0, a->nseg * sizeof(uint64_t), a->ctx->stream));
-	const adac::BpPairColumn ca {a->d_groups, d_a_blocks, a->type_size, a->is_signed};
-	const adac::BpPairColumn cb {b->d_groups, d_b_blocks, b->type_size, b->is_signed};
-	ADAC_HIP(adac::launch_bp_scan_pair_cmp(a->ctx->stream, ca, cb, a->d_group_seg, a->ngroups, d_validity, cmp, d_counts,
-	                                       want_bitmap ? d_bitmap : nullptr));
+	if ((st = out.clear_bitmap(a->ctx->stream)) != ADAC_OK) return st;
+	if ((st = out.clear_counts(a->ctx->stream)) != ADAC_OK) return st;
+	ADAC_HIP(adac::launch_bp_scan_pair_cmp(a->ctx->stream, bp_column(a, d_a_blocks), bp_column(b, d_b_blocks),
+	                                       a->d_group_seg, a->ngroups, d_validity, cmp, d_counts, out.bitmap()));
 	return ADAC_OK;
 }
 

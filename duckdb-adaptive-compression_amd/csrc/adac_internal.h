@@ -128,6 +128,37 @@ inline uint64_t type_sign_bit(uint32_t type_size, bool is_signed) {
 	return is_signed ? 1ull << (8 * type_size - 1) : 0ull;
 }
 
+// What the launchers take instead of loose parameters.
+// A packed column: its type, its segment descriptors and its packed words (BpColumn is the BITPACKING counterpart).
+struct Column {
+	uint32_t type_size;
+	bool is_signed;
+	const adac_segment_desc *d_descs;
+	const uint64_t *d_words;
+};
+// The work items of the layout a scan walks, the call's first column: its tiles (the staged kernels') and its scan
+// groups (the register-walk kernels' and the per-segment scans', which look at nothing else here).
+struct ScanWork {
+	const TileRef *d_tiles;
+	uint64_t ntiles;
+	const ScanGroup *d_scan_groups;
+	uint64_t nscan_groups;
+};
+// The state the grouped scans of one layout share: the partial buffer (group_sum_partial_bytes(), cleared when it is
+// allocated) and the number of the call, whose low bit picks the hand-over word.
+struct GroupScanState {
+	void *d_partial;
+	uint32_t call_parity;
+};
+// The type words every scan kernel takes per column: all-ones mask of the type's width and its sign bit.
+struct TypeWords {
+	uint64_t tmask, sbit;
+};
+template <class C> // Column, BpColumn or a layout: anything with type_size and is_signed
+inline TypeWords type_words(const C &col) {
+	return {type_mask(col.type_size), type_sign_bit(col.type_size, col.is_signed)};
+}
+
 // type_size in {1,2,4,8}; every launcher returns the hipError_t of the launch.
 hipError_t launch_analyze(hipStream_t s, uint32_t type_size, bool sign_extend, uint64_t null_bits, int rule,
                           const adac_segment_desc *d_descs, const TileRef *d_tiles, uint64_t ntiles,
@@ -138,75 +169,55 @@ hipError_t launch_plan(hipStream_t s, uint32_t type_size, int rule, int pad_to_b
 hipError_t launch_pack(hipStream_t s, uint32_t type_size, uint64_t null_bits, const adac_segment_desc *d_descs,
                        const TileRef *d_tiles, uint64_t ntiles, const void *d_vals, const uint64_t *d_validity,
                        uint64_t *d_words);
-hipError_t launch_unpack(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs, const TileRef *d_tiles,
-                         uint64_t ntiles, const uint64_t *d_words, void *d_out, const TileRec *d_recs);
-hipError_t launch_unpack_range(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs, RangeArgs range,
-                               const uint64_t *d_words, void *d_out);
-hipError_t launch_fetch(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs, const uint64_t *d_words,
-                        const uint32_t *d_segs, const uint32_t *d_rows, uint64_t n, void *d_out);
+// decode of a packed column to d_out: every tile (d_recs: the expanded tile records, or null), one range of one segment,
+// and the n rows (d_segs[i], d_rows[i])
+hipError_t launch_unpack(hipStream_t s, const Column &col, const TileRef *d_tiles, uint64_t ntiles, void *d_out,
+                         const TileRec *d_recs);
+hipError_t launch_unpack_range(hipStream_t s, const Column &col, RangeArgs range, void *d_out);
+hipError_t launch_fetch(hipStream_t s, const Column &col, const uint32_t *d_segs, const uint32_t *d_rows, uint64_t n,
+                        void *d_out);
 // single-pass encode (adac_encode_1p.inl): every segment must fit sixteen 16-byte chunks per thread of a 1024-thread
 // workgroup, counted from the 16-byte boundary at or before its first element
 constexpr uint64_t kEncodeOnePassBytes = 16ull * 1024 * 16;
 // 64-bit words of device scratch the single-pass encode needs for nseg segments (look-back words, ticket, cursor)
 inline uint64_t encode_1p_state_words(uint64_t nseg) { return nseg + 2; }
 hipError_t read_encode_stamps(void *host, uint64_t bytes);
-// grouped SUM / COUNT over two packed columns of one table (adac_group_sum.inl)
+// Grouped scans (adac_group_*.inl): all columns belong to one table, `work` and `state` to the first one's layout, keys
+// >= ngroups land in bin ngroups, d_validity (may be null) selects rows in the first column's element space.
 uint64_t group_sum_partial_bytes();
 uint32_t group_sum_max_groups();
 uint64_t group_sum_handover_word(uint32_t call_parity); // index (in 64-bit words of the partial buffer) of a call's hand-over word
-hipError_t launch_group_sum(hipStream_t s, uint32_t v_type_size, bool v_signed, uint32_t k_type_size,
-                            const adac_segment_desc *d_vdescs, const TileRef *d_vtiles, uint64_t ntiles,
-                            const ScanGroup *d_vgroups, uint64_t nvgroups, const uint64_t *d_vwords,
-                            const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups, void *d_partial,
-                            uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums, uint64_t *d_counts);
-// SUM(a * b) GROUP BY key over three packed columns of one table under a selection bitmap (adac_group_product.inl);
-// d_partial / call_parity: launch_group_sum's, d_counts may be null
-hipError_t launch_group_product(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
-                                uint32_t k_type_size, const adac_segment_desc *d_adescs, const TileRef *d_atiles,
-                                uint64_t ntiles, const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
-                                const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
-                                const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups,
-                                void *d_partial, uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums,
+// SUM(v), COUNT(*) GROUP BY k into d_sums / d_counts, ngroups + 1 words each
+hipError_t launch_group_sum(hipStream_t s, const Column &v, const Column &k, const ScanWork &work, uint32_t ngroups,
+                            const GroupScanState &state, const uint64_t *d_validity, uint64_t *d_sums, uint64_t *d_counts);
+// SUM(a * b) GROUP BY k; d_counts may be null
+hipError_t launch_group_product(hipStream_t s, const Column &a, const Column &b, const Column &k, const ScanWork &work,
+                                uint32_t ngroups, const GroupScanState &state, const uint64_t *d_validity, uint64_t *d_sums,
                                 uint64_t *d_counts);
-// SUM(a * b * c) GROUP BY key over four packed columns of one table under a selection bitmap
-// (adac_group_product3.inl); d_partial / call_parity: launch_group_sum's, d_counts may be null
-hipError_t launch_group_product3(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
-                                 uint32_t c_type_size, bool c_signed, uint32_t k_type_size,
-                                 const adac_segment_desc *d_adescs, const TileRef *d_atiles, uint64_t ntiles,
-                                 const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
-                                 const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
-                                 const adac_segment_desc *d_cdescs, const uint64_t *d_cwords,
-                                 const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups,
-                                 void *d_partial, uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums,
-                                 uint64_t *d_counts);
-// COUNT and the six sums of Q1 GROUP BY key over five packed columns of one table under a selection bitmap, one scan
-// (adac_group_q1.inl); type_size / is_signed: a, b, c, q, keys; d_partial / call_parity: launch_group_sum's;
-// d_out: 7 x (ngroups + 1) words, term t of group g at [t * (ngroups + 1) + g]
-hipError_t launch_group_q1(hipStream_t s, const uint32_t (&type_size)[5], const bool (&is_signed)[5],
-                           const adac_segment_desc *d_adescs, const TileRef *d_atiles, uint64_t ntiles,
-                           const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
-                           const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
-                           const adac_segment_desc *d_cdescs, const uint64_t *d_cwords,
-                           const adac_segment_desc *d_qdescs, const uint64_t *d_qwords,
-                           const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups, void *d_partial,
-                           uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_out);
-// SUM(a * b) over two packed columns of one table under a selection bitmap (adac_sum_product.inl)
-hipError_t launch_scan_sum_product(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
-                                   const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,
-                                   const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
+// SUM(a * b * c) GROUP BY k; d_counts may be null
+hipError_t launch_group_product3(hipStream_t s, const Column &a, const Column &b, const Column &c, const Column &k,
+                                 const ScanWork &work, uint32_t ngroups, const GroupScanState &state,
+                                 const uint64_t *d_validity, uint64_t *d_sums, uint64_t *d_counts);
+// COUNT and the six sums of Q1 GROUP BY key in one scan; cols: a, b, c, q, keys; d_out: 7 x (ngroups + 1) words, term t of
+// group g at [t * (ngroups + 1) + g]
+hipError_t launch_group_q1(hipStream_t s, const Column (&cols)[5], const ScanWork &work, uint32_t ngroups,
+                           const GroupScanState &state, const uint64_t *d_validity, uint64_t *d_out);
+// Per-segment scans over the scan groups of the first column's layout (`work`); d_validity as above; the caller has
+// cleared every output.
+// SUM(a * b) into d_sums (adac_sum_product.inl)
+hipError_t launch_scan_sum_product(hipStream_t s, const Column &a, const Column &b, const ScanWork &work,
                                    const uint64_t *d_validity, uint64_t *d_sums);
-// rows where value(a) <cmp> value(b) per segment, and their bitmap unless d_bitmap is null (adac_scan_compare.inl)
-hipError_t launch_scan_compare(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
-                               const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,
-                               const adac_segment_desc *d_bdescs, const uint64_t *d_bwords, const uint64_t *d_validity,
-                               uint32_t cmp, uint64_t *d_bitmap, uint64_t *d_counts);
-// rows whose value is a member of the bit set d_set over [set_base, set_base + set_bits - 1] per segment, and their bitmap
-// unless d_bitmap is null; the set built from the wanted rows of a column (adac_scan_member.inl)
-hipError_t launch_scan_member(hipStream_t s, uint32_t type_size, bool is_signed, const ScanGroup *d_groups,
-                              uint64_t ngroups, const uint64_t *d_words, const uint64_t *d_validity, const uint64_t *d_set,
-                              uint64_t set_base, uint64_t set_bits, uint64_t *d_bitmap, uint64_t *d_counts);
-hipError_t launch_scan_member_build(hipStream_t s, uint32_t type_size, bool is_signed, const ScanGroup *d_groups,
-                                    uint64_t ngroups, const uint64_t *d_words, const uint64_t *d_validity,
+// rows where value(a) <cmp> value(b), cmp an OR of ADAC_CMP_*: d_counts and, unless null, their d_bitmap in a's element
+// space (adac_scan_compare.inl)
+hipError_t launch_scan_compare(hipStream_t s, const Column &a, const Column &b, const ScanWork &work,
+                               const uint64_t *d_validity, uint32_t cmp, uint64_t *d_bitmap, uint64_t *d_counts);
+// rows whose value is a member of the bit set d_set over [set_base, set_base + set_bits - 1], which the caller has checked
+// against the type: d_counts and, unless null, their d_bitmap; and the set built from the wanted rows of a column, with
+// the rows inside the domain in d_counts (adac_scan_member.inl)
+hipError_t launch_scan_member(hipStream_t s, const Column &col, const ScanWork &work, const uint64_t *d_validity,
+                              const uint64_t *d_set, uint64_t set_base, uint64_t set_bits, uint64_t *d_bitmap,
+                              uint64_t *d_counts);
+hipError_t launch_scan_member_build(hipStream_t s, const Column &col, const ScanWork &work, const uint64_t *d_validity,
                                     uint64_t set_base, uint64_t set_bits, uint64_t *d_set, uint64_t *d_counts);
 hipError_t launch_encode_1p(hipStream_t s, uint32_t type_size, bool sign_extend, uint64_t null_bits, int rule,
                             int pad_to_byte, adac_segment_desc *d_descs, uint64_t nseg, const void *d_vals,
@@ -234,20 +245,25 @@ hipError_t launch_expand_tiles(hipStream_t s, uint32_t type_size, const adac_seg
                                uint64_t ntiles, TileRec *d_recs);
 hipError_t launch_expand_groups(hipStream_t s, const adac_segment_desc *d_descs, const ScanGroupRef *d_refs,
                                 uint64_t ngroups, ScanGroup *d_groups, uint32_t *d_narrow_idx, uint32_t *d_narrow_count);
-hipError_t launch_gather_selected(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs,
-                                  const TileRef *d_tiles, uint64_t ntiles, const uint64_t *d_words,
-                                  const TileRec *d_recs, const uint64_t *d_bitmap, uint64_t bitmap_words, uint32_t *d_tile_cnt,
-                                  uint64_t *d_tile_off, uint64_t *d_block_tot, void *d_out, uint64_t *d_out_ids,
-                                  uint64_t *d_total);
-hipError_t launch_scan_sum(hipStream_t s, uint32_t type_size, const ScanGroupList &gl, const uint64_t *d_words,
-                           const uint64_t *d_validity, uint64_t sbit, uint64_t *d_sums);
+// scan with selection: the rows of the column whose bit is set in d_bitmap to d_out, their element indices to
+// d_out_ids unless null, *d_total = rows written.  d_tile_cnt / d_tile_off: ntiles entries of scratch, d_block_tot:
+// ceil(ntiles / 1024) words
+hipError_t launch_gather_selected(hipStream_t s, const Column &col, const TileRef *d_tiles, uint64_t ntiles,
+                                  const TileRec *d_recs, const uint64_t *d_bitmap, uint64_t bitmap_words,
+                                  uint32_t *d_tile_cnt, uint64_t *d_tile_off, uint64_t *d_block_tot, void *d_out,
+                                  uint64_t *d_out_ids, uint64_t *d_total);
+// The fused scans of one column over its layout's groups `gl` (k_scan_agg; col.d_descs plays no part, the groups carry
+// the descriptors).  SUM per segment into d_sums
+hipError_t launch_scan_sum(hipStream_t s, const Column &col, const ScanGroupList &gl, const uint64_t *d_validity,
+                           uint64_t *d_sums);
 uint64_t sel_edge_bytes(uint64_t ngroups);
 hipError_t launch_sel_merge_edges(hipStream_t s, const void *d_edges, uint64_t ngroups, uint64_t *d_bitmap,
                                   uint64_t tail_word);
-hipError_t launch_scan_count_range(hipStream_t s, uint32_t type_size, const ScanGroupList &gl, const uint64_t *d_words,
-                                   const uint64_t *d_validity, uint64_t blo, uint64_t bspan, uint64_t sbit,
-                                   uint64_t *d_counts, uint64_t *d_bitmap, void *d_edges, bool edge_cells,
-                                   uint64_t tail_word);
+// rows with blo <= bits ^ sign bit <= blo + bspan per segment into d_counts and, unless null, their d_bitmap; the words
+// of the bitmap that groups share go to d_edges (launch_sel_merge_edges stores them) or through the edge cells
+hipError_t launch_scan_count_range(hipStream_t s, const Column &col, const ScanGroupList &gl, const uint64_t *d_validity,
+                                   uint64_t blo, uint64_t bspan, uint64_t *d_counts, uint64_t *d_bitmap, void *d_edges,
+                                   bool edge_cells, uint64_t tail_word);
 
 // Persistent block images (adac_block_image.inl): one segment's packed words <-> its image in a block buffer.
 struct BlockJob {
@@ -289,43 +305,43 @@ hipError_t launch_bp_stats(hipStream_t s, uint32_t type_size, bool is_signed, co
 hipError_t launch_bp_write(hipStream_t s, uint32_t type_size, const void *d_recs, uint64_t ngroups, const void *d_vals,
                            const uint64_t *d_validity, uint64_t block_stride, void *d_blocks);
 hipError_t launch_bp_prepare(hipStream_t s, uint32_t type_size, void *d_groups, uint64_t ngroups, const void *d_blocks);
-hipError_t launch_bp_unpack(hipStream_t s, uint32_t type_size, const void *d_groups, uint64_t ngroups,
-                            const void *d_blocks, void *d_out);
-hipError_t launch_bp_unpack_range(hipStream_t s, uint32_t type_size, const void *d_groups, uint32_t group0,
-                                  uint32_t skip_first, uint64_t count, uint64_t out_off, const void *d_blocks,
-                                  void *d_out);
-hipError_t launch_bp_fetch(hipStream_t s, uint32_t type_size, const uint64_t *d_block_offs, const void *d_blocks,
-                           const uint32_t *d_segs, const uint32_t *d_rows, uint64_t n, void *d_out);
-// fused scans on the block images (adac_bp_scans.inl); op values match kBpScanSum / Range / MinMax there.  d_res:
-// sums | counts | min, max pairs; the caller has filled it (and the bitmap) — see the kernel's header
-enum : int { kBpScanOpSum = 0, kBpScanOpRange = 1, kBpScanOpMinMax = 2 };
-hipError_t launch_bp_scan(hipStream_t s, uint32_t type_size, bool is_signed, int op, const void *d_groups,
-                          const uint32_t *d_group_seg, uint64_t ngroups, const void *d_blocks,
-                          const uint64_t *d_validity, uint64_t blo, uint64_t bspan, uint64_t *d_res, uint64_t *d_bitmap);
-hipError_t launch_bp_scan_minmax_finish(hipStream_t s, uint32_t type_size, bool is_signed, uint64_t *d_minmax,
-                                        uint64_t nseg);
-// pair scans on the block images of two layouts whose group tables agree (adac_bp_pair_scans.inl).  The caller has
-// zeroed the results.  a's group_seg: SUM(a * b) is per segment of a
-struct BpPairColumn {
+// A BITPACKING column: its type, its parsed group table (launch_bp_prepare's) and the blocks buffer it is bound to.
+struct BpColumn {
 	const void *d_groups, *d_blocks;
 	uint32_t type_size;
 	bool is_signed;
 };
-hipError_t launch_bp_scan_pair_sum(hipStream_t s, const BpPairColumn &a, const BpPairColumn &b,
-                                   const uint32_t *d_group_seg, uint64_t ngroups, const uint64_t *d_validity,
-                                   uint64_t *d_sums);
-hipError_t launch_bp_scan_pair_gsum(hipStream_t s, const BpPairColumn &v, const BpPairColumn &k, uint64_t ngroups,
+// decode: every group, or `count` rows from row skip_first of group group0 to d_out + out_off
+hipError_t launch_bp_unpack(hipStream_t s, const BpColumn &col, uint64_t ngroups, void *d_out);
+hipError_t launch_bp_unpack_range(hipStream_t s, const BpColumn &col, uint32_t group0, uint32_t skip_first, uint64_t count,
+                                  uint64_t out_off, void *d_out);
+hipError_t launch_bp_fetch(hipStream_t s, uint32_t type_size, const uint64_t *d_block_offs, const void *d_blocks,
+                           const uint32_t *d_segs, const uint32_t *d_rows, uint64_t n, void *d_out);
+// fused scans on the block images (adac_bp_scans.inl); op values match kBpScanSum / Range / MinMax there.  d_res:
+// sums | counts | min, max pairs per segment (d_group_seg: the segment of every group); the caller has filled it (and
+// the bitmap) - see the kernel's header
+enum : int { kBpScanOpSum = 0, kBpScanOpRange = 1, kBpScanOpMinMax = 2 };
+hipError_t launch_bp_scan(hipStream_t s, const BpColumn &col, int op, const uint32_t *d_group_seg, uint64_t ngroups,
+                          const uint64_t *d_validity, uint64_t blo, uint64_t bspan, uint64_t *d_res, uint64_t *d_bitmap);
+hipError_t launch_bp_scan_minmax_finish(hipStream_t s, uint32_t type_size, bool is_signed, uint64_t *d_minmax,
+                                        uint64_t nseg);
+// pair scans on the block images of two layouts whose group tables agree (adac_bp_pair_scans.inl).  The caller has
+// zeroed the results.  SUM(a * b) per segment of a (d_group_seg: a's)
+hipError_t launch_bp_scan_pair_sum(hipStream_t s, const BpColumn &a, const BpColumn &b, const uint32_t *d_group_seg,
+                                   uint64_t ngroups, const uint64_t *d_validity, uint64_t *d_sums);
+// SUM(v), COUNT(*) GROUP BY k, keys >= nkeys in bin nkeys; d_counts may be null
+hipError_t launch_bp_scan_pair_gsum(hipStream_t s, const BpColumn &v, const BpColumn &k, uint64_t ngroups,
                                     const uint64_t *d_validity, uint32_t nkeys, uint64_t *d_sums, uint64_t *d_counts);
 // rows where value(a) <cmp> value(b), cmp an OR of ADAC_CMP_*: d_counts per segment of a and, unless nullptr, d_bitmap
-// in a's element space; the caller has zeroed both
-hipError_t launch_bp_scan_pair_cmp(hipStream_t s, const BpPairColumn &a, const BpPairColumn &b,
-                                   const uint32_t *d_group_seg, uint64_t ngroups, const uint64_t *d_validity,
-                                   uint32_t cmp, uint64_t *d_counts, uint64_t *d_bitmap);
-// scan with selection on the block images (adac_bp_select_gather.inl).  d_group_cnt / d_group_off: ngroups entries of
-// scratch, d_block_tot: ceil(ngroups / 1024) words; *d_total = rows written
-hipError_t launch_bp_gather_selected(hipStream_t s, uint32_t type_size, const void *d_groups, uint64_t ngroups,
-                                     const void *d_blocks, const uint64_t *d_bitmap, uint32_t *d_group_cnt,
-                                     uint64_t *d_group_off, uint64_t *d_block_tot, void *d_out, uint64_t *d_out_ids,
-                                     uint64_t *d_total);
+// in a's element space
+hipError_t launch_bp_scan_pair_cmp(hipStream_t s, const BpColumn &a, const BpColumn &b, const uint32_t *d_group_seg,
+                                   uint64_t ngroups, const uint64_t *d_validity, uint32_t cmp, uint64_t *d_counts,
+                                   uint64_t *d_bitmap);
+// scan with selection on the block images (adac_bp_select_gather.inl): the rows whose bit is set in d_bitmap to d_out,
+// their element indices to d_out_ids unless null, *d_total = rows written.  d_group_cnt / d_group_off: ngroups entries
+// of scratch, d_block_tot: ceil(ngroups / 1024) words
+hipError_t launch_bp_gather_selected(hipStream_t s, const BpColumn &col, uint64_t ngroups, const uint64_t *d_bitmap,
+                                     uint32_t *d_group_cnt, uint64_t *d_group_off, uint64_t *d_block_tot, void *d_out,
+                                     uint64_t *d_out_ids, uint64_t *d_total);
 
 } // namespace adac

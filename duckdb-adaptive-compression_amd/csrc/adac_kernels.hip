@@ -1945,6 +1945,24 @@ hipError_t dispatch_size(uint32_t type_size, F &&f) {
 	}
 }
 
+// Runtime bools -> template arguments: dispatch_flags(f, x, y) calls f(std::bool_constant<x> {}, std::bool_constant<y> {}),
+// so a launcher names its kernel once, as k<V.value, C.value>, and only the combinations it spells are instantiated.
+template <class F>
+void dispatch_flags(F &&f) {
+	f();
+}
+template <class F, class... Rest>
+void dispatch_flags(F &&f, bool flag, Rest... rest) {
+	auto bind = [&](auto c) { dispatch_flags([&](auto... cs) { f(c, cs...); }, rest...); };
+	if (flag) bind(std::true_type {}); else bind(std::false_type {});
+}
+// ... and a runtime int out of a short list: dispatch_int<A, B>(v, f) calls f(std::integral_constant<int, v> {}) when v
+// is A or B; false when it is neither
+template <int... Vs, class F>
+bool dispatch_int(int v, F &&f) {
+	return ((v == Vs && (f(std::integral_constant<int, Vs> {}), true)) || ...);
+}
+
 #include "adac_bitpacking.inl"
 #include "adac_bp_walk.inl"
 #include "adac_bp_scans.inl"
@@ -2054,7 +2072,7 @@ uint64_t group_sum_handover_word(uint32_t call_parity) { return (uint64_t)kGroup
 
 namespace {
 
-// The steps every grouped scan takes on the `a` layout's partial buffer and hand-over slots (d_partial, call_parity:
+// The steps every grouped scan takes on the `a` layout's work items and on its partial buffer and hand-over slots (`state`:
 // shared between the grouped entry points, each call uses slot (calls & 1) and clears the other one for the call after it):
 //   1. the register-walk kernel over a's scan groups, when there are at most kGroupPrivateBins bins, its knob is on and
 //      there is a scan group; persistent, rw_resident workgroups per CU; it counts the scan groups it cannot take in
@@ -2066,26 +2084,26 @@ namespace {
 // `cap`: the most workgroups either kernel may have (its half of the partial buffer).  The launch_* callables launch
 // the call's own kernels with the grids and pointers computed here.
 template <class Rw, class Staged, class Final>
-hipError_t launch_group_scan(uint32_t nbins, bool rw_knob, uint64_t nagroups, uint64_t ntiles, uint32_t rw_resident,
-                             uint32_t staged_resident, uint64_t cap, uint32_t row_words, void *d_partial,
-                             uint32_t call_parity, Rw launch_rw, Staged launch_staged, Final launch_final) {
-	unsigned long long *partial = static_cast<unsigned long long *>(d_partial);
-	unsigned long long *fallback = partial + group_sum_handover_word(call_parity);
-	unsigned long long *next_fallback = partial + group_sum_handover_word(call_parity + 1u);
+hipError_t launch_group_scan(uint32_t nbins, bool rw_knob, const ScanWork &work, uint32_t rw_resident,
+                             uint32_t staged_resident, uint64_t cap, uint32_t row_words, const GroupScanState &state,
+                             Rw launch_rw, Staged launch_staged, Final launch_final) {
+	unsigned long long *partial = static_cast<unsigned long long *>(state.d_partial);
+	unsigned long long *fallback = partial + group_sum_handover_word(state.call_parity);
+	unsigned long long *next_fallback = partial + group_sum_handover_word(state.call_parity + 1u);
 	auto grid = [&](uint64_t items, uint32_t resident) {
 		uint64_t most = (uint64_t)resident * device_cus();
 		most = most < cap ? most : cap;
 		return (uint32_t)(items < most ? items : most);
 	};
 	uint32_t nwg_rw = 0;
-	const bool rw = nbins <= kGroupPrivateBins && rw_knob && nagroups > 0;
+	const bool rw = nbins <= kGroupPrivateBins && rw_knob && work.nscan_groups > 0;
 	if (rw) {
-		nwg_rw = grid(nagroups, rw_resident);
+		nwg_rw = grid(work.nscan_groups, rw_resident);
 		launch_rw(nwg_rw, partial, fallback);
 		hipError_t e = hipGetLastError();
 		if (e != hipSuccess) return e;
 	}
-	const uint32_t nwg = grid(ntiles, staged_resident);
+	const uint32_t nwg = grid(work.ntiles, staged_resident);
 	if (nwg) {
 		launch_staged(nwg, partial + (uint64_t)nwg_rw * row_words, rw ? fallback : static_cast<const unsigned long long *>(nullptr));
 		hipError_t e = hipGetLastError();
@@ -2095,17 +2113,14 @@ hipError_t launch_group_scan(uint32_t nbins, bool rw_knob, uint64_t nagroups, ui
 	return hipGetLastError();
 }
 
-// the type words the grouped kernels take: all-ones mask of the type's width and its sign bit per column
-GroupProductTypes group_product_types(uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
-                                      uint32_t k_type_size) {
-	GroupProductTypes ty;
-	ty.p.a_tmask = type_mask(a_type_size);
-	ty.p.a_sbit = type_sign_bit(a_type_size, a_signed);
-	ty.p.b_tmask = type_mask(b_type_size);
-	ty.p.b_sbit = type_sign_bit(b_type_size, b_signed);
-	ty.k_tmask = type_mask(k_type_size);
-	ty.a_tile_rows = tile_values(a_type_size);
-	return ty;
+// the type words the kernels take, per column
+ProductTypes product_types(const TypeWords &a, const TypeWords &b) { return {a.tmask, a.sbit, b.tmask, b.sbit}; }
+GroupProductTypes group_product_types(const Column &a, const Column &b, const Column &k) {
+	return {product_types(type_words(a), type_words(b)), type_words(k).tmask, tile_values(a.type_size)};
+}
+GroupProduct3Types group_product3_types(const Column &a, const Column &b, const Column &c, const Column &k) {
+	const TypeWords tc = type_words(c);
+	return {group_product_types(a, b, k), tc.tmask, tc.sbit};
 }
 
 // step 3 of the scans that end in {sum, count} pairs per bin: k_group_final (d_counts may be null)
@@ -2119,150 +2134,113 @@ auto group_pairs_final(hipStream_t s, uint32_t nbins, uint64_t *d_sums, uint64_t
 
 } // namespace
 
-// SUM(value), COUNT(*) GROUP BY key, optionally under a selection bitmap (adac_group_sum.inl).  The register walk is
-// resident with seven workgroups per CU, six under a mask; the staged kernel with seven (21 KiB of LDS each).
-hipError_t launch_group_sum(hipStream_t s, uint32_t v_type_size, bool v_signed, uint32_t k_type_size,
-                            const adac_segment_desc *d_vdescs, const TileRef *d_vtiles, uint64_t ntiles,
-                            const ScanGroup *d_vgroups, uint64_t nvgroups, const uint64_t *d_vwords,
-                            const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups, void *d_partial,
-                            uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums, uint64_t *d_counts) {
-	GroupSumTypes ty;
-	ty.v_tmask = type_mask(v_type_size);
-	ty.v_sbit = type_sign_bit(v_type_size, v_signed);
-	ty.k_tmask = type_mask(k_type_size);
-	ty.v_tile_rows = tile_values(v_type_size);
-	ty.wide_only = g_tuning.group_sum_wide ? 1u : 0u;
-	const uint32_t nbins = ngroups + 1u;
-	return launch_group_scan(
-	    nbins, !ty.wide_only && g_tuning.group_sum_rw, nvgroups, ntiles,
-	    d_validity ? kGroupRwResident<true> : kGroupRwResident<false>, 7u, kGroupMaxWorkgroups / 2, 2u * nbins, d_partial,
-	    call_parity,
-	    [&](uint32_t nwg, unsigned long long *partial, unsigned long long *fallback) {
-		    auto launch = [&](auto kernel) {
-			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_vgroups, (uint32_t)nvgroups, d_vwords, d_kdescs,
-			                       d_kwords, ty, ngroups, partial, fallback, d_validity);
-		    };
-		    if (d_validity) launch(k_group_sum_rw<true>); else launch(k_group_sum_rw<false>);
-	    },
-	    [&](uint32_t nwg, unsigned long long *partial, const unsigned long long *handed) {
-		    auto launch = [&](auto kernel) {
-			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_vdescs, d_vtiles, (uint32_t)ntiles, d_vwords,
-			                       d_kdescs, d_kwords, ty, ngroups, partial, handed, d_validity);
-		    };
-		    if (d_validity) launch(k_group_sum<true>); else launch(k_group_sum<false>);
-	    },
-	    group_pairs_final(s, nbins, d_sums, d_counts));
-}
+// The grouped launchers hand launch_group_scan their kernels: the register walk takes the first column's scan groups and
+// words, then every further column's descriptors and words; the staged kernel the same with the tiles in front.
 
-// SUM(a * b) GROUP BY key under a selection bitmap (adac_group_product.inl).  Without d_counts the walk keeps no row counts.
-hipError_t launch_group_product(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
-                                uint32_t k_type_size, const adac_segment_desc *d_adescs, const TileRef *d_atiles,
-                                uint64_t ntiles, const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
-                                const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
-                                const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups,
-                                void *d_partial, uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums,
-                                uint64_t *d_counts) {
-	const GroupProductTypes ty = group_product_types(a_type_size, a_signed, b_type_size, b_signed, k_type_size);
+// The register walk is resident with seven workgroups per CU, six under a mask; the staged kernel with seven (21 KiB of
+// LDS each).
+hipError_t launch_group_sum(hipStream_t s, const Column &v, const Column &k, const ScanWork &work, uint32_t ngroups,
+                            const GroupScanState &state, const uint64_t *d_validity, uint64_t *d_sums, uint64_t *d_counts) {
+	const TypeWords tv = type_words(v);
+	const GroupSumTypes ty = {tv.tmask, tv.sbit, type_words(k).tmask, tile_values(v.type_size),
+	                          g_tuning.group_sum_wide ? 1u : 0u};
 	const uint32_t nbins = ngroups + 1u;
 	return launch_group_scan(
-	    nbins, g_tuning.group_product_rw != 0, nagroups, ntiles, kGroupProductRwResident, kGroupProductResident,
-	    kGroupMaxWorkgroups / 2, 2u * nbins, d_partial, call_parity,
+	    nbins, !ty.wide_only && g_tuning.group_sum_rw, work,
+	    d_validity ? kGroupRwResident<true> : kGroupRwResident<false>, 7u, kGroupMaxWorkgroups / 2, 2u * nbins, state,
 	    [&](uint32_t nwg, unsigned long long *partial, unsigned long long *fallback) {
-		    auto launch = [&](auto kernel) {
-			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_agroups, (uint32_t)nagroups, d_awords, d_bdescs,
-			                       d_bwords, d_kdescs, d_kwords, ty, ngroups, partial, fallback, d_validity);
-		    };
-		    if (d_validity) {
-			    if (d_counts) launch(k_group_product_rw<true, true>); else launch(k_group_product_rw<true, false>);
-		    } else {
-			    if (d_counts) launch(k_group_product_rw<false, true>); else launch(k_group_product_rw<false, false>);
-		    }
-	    },
-	    [&](uint32_t nwg, unsigned long long *partial, const unsigned long long *handed) {
-		    auto launch = [&](auto kernel) {
-			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles, d_awords,
-			                       d_bdescs, d_bwords, d_kdescs, d_kwords, ty, ngroups, partial, handed, d_validity);
-		    };
-		    if (d_validity) launch(k_group_product<true>); else launch(k_group_product<false>);
-	    },
-	    group_pairs_final(s, nbins, d_sums, d_counts));
-}
-
-// SUM(a * b * c) GROUP BY key under a selection bitmap (adac_group_product3.inl)
-hipError_t launch_group_product3(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
-                                 uint32_t c_type_size, bool c_signed, uint32_t k_type_size,
-                                 const adac_segment_desc *d_adescs, const TileRef *d_atiles, uint64_t ntiles,
-                                 const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
-                                 const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
-                                 const adac_segment_desc *d_cdescs, const uint64_t *d_cwords,
-                                 const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups,
-                                 void *d_partial, uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_sums,
-                                 uint64_t *d_counts) {
-	const GroupProduct3Types ty = {group_product_types(a_type_size, a_signed, b_type_size, b_signed, k_type_size),
-	                               type_mask(c_type_size), type_sign_bit(c_type_size, c_signed)};
-	const uint32_t nbins = ngroups + 1u;
-	return launch_group_scan(
-	    nbins, g_tuning.group_product3_rw != 0, nagroups, ntiles, kGroupProduct3RwResident, kGroupProduct3Resident,
-	    kGroupMaxWorkgroups / 2, 2u * nbins, d_partial, call_parity,
-	    [&](uint32_t nwg, unsigned long long *partial, unsigned long long *fallback) {
-		    auto launch = [&](auto kernel) {
-			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_agroups, (uint32_t)nagroups, d_awords, d_bdescs,
-			                       d_bwords, d_cdescs, d_cwords, d_kdescs, d_kwords, ty, ngroups, partial, fallback, d_validity);
-		    };
-		    if (d_validity) {
-			    if (d_counts) launch(k_group_product3_rw<true, true>); else launch(k_group_product3_rw<true, false>);
-		    } else {
-			    if (d_counts) launch(k_group_product3_rw<false, true>); else launch(k_group_product3_rw<false, false>);
-		    }
-	    },
-	    [&](uint32_t nwg, unsigned long long *partial, const unsigned long long *handed) {
-		    auto launch = [&](auto kernel) {
-			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles, d_awords,
-			                       d_bdescs, d_bwords, d_cdescs, d_cwords, d_kdescs, d_kwords, ty, ngroups, partial, handed,
+		    dispatch_flags([&](auto V) {
+			    hipLaunchKernelGGL(k_group_sum_rw<V.value>, dim3(nwg), dim3(kWorkgroup), 0, s, work.d_scan_groups,
+			                       (uint32_t)work.nscan_groups, v.d_words, k.d_descs, k.d_words, ty, ngroups, partial, fallback,
 			                       d_validity);
-		    };
-		    if (d_validity) launch(k_group_product3<true>); else launch(k_group_product3<false>);
+		    }, d_validity != nullptr);
+	    },
+	    [&](uint32_t nwg, unsigned long long *partial, const unsigned long long *handed) {
+		    dispatch_flags([&](auto V) {
+			    hipLaunchKernelGGL(k_group_sum<V.value>, dim3(nwg), dim3(kWorkgroup), 0, s, v.d_descs, work.d_tiles,
+			                       (uint32_t)work.ntiles, v.d_words, k.d_descs, k.d_words, ty, ngroups, partial, handed,
+			                       d_validity);
+		    }, d_validity != nullptr);
 	    },
 	    group_pairs_final(s, nbins, d_sums, d_counts));
 }
 
-// COUNT, SUM(q), SUM(a), SUM(b), SUM(a * b), SUM(a * c), SUM(a * b * c) GROUP BY key under a selection bitmap in one scan
-// (adac_group_q1.inl); type_size / is_signed: a, b, c, q, keys.  A workgroup's partial row is 7 x nbins words here, not
-// 2 x nbins, so the grids are capped at the rows the buffer holds, half for either kernel (257 bins: 585 rows each;
-// 8 bins: more than either grid asks for).
-hipError_t launch_group_q1(hipStream_t s, const uint32_t (&type_size)[5], const bool (&is_signed)[5],
-                           const adac_segment_desc *d_adescs, const TileRef *d_atiles, uint64_t ntiles,
-                           const ScanGroup *d_agroups, uint64_t nagroups, const uint64_t *d_awords,
-                           const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
-                           const adac_segment_desc *d_cdescs, const uint64_t *d_cwords,
-                           const adac_segment_desc *d_qdescs, const uint64_t *d_qwords,
-                           const adac_segment_desc *d_kdescs, const uint64_t *d_kwords, uint32_t ngroups, void *d_partial,
-                           uint32_t call_parity, const uint64_t *d_validity, uint64_t *d_out) {
-	const GroupQ1Types ty = {
-	    {group_product_types(type_size[0], is_signed[0], type_size[1], is_signed[1], type_size[4]), type_mask(type_size[2]),
-	     type_sign_bit(type_size[2], is_signed[2])},
-	    type_mask(type_size[3]),
-	    type_sign_bit(type_size[3], is_signed[3])};
+// Without d_counts the walk keeps no row counts.
+hipError_t launch_group_product(hipStream_t s, const Column &a, const Column &b, const Column &k, const ScanWork &work,
+                                uint32_t ngroups, const GroupScanState &state, const uint64_t *d_validity, uint64_t *d_sums,
+                                uint64_t *d_counts) {
+	const GroupProductTypes ty = group_product_types(a, b, k);
+	const uint32_t nbins = ngroups + 1u;
+	return launch_group_scan(
+	    nbins, g_tuning.group_product_rw != 0, work, kGroupProductRwResident, kGroupProductResident,
+	    kGroupMaxWorkgroups / 2, 2u * nbins, state,
+	    [&](uint32_t nwg, unsigned long long *partial, unsigned long long *fallback) {
+		    dispatch_flags([&](auto V, auto C) {
+			    hipLaunchKernelGGL((k_group_product_rw<V.value, C.value>), dim3(nwg), dim3(kWorkgroup), 0, s,
+			                       work.d_scan_groups, (uint32_t)work.nscan_groups, a.d_words, b.d_descs, b.d_words, k.d_descs,
+			                       k.d_words, ty, ngroups, partial, fallback, d_validity);
+		    }, d_validity != nullptr, d_counts != nullptr);
+	    },
+	    [&](uint32_t nwg, unsigned long long *partial, const unsigned long long *handed) {
+		    dispatch_flags([&](auto V) {
+			    hipLaunchKernelGGL(k_group_product<V.value>, dim3(nwg), dim3(kWorkgroup), 0, s, a.d_descs, work.d_tiles,
+			                       (uint32_t)work.ntiles, a.d_words, b.d_descs, b.d_words, k.d_descs, k.d_words, ty, ngroups,
+			                       partial, handed, d_validity);
+		    }, d_validity != nullptr);
+	    },
+	    group_pairs_final(s, nbins, d_sums, d_counts));
+}
+
+hipError_t launch_group_product3(hipStream_t s, const Column &a, const Column &b, const Column &c, const Column &k,
+                                 const ScanWork &work, uint32_t ngroups, const GroupScanState &state,
+                                 const uint64_t *d_validity, uint64_t *d_sums, uint64_t *d_counts) {
+	const GroupProduct3Types ty = group_product3_types(a, b, c, k);
+	const uint32_t nbins = ngroups + 1u;
+	return launch_group_scan(
+	    nbins, g_tuning.group_product3_rw != 0, work, kGroupProduct3RwResident, kGroupProduct3Resident,
+	    kGroupMaxWorkgroups / 2, 2u * nbins, state,
+	    [&](uint32_t nwg, unsigned long long *partial, unsigned long long *fallback) {
+		    dispatch_flags([&](auto V, auto C) {
+			    hipLaunchKernelGGL((k_group_product3_rw<V.value, C.value>), dim3(nwg), dim3(kWorkgroup), 0, s,
+			                       work.d_scan_groups, (uint32_t)work.nscan_groups, a.d_words, b.d_descs, b.d_words, c.d_descs,
+			                       c.d_words, k.d_descs, k.d_words, ty, ngroups, partial, fallback, d_validity);
+		    }, d_validity != nullptr, d_counts != nullptr);
+	    },
+	    [&](uint32_t nwg, unsigned long long *partial, const unsigned long long *handed) {
+		    dispatch_flags([&](auto V) {
+			    hipLaunchKernelGGL(k_group_product3<V.value>, dim3(nwg), dim3(kWorkgroup), 0, s, a.d_descs, work.d_tiles,
+			                       (uint32_t)work.ntiles, a.d_words, b.d_descs, b.d_words, c.d_descs, c.d_words, k.d_descs,
+			                       k.d_words, ty, ngroups, partial, handed, d_validity);
+		    }, d_validity != nullptr);
+	    },
+	    group_pairs_final(s, nbins, d_sums, d_counts));
+}
+
+// A workgroup's partial row is 7 x nbins words here, not 2 x nbins, so the grids are capped at the rows the buffer holds,
+// half for either kernel (257 bins: 585 rows each; 8 bins: more than either grid asks for).
+hipError_t launch_group_q1(hipStream_t s, const Column (&cols)[5], const ScanWork &work, uint32_t ngroups,
+                           const GroupScanState &state, const uint64_t *d_validity, uint64_t *d_out) {
+	const Column &a = cols[0], &b = cols[1], &c = cols[2], &q = cols[3], &k = cols[4];
+	const TypeWords tq = type_words(q);
+	const GroupQ1Types ty = {group_product3_types(a, b, c, k), tq.tmask, tq.sbit};
 	const uint32_t nbins = ngroups + 1u;
 	const uint64_t rows_cap = ((uint64_t)kGroupMaxWorkgroups * 2u * kGroupMaxBins) / ((uint64_t)kGroupQ1Terms * nbins) / 2u;
 	return launch_group_scan(
-	    nbins, g_tuning.group_q1_rw != 0, nagroups, ntiles, kGroupQ1RwResident, kGroupQ1Resident, rows_cap,
-	    kGroupQ1Terms * nbins, d_partial, call_parity,
+	    nbins, g_tuning.group_q1_rw != 0, work, kGroupQ1RwResident, kGroupQ1Resident, rows_cap, kGroupQ1Terms * nbins,
+	    state,
 	    [&](uint32_t nwg, unsigned long long *partial, unsigned long long *fallback) {
-		    auto launch = [&](auto kernel) {
-			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_agroups, (uint32_t)nagroups, d_awords, d_bdescs,
-			                       d_bwords, d_cdescs, d_cwords, d_qdescs, d_qwords, d_kdescs, d_kwords, ty, ngroups, partial,
-			                       fallback, d_validity);
-		    };
-		    if (d_validity) launch(k_group_q1_rw<true>); else launch(k_group_q1_rw<false>);
+		    dispatch_flags([&](auto V) {
+			    hipLaunchKernelGGL(k_group_q1_rw<V.value>, dim3(nwg), dim3(kWorkgroup), 0, s, work.d_scan_groups,
+			                       (uint32_t)work.nscan_groups, a.d_words, b.d_descs, b.d_words, c.d_descs, c.d_words, q.d_descs,
+			                       q.d_words, k.d_descs, k.d_words, ty, ngroups, partial, fallback, d_validity);
+		    }, d_validity != nullptr);
 	    },
 	    [&](uint32_t nwg, unsigned long long *partial, const unsigned long long *handed) {
-		    auto launch = [&](auto kernel) {
-			    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(kWorkgroup), 0, s, d_adescs, d_atiles, (uint32_t)ntiles, d_awords,
-			                       d_bdescs, d_bwords, d_cdescs, d_cwords, d_qdescs, d_qwords, d_kdescs, d_kwords, ty, ngroups,
-			                       partial, handed, d_validity);
-		    };
-		    if (d_validity) launch(k_group_q1<true>); else launch(k_group_q1<false>);
+		    dispatch_flags([&](auto V) {
+			    hipLaunchKernelGGL(k_group_q1<V.value>, dim3(nwg), dim3(kWorkgroup), 0, s, a.d_descs, work.d_tiles,
+			                       (uint32_t)work.ntiles, a.d_words, b.d_descs, b.d_words, c.d_descs, c.d_words, q.d_descs,
+			                       q.d_words, k.d_descs, k.d_words, ty, ngroups, partial, handed, d_validity);
+		    }, d_validity != nullptr);
 	    },
 	    [&](const unsigned long long *partial, uint32_t nwg_rw, uint32_t nwg, const unsigned long long *fallback,
 	        unsigned long long *next_fallback, int rw_ran) {
@@ -2271,104 +2249,60 @@ hipError_t launch_group_q1(hipStream_t s, const uint32_t (&type_size)[5], const 
 	    });
 }
 
-// SUM(a * b) per segment under a selection bitmap (adac_sum_product.inl): one workgroup per scan group of `a`; the
-// caller has cleared d_sums
-hipError_t launch_scan_sum_product(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
-                                   const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,
-                                   const adac_segment_desc *d_bdescs, const uint64_t *d_bwords,
+// The per-segment scans of one or two columns: one workgroup per scan group of the first.
+hipError_t launch_scan_sum_product(hipStream_t s, const Column &a, const Column &b, const ScanWork &work,
                                    const uint64_t *d_validity, uint64_t *d_sums) {
-	if (ngroups == 0) return hipSuccess;
-	ProductTypes ty;
-	ty.a_tmask = type_mask(a_type_size);
-	ty.a_sbit = type_sign_bit(a_type_size, a_signed);
-	ty.b_tmask = type_mask(b_type_size);
-	ty.b_sbit = type_sign_bit(b_type_size, b_signed);
-	unsigned long long *sums = reinterpret_cast<unsigned long long *>(d_sums);
-	if (d_validity) {
-		hipLaunchKernelGGL(k_scan_product<true>, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_agroups, d_awords,
-		                   d_bdescs, d_bwords, ty, d_validity, sums);
-	} else {
-		hipLaunchKernelGGL(k_scan_product<false>, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_agroups, d_awords,
-		                   d_bdescs, d_bwords, ty, d_validity, sums);
-	}
+	if (work.nscan_groups == 0) return hipSuccess;
+	const ProductTypes ty = product_types(type_words(a), type_words(b));
+	dispatch_flags([&](auto V) {
+		hipLaunchKernelGGL(k_scan_product<V.value>, dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
+		                   work.d_scan_groups, a.d_words, b.d_descs, b.d_words, ty, d_validity,
+		                   reinterpret_cast<unsigned long long *>(d_sums));
+	}, d_validity != nullptr);
 	return hipGetLastError();
 }
 
-// Rows where value(a) <cmp> value(b), per segment, and their bitmap when d_bitmap is given (adac_scan_compare.inl): one
-// workgroup per scan group of `a`; the caller has cleared d_counts and the bitmap
-hipError_t launch_scan_compare(hipStream_t s, uint32_t a_type_size, bool a_signed, uint32_t b_type_size, bool b_signed,
-                               const ScanGroup *d_agroups, uint64_t ngroups, const uint64_t *d_awords,
-                               const adac_segment_desc *d_bdescs, const uint64_t *d_bwords, const uint64_t *d_validity,
-                               uint32_t cmp, uint64_t *d_bitmap, uint64_t *d_counts) {
-	if (ngroups == 0) return hipSuccess;
-	ProductTypes ty;
-	ty.a_tmask = type_mask(a_type_size);
-	ty.a_sbit = type_sign_bit(a_type_size, a_signed);
-	ty.b_tmask = type_mask(b_type_size);
-	ty.b_sbit = type_sign_bit(b_type_size, b_signed);
-	unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_counts);
-	uint32_t *bitmap32 = reinterpret_cast<uint32_t *>(d_bitmap);
-	auto launch = [&](auto kernel) {
-		hipLaunchKernelGGL(kernel, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_agroups, d_awords, d_bdescs, d_bwords,
-		                   ty, d_validity, cmp, bitmap32, counts);
-	};
-	if (d_bitmap) {
-		if (d_validity) launch(k_scan_compare<true, true>); else launch(k_scan_compare<false, true>);
-	} else {
-		if (d_validity) launch(k_scan_compare<true, false>); else launch(k_scan_compare<false, false>);
-	}
+hipError_t launch_scan_compare(hipStream_t s, const Column &a, const Column &b, const ScanWork &work,
+                               const uint64_t *d_validity, uint32_t cmp, uint64_t *d_bitmap, uint64_t *d_counts) {
+	if (work.nscan_groups == 0) return hipSuccess;
+	const ProductTypes ty = product_types(type_words(a), type_words(b));
+	dispatch_flags([&](auto V, auto SEL) {
+		hipLaunchKernelGGL((k_scan_compare<V.value, SEL.value>), dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
+		                   work.d_scan_groups, a.d_words, b.d_descs, b.d_words, ty, d_validity, cmp,
+		                   reinterpret_cast<uint32_t *>(d_bitmap), reinterpret_cast<unsigned long long *>(d_counts));
+	}, d_validity != nullptr, d_bitmap != nullptr);
 	return hipGetLastError();
 }
 
 // the domain [set_base, set_base + set_bits - 1] of a member scan in the biased form the kernels work in
-static MemberDomain member_domain(uint32_t type_size, bool is_signed, uint64_t set_base, uint64_t set_bits) {
-	MemberDomain dom;
-	dom.tmask = type_mask(type_size);
-	dom.sbit = type_sign_bit(type_size, is_signed);
-	dom.bbase = set_base ^ dom.sbit;
-	dom.set_bits = set_bits;
-	return dom;
+static MemberDomain member_domain(const Column &col, uint64_t set_base, uint64_t set_bits) {
+	const TypeWords t = type_words(col);
+	return {t.tmask, t.sbit, set_base ^ t.sbit, set_bits};
 }
 
-// Rows whose value is a member of the bit set d_set over [set_base, set_base + set_bits - 1], per segment, and their
-// bitmap when d_bitmap is given (adac_scan_member.inl): one workgroup per scan group; the caller has checked the domain
-// against the type and cleared d_counts and the bitmap
-hipError_t launch_scan_member(hipStream_t s, uint32_t type_size, bool is_signed, const ScanGroup *d_groups,
-                              uint64_t ngroups, const uint64_t *d_words, const uint64_t *d_validity, const uint64_t *d_set,
-                              uint64_t set_base, uint64_t set_bits, uint64_t *d_bitmap, uint64_t *d_counts) {
-	if (ngroups == 0) return hipSuccess;
-	const MemberDomain dom = member_domain(type_size, is_signed, set_base, set_bits);
-	unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_counts);
-	uint32_t *bitmap32 = reinterpret_cast<uint32_t *>(d_bitmap);
+hipError_t launch_scan_member(hipStream_t s, const Column &col, const ScanWork &work, const uint64_t *d_validity,
+                              const uint64_t *d_set, uint64_t set_base, uint64_t set_bits, uint64_t *d_bitmap,
+                              uint64_t *d_counts) {
+	if (work.nscan_groups == 0) return hipSuccess;
+	const MemberDomain dom = member_domain(col, set_base, set_bits);
 	uint32_t *set32 = reinterpret_cast<uint32_t *>(const_cast<uint64_t *>(d_set)); // the probe only reads it
-	auto launch = [&](auto kernel) {
-		hipLaunchKernelGGL(kernel, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_groups, d_words, dom, d_validity,
-		                   set32, bitmap32, counts);
-	};
-	if (d_bitmap) {
-		if (d_validity) launch(k_scan_member<true, true>); else launch(k_scan_member<false, true>);
-	} else {
-		if (d_validity) launch(k_scan_member<true, false>); else launch(k_scan_member<false, false>);
-	}
+	dispatch_flags([&](auto V, auto SEL) {
+		hipLaunchKernelGGL((k_scan_member<V.value, SEL.value>), dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
+		                   work.d_scan_groups, col.d_words, dom, d_validity, set32, reinterpret_cast<uint32_t *>(d_bitmap),
+		                   reinterpret_cast<unsigned long long *>(d_counts));
+	}, d_validity != nullptr, d_bitmap != nullptr);
 	return hipGetLastError();
 }
 
-// The set of the wanted rows' values and the rows inside the domain per segment; the caller has cleared d_set and
-// d_counts
-hipError_t launch_scan_member_build(hipStream_t s, uint32_t type_size, bool is_signed, const ScanGroup *d_groups,
-                                    uint64_t ngroups, const uint64_t *d_words, const uint64_t *d_validity,
+hipError_t launch_scan_member_build(hipStream_t s, const Column &col, const ScanWork &work, const uint64_t *d_validity,
                                     uint64_t set_base, uint64_t set_bits, uint64_t *d_set, uint64_t *d_counts) {
-	if (ngroups == 0) return hipSuccess;
-	const MemberDomain dom = member_domain(type_size, is_signed, set_base, set_bits);
-	unsigned long long *counts = reinterpret_cast<unsigned long long *>(d_counts);
-	uint32_t *set32 = reinterpret_cast<uint32_t *>(d_set);
-	if (d_validity) {
-		hipLaunchKernelGGL(k_scan_member_build<true>, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_groups, d_words,
-		                   dom, d_validity, set32, counts);
-	} else {
-		hipLaunchKernelGGL(k_scan_member_build<false>, dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s, d_groups, d_words,
-		                   dom, d_validity, set32, counts);
-	}
+	if (work.nscan_groups == 0) return hipSuccess;
+	const MemberDomain dom = member_domain(col, set_base, set_bits);
+	dispatch_flags([&](auto V) {
+		hipLaunchKernelGGL(k_scan_member_build<V.value>, dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
+		                   work.d_scan_groups, col.d_words, dom, d_validity, reinterpret_cast<uint32_t *>(d_set),
+		                   reinterpret_cast<unsigned long long *>(d_counts));
+	}, d_validity != nullptr);
 	return hipGetLastError();
 }
 
@@ -2409,31 +2343,27 @@ hipError_t launch_expand_tiles(hipStream_t s, uint32_t type_size, const adac_seg
 	return hipGetLastError();
 }
 
-hipError_t launch_unpack(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs, const TileRef *d_tiles,
-                         uint64_t ntiles, const uint64_t *d_words, void *d_out, const TileRec *d_recs) {
+hipError_t launch_unpack(hipStream_t s, const Column &col, const TileRef *d_tiles, uint64_t ntiles, void *d_out,
+                         const TileRec *d_recs) {
 	if (ntiles == 0) return hipSuccess;
-	return dispatch_size(type_size, [&](auto tag) {
+	return dispatch_size(col.type_size, [&](auto tag) {
 		using U = decltype(tag);
-		if (d_recs) {
-			hipLaunchKernelGGL((k_unpack<U, false, true>), dim3((unsigned)ntiles), dim3(kWorkgroup), 0, s, d_descs, d_tiles,
-			                   RangeArgs {}, d_words, static_cast<U *>(d_out), d_recs);
-			return hipGetLastError();
-		}
-		hipLaunchKernelGGL((k_unpack<U, false>), dim3((unsigned)ntiles), dim3(kWorkgroup), 0, s, d_descs, d_tiles,
-		                   RangeArgs {}, d_words, static_cast<U *>(d_out), static_cast<const TileRec *>(nullptr));
+		dispatch_flags([&](auto RECS) { // the expanded tile records, when the caller has them
+			hipLaunchKernelGGL((k_unpack<U, false, RECS.value>), dim3((unsigned)ntiles), dim3(kWorkgroup), 0, s, col.d_descs,
+			                   d_tiles, RangeArgs {}, col.d_words, static_cast<U *>(d_out), d_recs);
+		}, d_recs != nullptr);
 		return hipGetLastError();
 	});
 }
 
-hipError_t launch_unpack_range(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs, RangeArgs range,
-                               const uint64_t *d_words, void *d_out) {
+hipError_t launch_unpack_range(hipStream_t s, const Column &col, RangeArgs range, void *d_out) {
 	if (range.count == 0) return hipSuccess;
-	return dispatch_size(type_size, [&](auto tag) {
+	return dispatch_size(col.type_size, [&](auto tag) {
 		using U = decltype(tag);
 		const uint32_t tile = kTileBytes / sizeof(U);
 		const uint32_t nt = (range.count + tile - 1) / tile;
-		hipLaunchKernelGGL((k_unpack<U, true>), dim3(nt), dim3(kWorkgroup), 0, s, d_descs,
-		                   static_cast<const TileRef *>(nullptr), range, d_words, static_cast<U *>(d_out),
+		hipLaunchKernelGGL((k_unpack<U, true>), dim3(nt), dim3(kWorkgroup), 0, s, col.d_descs,
+		                   static_cast<const TileRef *>(nullptr), range, col.d_words, static_cast<U *>(d_out),
 		                   static_cast<const TileRec *>(nullptr));
 		return hipGetLastError();
 	});
@@ -2450,13 +2380,13 @@ hipError_t launch_unpack_jobs(hipStream_t s, uint32_t type_size, const UnpackJob
 	});
 }
 
-hipError_t launch_fetch(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs, const uint64_t *d_words,
-                        const uint32_t *d_segs, const uint32_t *d_rows, uint64_t n, void *d_out) {
+hipError_t launch_fetch(hipStream_t s, const Column &col, const uint32_t *d_segs, const uint32_t *d_rows, uint64_t n,
+                        void *d_out) {
 	if (n == 0) return hipSuccess;
-	return dispatch_size(type_size, [&](auto tag) {
+	return dispatch_size(col.type_size, [&](auto tag) {
 		using U = decltype(tag);
 		hipLaunchKernelGGL(k_fetch<U>, dim3((unsigned)((n + kWorkgroup - 1) / kWorkgroup)), dim3(kWorkgroup), 0, s,
-		                   d_descs, d_words, d_segs, d_rows, n, static_cast<U *>(d_out));
+		                   col.d_descs, col.d_words, d_segs, d_rows, n, static_cast<U *>(d_out));
 		return hipGetLastError();
 	});
 }
@@ -2470,28 +2400,35 @@ hipError_t launch_expand_groups(hipStream_t s, const adac_segment_desc *d_descs,
 	return hipGetLastError();
 }
 
-hipError_t launch_scan_sum(hipStream_t s, uint32_t type_size, const ScanGroupList &gl, const uint64_t *d_words,
-                           const uint64_t *d_validity, uint64_t sbit, uint64_t *d_sums) {
+namespace {
+// k_scan_agg over every group (it leaves the groups at widths 2 and 3 alone), then its narrow form over those, where
+// the scan has one; args: the kernel's parameters after narrow_idx
+template <typename U, int OP, bool V, class... Args>
+void launch_scan_agg(hipStream_t s, const ScanGroupList &gl, Args... args) {
+	hipLaunchKernelGGL((k_scan_agg<U, OP, V, false>), dim3((unsigned)gl.ngroups), dim3(kWorkgroup), 0, s, gl.d_groups,
+	                   gl.d_narrow_idx, args...);
+	if constexpr (kScanHasNarrowKernel<OP, V>) {
+		if (gl.n_narrow) {
+			hipLaunchKernelGGL((k_scan_agg<U, OP, V, true>), dim3(gl.n_narrow), dim3(kWorkgroup), 0, s, gl.d_groups,
+			                   gl.d_narrow_idx, args...);
+		}
+	}
+}
+} // namespace
+
+hipError_t launch_scan_sum(hipStream_t s, const Column &col, const ScanGroupList &gl, const uint64_t *d_validity,
+                           uint64_t *d_sums) {
 	if (gl.ngroups == 0) return hipSuccess;
-	const RangePred widen {0ull, 0ull, sbit}; // SUM only needs T's sign bit
-	return dispatch_size(type_size, [&](auto tag) {
+	const RangePred widen {0ull, 0ull, type_words(col).sbit}; // SUM only needs T's sign bit
+	return dispatch_size(col.type_size, [&](auto tag) {
 		using U = decltype(tag);
-		const dim3 grid((unsigned)gl.ngroups);
 		const int tpl = g_tuning.templated_scan | (g_tuning.sel_debug == 7 ? 7 << 1 : 0);
 		uint32_t *no_bitmap = nullptr;
 		SelEdge *no_edges = nullptr;
-		if (d_validity) {
-			hipLaunchKernelGGL((k_scan_agg<U, 0, true, false>), grid, dim3(kWorkgroup), 0, s, gl.d_groups, gl.d_narrow_idx,
-			                   tpl, d_words, widen, d_validity, d_sums, no_bitmap, no_edges, gl.d_res_cells, no_bitmap, 0u, ~0ull);
-		} else {
-			hipLaunchKernelGGL((k_scan_agg<U, 0, false, false>), grid, dim3(kWorkgroup), 0, s, gl.d_groups, gl.d_narrow_idx,
-			                   tpl, d_words, widen, d_validity, d_sums, no_bitmap, no_edges, gl.d_res_cells, no_bitmap, 0u, ~0ull);
-			if (gl.n_narrow) {
-				hipLaunchKernelGGL((k_scan_agg<U, 0, false, true>), dim3(gl.n_narrow), dim3(kWorkgroup), 0, s, gl.d_groups,
-				                   gl.d_narrow_idx, tpl, d_words, widen, d_validity, d_sums, no_bitmap, no_edges,
-				                   gl.d_res_cells, no_bitmap, 0u, ~0ull);
-			}
-		}
+		dispatch_flags([&](auto V) {
+			launch_scan_agg<U, 0, V.value>(s, gl, tpl, col.d_words, widen, d_validity, d_sums, no_bitmap, no_edges,
+			                               gl.d_res_cells, no_bitmap, 0u, ~0ull);
+		}, d_validity != nullptr);
 		return hipGetLastError();
 	});
 }
@@ -2506,37 +2443,22 @@ hipError_t launch_sel_merge_edges(hipStream_t s, const void *d_edges, uint64_t n
 	return hipGetLastError();
 }
 
-hipError_t launch_scan_count_range(hipStream_t s, uint32_t type_size, const ScanGroupList &gl, const uint64_t *d_words,
-                                   const uint64_t *d_validity, uint64_t blo, uint64_t bspan, uint64_t sbit,
-                                   uint64_t *d_counts, uint64_t *d_bitmap, void *d_edges, bool edge_cells,
-                                   uint64_t tail_word) {
+hipError_t launch_scan_count_range(hipStream_t s, const Column &col, const ScanGroupList &gl, const uint64_t *d_validity,
+                                   uint64_t blo, uint64_t bspan, uint64_t *d_counts, uint64_t *d_bitmap, void *d_edges,
+                                   bool edge_cells, uint64_t tail_word) {
 	if (gl.ngroups == 0) return hipSuccess;
 	uint32_t *const ecells = edge_cells ? gl.d_edge_cells : nullptr;
 	const uint32_t last_group = (uint32_t)(gl.ngroups - 1);
-	return dispatch_size(type_size, [&](auto tag) {
+	const RangePred pred {blo, bspan, type_words(col).sbit};
+	return dispatch_size(col.type_size, [&](auto tag) {
 		using U = decltype(tag);
-		const dim3 grid((unsigned)gl.ngroups);
-		const RangePred pred {blo, bspan, sbit};
-		uint32_t *bm = reinterpret_cast<uint32_t *>(d_bitmap);
 		const int tpl = g_tuning.templated_scan | ((g_tuning.sel_debug == 5 ? 0 : g_tuning.sel_debug) << 1);
-		// the common kernel over every group (it leaves the groups at widths 2 and 3 alone), then the narrow one over those
-#define ADAC_SCAN(OPN, VAL)                                                                                            \
-	do {                                                                                                               \
-		hipLaunchKernelGGL((k_scan_agg<U, OPN, VAL, false>), grid, dim3(kWorkgroup), 0, s, gl.d_groups, gl.d_narrow_idx, \
-		                   tpl, d_words, pred, d_validity, d_counts, bm, static_cast<SelEdge *>(d_edges),                \
-		                   gl.d_res_cells, ecells, last_group, tail_word);                                               \
-		if (gl.n_narrow) {                                                                                             \
-			hipLaunchKernelGGL((k_scan_agg<U, OPN, VAL, true>), dim3(gl.n_narrow), dim3(kWorkgroup), 0, s, gl.d_groups,  \
-			                   gl.d_narrow_idx, tpl, d_words, pred, d_validity, d_counts, bm,                            \
-			                   static_cast<SelEdge *>(d_edges), gl.d_res_cells, ecells, last_group, tail_word);          \
-		}                                                                                                              \
-	} while (0)
-		if (d_bitmap) {
-			if (d_validity) ADAC_SCAN(3, true); else ADAC_SCAN(3, false);
-		} else {
-			if (d_validity) ADAC_SCAN(1, true); else ADAC_SCAN(1, false);
-		}
-#undef ADAC_SCAN
+		dispatch_flags([&](auto SEL, auto V) { // OP 3: COUNT + selection bitmap, 1: COUNT
+			launch_scan_agg<U, SEL.value ? 3 : 1, V.value>(s, gl, tpl, col.d_words, pred, d_validity, d_counts,
+			                                               reinterpret_cast<uint32_t *>(d_bitmap),
+			                                               static_cast<SelEdge *>(d_edges), gl.d_res_cells, ecells,
+			                                               last_group, tail_word);
+		}, d_bitmap != nullptr, d_validity != nullptr);
 		return hipGetLastError();
 	});
 }
@@ -2594,27 +2516,25 @@ hipError_t launch_bp_write(hipStream_t s, uint32_t type_size, const void *d_recs
 	});
 }
 
-hipError_t launch_bp_unpack(hipStream_t s, uint32_t type_size, const void *d_groups, uint64_t ngroups,
-                            const void *d_blocks, void *d_out) {
+hipError_t launch_bp_unpack(hipStream_t s, const BpColumn &col, uint64_t ngroups, void *d_out) {
 	if (ngroups == 0) return hipSuccess;
-	return dispatch_size(type_size, [&](auto tag) {
+	return dispatch_size(col.type_size, [&](auto tag) {
 		using U = decltype(tag);
 		hipLaunchKernelGGL((k_bp_unpack<U, false>), dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s,
-		                   static_cast<const BpGroup *>(d_groups), static_cast<const uint8_t *>(d_blocks), BpRangeArgs {},
-		                   static_cast<U *>(d_out));
+		                   static_cast<const BpGroup *>(col.d_groups), static_cast<const uint8_t *>(col.d_blocks),
+		                   BpRangeArgs {}, static_cast<U *>(d_out));
 		return hipGetLastError();
 	});
 }
 
-hipError_t launch_bp_unpack_range(hipStream_t s, uint32_t type_size, const void *d_groups, uint32_t group0,
-                                  uint32_t skip_first, uint64_t count, uint64_t out_off, const void *d_blocks,
-                                  void *d_out) {
+hipError_t launch_bp_unpack_range(hipStream_t s, const BpColumn &col, uint32_t group0, uint32_t skip_first, uint64_t count,
+                                  uint64_t out_off, void *d_out) {
 	if (count == 0) return hipSuccess;
-	return dispatch_size(type_size, [&](auto tag) {
+	return dispatch_size(col.type_size, [&](auto tag) {
 		using U = decltype(tag);
 		const uint64_t ngroups = ((uint64_t)skip_first + count + kBpGroupRows - 1) / kBpGroupRows;
 		hipLaunchKernelGGL((k_bp_unpack<U, true>), dim3((unsigned)ngroups), dim3(kWorkgroup), 0, s,
-		                   static_cast<const BpGroup *>(d_groups), static_cast<const uint8_t *>(d_blocks),
+		                   static_cast<const BpGroup *>(col.d_groups), static_cast<const uint8_t *>(col.d_blocks),
 		                   BpRangeArgs {group0, skip_first, count, out_off}, static_cast<U *>(d_out));
 		return hipGetLastError();
 	});
@@ -2654,33 +2574,28 @@ static void launch_exclusive_prefix(hipStream_t s, const uint32_t *d_cnt, uint64
 }
 
 // Fused scans on BITPACKING blocks (adac_bp_scans.inl): 8 workgroups = 32 waves per CU.
-hipError_t launch_bp_scan(hipStream_t s, uint32_t type_size, bool is_signed, int op, const void *d_groups,
-                          const uint32_t *d_group_seg, uint64_t ngroups, const void *d_blocks,
+hipError_t launch_bp_scan(hipStream_t s, const BpColumn &col, int op, const uint32_t *d_group_seg, uint64_t ngroups,
                           const uint64_t *d_validity, uint64_t blo, uint64_t bspan, uint64_t *d_res, uint64_t *d_bitmap) {
 	static_assert(kBpScanOpSum == kBpScanSum && kBpScanOpRange == kBpScanRange && kBpScanOpMinMax == kBpScanMinMax, "ops");
 	if (ngroups == 0) return hipSuccess;
 	BpScanArgs a;
-	const BpGroup *groups = static_cast<const BpGroup *>(d_groups);
 	const dim3 grid = bp_wave_grid(ngroups, 8, a.run);
-	a.blocks = static_cast<const uint8_t *>(d_blocks);
+	a.blocks = static_cast<const uint8_t *>(col.d_blocks);
 	a.validity = d_validity;
-	a.sbit = type_sign_bit(type_size, is_signed);
+	a.sbit = type_words(col).sbit;
 	a.blo = blo;
 	a.bspan = bspan;
 	a.res = reinterpret_cast<unsigned long long *>(d_res);
 	a.bitmap = reinterpret_cast<unsigned long long *>(d_bitmap);
-	return dispatch_size(type_size, [&](auto tag) {
+	return dispatch_size(col.type_size, [&](auto tag) {
 		using U = decltype(tag);
-#define ADAC_BP_SCAN(OP)                                                                                               \
-	do {                                                                                                               \
-		if (d_validity) hipLaunchKernelGGL((k_bp_scan<U, OP, true>), grid, dim3(kWorkgroup), 0, s, groups, d_group_seg, a); \
-		else hipLaunchKernelGGL((k_bp_scan<U, OP, false>), grid, dim3(kWorkgroup), 0, s, groups, d_group_seg, a);      \
-	} while (0)
-		if (op == kBpScanSum) ADAC_BP_SCAN(kBpScanSum);
-		else if (op == kBpScanRange) ADAC_BP_SCAN(kBpScanRange);
-		else ADAC_BP_SCAN(kBpScanMinMax);
-#undef ADAC_BP_SCAN
-		return hipGetLastError();
+		const bool known = dispatch_int<kBpScanSum, kBpScanRange, kBpScanMinMax>(op, [&](auto OP) {
+			dispatch_flags([&](auto V) {
+				hipLaunchKernelGGL((k_bp_scan<U, OP.value, V.value>), grid, dim3(kWorkgroup), 0, s,
+				                   static_cast<const BpGroup *>(col.d_groups), d_group_seg, a);
+			}, d_validity != nullptr);
+		});
+		return known ? hipGetLastError() : hipErrorInvalidValue;
 	});
 }
 
@@ -2694,36 +2609,37 @@ hipError_t launch_bp_scan_minmax_finish(hipStream_t s, uint32_t type_size, bool 
 
 // Pair scans on BITPACKING blocks (adac_bp_pair_scans.inl).  Two stage buffers per wave (and the grouped kernel's
 // bins) leave room for `resident` workgroups per CU.
-static BpPairArgs bp_pair_args(const BpPairColumn &a, const BpPairColumn &b, uint64_t ngroups, uint64_t resident,
+static BpPairArgs bp_pair_args(const BpColumn &a, const BpColumn &b, uint64_t ngroups, uint64_t resident,
                                const uint64_t *d_validity, uint64_t *d_res, dim3 &grid) {
+	const TypeWords ta = type_words(a), tb = type_words(b);
 	BpPairArgs s;
 	grid = bp_wave_grid(ngroups, resident, s.run);
 	s.a_blocks = static_cast<const uint8_t *>(a.d_blocks);
 	s.b_blocks = static_cast<const uint8_t *>(b.d_blocks);
 	s.validity = d_validity;
-	s.a_tmask = type_mask(a.type_size);
-	s.a_sbit = type_sign_bit(a.type_size, a.is_signed);
-	s.b_tmask = type_mask(b.type_size);
-	s.b_sbit = type_sign_bit(b.type_size, b.is_signed);
+	s.a_tmask = ta.tmask;
+	s.a_sbit = ta.sbit;
+	s.b_tmask = tb.tmask;
+	s.b_sbit = tb.sbit;
 	s.res = reinterpret_cast<unsigned long long *>(d_res);
 	s.counts = nullptr;
 	s.nkeys = 0;
 	return s;
 }
 
-hipError_t launch_bp_scan_pair_sum(hipStream_t st, const BpPairColumn &a, const BpPairColumn &b,
-                                   const uint32_t *d_group_seg, uint64_t ngroups, const uint64_t *d_validity,
-                                   uint64_t *d_sums) {
+hipError_t launch_bp_scan_pair_sum(hipStream_t st, const BpColumn &a, const BpColumn &b, const uint32_t *d_group_seg,
+                                   uint64_t ngroups, const uint64_t *d_validity, uint64_t *d_sums) {
 	if (ngroups == 0) return hipSuccess;
 	dim3 grid;
 	const BpPairArgs s = bp_pair_args(a, b, ngroups, 4, d_validity, d_sums, grid);
 	const BpGroup *ga = static_cast<const BpGroup *>(a.d_groups), *gb = static_cast<const BpGroup *>(b.d_groups);
-	if (d_validity) hipLaunchKernelGGL(k_bp_scan_pair_sum<true>, grid, dim3(kWorkgroup), 0, st, ga, gb, d_group_seg, s);
-	else hipLaunchKernelGGL(k_bp_scan_pair_sum<false>, grid, dim3(kWorkgroup), 0, st, ga, gb, d_group_seg, s);
+	dispatch_flags([&](auto V) {
+		hipLaunchKernelGGL(k_bp_scan_pair_sum<V.value>, grid, dim3(kWorkgroup), 0, st, ga, gb, d_group_seg, s);
+	}, d_validity != nullptr);
 	return hipGetLastError();
 }
 
-hipError_t launch_bp_scan_pair_gsum(hipStream_t st, const BpPairColumn &v, const BpPairColumn &k, uint64_t ngroups,
+hipError_t launch_bp_scan_pair_gsum(hipStream_t st, const BpColumn &v, const BpColumn &k, uint64_t ngroups,
                                     const uint64_t *d_validity, uint32_t nkeys, uint64_t *d_sums, uint64_t *d_counts) {
 	if (ngroups == 0) return hipSuccess;
 	static_assert(kBpPairBins == 257, "adac_bp_scan_group_sum admits 256 keys + the overflow entry");
@@ -2732,14 +2648,15 @@ hipError_t launch_bp_scan_pair_gsum(hipStream_t st, const BpPairColumn &v, const
 	s.counts = reinterpret_cast<unsigned long long *>(d_counts);
 	s.nkeys = nkeys;
 	const BpGroup *gv = static_cast<const BpGroup *>(v.d_groups), *gk = static_cast<const BpGroup *>(k.d_groups);
-	if (d_validity) hipLaunchKernelGGL(k_bp_scan_pair_gsum<true>, grid, dim3(kWorkgroup), 0, st, gv, gk, s);
-	else hipLaunchKernelGGL(k_bp_scan_pair_gsum<false>, grid, dim3(kWorkgroup), 0, st, gv, gk, s);
+	dispatch_flags([&](auto V) {
+		hipLaunchKernelGGL(k_bp_scan_pair_gsum<V.value>, grid, dim3(kWorkgroup), 0, st, gv, gk, s);
+	}, d_validity != nullptr);
 	return hipGetLastError();
 }
 
-hipError_t launch_bp_scan_pair_cmp(hipStream_t st, const BpPairColumn &a, const BpPairColumn &b,
-                                   const uint32_t *d_group_seg, uint64_t ngroups, const uint64_t *d_validity,
-                                   uint32_t cmp, uint64_t *d_counts, uint64_t *d_bitmap) {
+hipError_t launch_bp_scan_pair_cmp(hipStream_t st, const BpColumn &a, const BpColumn &b, const uint32_t *d_group_seg,
+                                   uint64_t ngroups, const uint64_t *d_validity, uint32_t cmp, uint64_t *d_counts,
+                                   uint64_t *d_bitmap) {
 	static_assert(kBpCmpLt == ADAC_CMP_LT && kBpCmpEq == ADAC_CMP_EQ && kBpCmpGt == ADAC_CMP_GT, "cmp bits");
 	if (ngroups == 0) return hipSuccess;
 	dim3 grid;
@@ -2748,44 +2665,47 @@ hipError_t launch_bp_scan_pair_cmp(hipStream_t st, const BpPairColumn &a, const 
 	c.bitmap = reinterpret_cast<unsigned long long *>(d_bitmap);
 	c.cmp = cmp;
 	const BpGroup *ga = static_cast<const BpGroup *>(a.d_groups), *gb = static_cast<const BpGroup *>(b.d_groups);
-	if (d_validity) hipLaunchKernelGGL(k_bp_scan_pair_cmp<true>, grid, dim3(kWorkgroup), 0, st, ga, gb, d_group_seg, c);
-	else hipLaunchKernelGGL(k_bp_scan_pair_cmp<false>, grid, dim3(kWorkgroup), 0, st, ga, gb, d_group_seg, c);
+	dispatch_flags([&](auto V) {
+		hipLaunchKernelGGL(k_bp_scan_pair_cmp<V.value>, grid, dim3(kWorkgroup), 0, st, ga, gb, d_group_seg, c);
+	}, d_validity != nullptr);
 	return hipGetLastError();
 }
 
 // Scan with selection on BITPACKING blocks (adac_bp_select_gather.inl): counts per metadata group, their exclusive
 // prefix, then the gather at launch_bp_scan's 8 workgroups = 32 waves per CU.
-hipError_t launch_bp_gather_selected(hipStream_t s, uint32_t type_size, const void *d_groups, uint64_t ngroups,
-                                     const void *d_blocks, const uint64_t *d_bitmap, uint32_t *d_group_cnt,
-                                     uint64_t *d_group_off, uint64_t *d_block_tot, void *d_out, uint64_t *d_out_ids,
-                                     uint64_t *d_total) {
+hipError_t launch_bp_gather_selected(hipStream_t s, const BpColumn &col, uint64_t ngroups, const uint64_t *d_bitmap,
+                                     uint32_t *d_group_cnt, uint64_t *d_group_off, uint64_t *d_block_tot, void *d_out,
+                                     uint64_t *d_out_ids, uint64_t *d_total) {
 	if (ngroups == 0) return hipMemsetAsync(d_total, 0, sizeof(uint64_t), s);
-	const BpGroup *groups = static_cast<const BpGroup *>(d_groups);
+	const BpGroup *groups = static_cast<const BpGroup *>(col.d_groups);
 	hipLaunchKernelGGL(k_bp_group_popc, dim3((unsigned)((ngroups + kBpWaves - 1) / kBpWaves)), dim3(kWorkgroup), 0, s,
 	                   groups, (uint32_t)ngroups, d_bitmap, d_group_cnt);
 	launch_exclusive_prefix(s, d_group_cnt, ngroups, d_group_off, d_block_tot, d_total);
 	BpGatherArgs a;
 	const dim3 grid = bp_wave_grid(ngroups, 8, a.run);
-	a.blocks = static_cast<const uint8_t *>(d_blocks);
+	a.blocks = static_cast<const uint8_t *>(col.d_blocks);
 	a.bitmap = d_bitmap;
-	a.tmask = type_mask(type_size);
+	a.tmask = type_words(col).tmask;
 	a.group_cnt = d_group_cnt;
 	a.group_off = d_group_off;
-	return dispatch_size(type_size, [&](auto tag) {
+	return dispatch_size(col.type_size, [&](auto tag) {
 		using U = decltype(tag);
-		if (d_out_ids) hipLaunchKernelGGL((k_bp_gather<U, true>), grid, dim3(kWorkgroup), 0, s, groups, a, static_cast<U *>(d_out), d_out_ids);
-		else hipLaunchKernelGGL((k_bp_gather<U, false>), grid, dim3(kWorkgroup), 0, s, groups, a, static_cast<U *>(d_out), d_out_ids);
+		dispatch_flags([&](auto IDS) {
+			hipLaunchKernelGGL((k_bp_gather<U, IDS.value>), grid, dim3(kWorkgroup), 0, s, groups, a, static_cast<U *>(d_out),
+			                   d_out_ids);
+		}, d_out_ids != nullptr);
 		return hipGetLastError();
 	});
 }
 
-hipError_t launch_gather_selected(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs,
-                                  const TileRef *d_tiles, uint64_t ntiles, const uint64_t *d_words,
-                                  const TileRec *d_recs, const uint64_t *d_bitmap, uint64_t bitmap_words, uint32_t *d_tile_cnt,
-                                  uint64_t *d_tile_off, uint64_t *d_block_tot, void *d_out, uint64_t *d_out_ids,
-                                  uint64_t *d_total) {
+hipError_t launch_gather_selected(hipStream_t s, const Column &col, const TileRef *d_tiles, uint64_t ntiles,
+                                  const TileRec *d_recs, const uint64_t *d_bitmap, uint64_t bitmap_words,
+                                  uint32_t *d_tile_cnt, uint64_t *d_tile_off, uint64_t *d_block_tot, void *d_out,
+                                  uint64_t *d_out_ids, uint64_t *d_total) {
 	if (ntiles == 0) return hipMemsetAsync(d_total, 0, sizeof(uint64_t), s);
-	return dispatch_size(type_size, [&](auto tag) {
+	const adac_segment_desc *d_descs = col.d_descs;
+	const uint64_t *d_words = col.d_words;
+	return dispatch_size(col.type_size, [&](auto tag) {
 		using U = decltype(tag);
 		const unsigned per = kWorkgroup / 64;
 		hipLaunchKernelGGL(k_tile_popc<U>, dim3((unsigned)((ntiles + per - 1) / per)), dim3(kWorkgroup), 0, s, d_descs,
