@@ -1118,6 +1118,142 @@ def q4_packed(adac, n_orders=15_000_000):
     return out
 
 
+Q18_QUANTITY = 300   # HAVING SUM(l_quantity) > 300
+
+
+def q18_packed(adac, n_orders=15_000_000):
+    """TPC-H Q18's aggregate on packed columns: SUM(l_quantity) GROUP BY l_orderkey as adac_scan_group_sum_dense over the
+    dense domain of the order keys, then HAVING SUM > 300 and the orders: adac_encode of the sums as a UINT64 layout,
+    adac_scan_select_between for > 300, and that bitmap as the d_set of adac_scan_select_member over o_orderkey; the
+    qualifying orders checked against numpy before and after the timing.  Synthetic tables at SF10 size as in q4_packed:
+    o_orderkey sparse-increasing (8 keys used of every 32), one to seven lineitems per order, l_quantity 1 .. 50.
+    Interleaved in the same process: the sum with and without d_counts at group_dense_combine 1 and 0, the count entry,
+    adac_scan_build_member over the same key column and adac_unpack of the two columns (the comparison points), the same
+    sum with the rows shuffled (no runs), GROUP BY l_shipdate over all days, and over one year of days (a domain of 365
+    keys: the window form) with the window on and off (group_dense_window)."""
+    ctx = adac.Context(0)
+    rng = np.random.default_rng(1998)
+    idx = np.arange(n_orders, dtype=np.int64)
+    o_orderkey = ((idx // 8) * 32 + idx % 8 + 1).astype(np.int32)
+    del idx
+    l_orderkey = np.repeat(o_orderkey, rng.integers(1, 8, size=n_orders))
+    n = len(l_orderkey)
+    cols = lineitem(rng, n, ("l_quantity", "l_shipdate"))
+    perm = rng.permutation(n)
+    oc, lc = adac.appender_segment_counts(n_orders, 4), adac.appender_segment_counts(n, 4)
+    okey = encode_column(adac, ctx, o_orderkey, oc)
+    lkey, qty = encode_column(adac, ctx, l_orderkey, lc), encode_column(adac, ctx, cols["l_quantity"], lc)
+    skey, sqty = encode_column(adac, ctx, l_orderkey[perm], lc), encode_column(adac, ctx, cols["l_quantity"][perm], lc)
+    ship = encode_column(adac, ctx, cols["l_shipdate"], lc)
+    base, span = 1, int(o_orderkey.max())
+    day0, days = 8036, 10562 - 8036
+    year0, year = 8766, 365   # 1994
+    sw, ow, lseg, oseg = (span + 63) // 64, (n_orders + 63) // 64, len(lc), len(oc)
+    d_sums, d_counts, d_sums2 = ctx.alloc(span * 8), ctx.alloc(span * 8), ctx.alloc(span * 8)
+    d_day_sums = ctx.alloc(days * 8)
+    d_set, d_lcnt, d_ocnt = ctx.alloc(sw * 8 + 8), ctx.alloc(lseg * 8), ctx.alloc(oseg * 8)
+    bm_o = ctx.alloc(ow * 8 + 8)
+    d_out = ctx.alloc(n * 4 + 64)
+    sc = adac.appender_segment_counts(span, 8)
+    slay = adac.Layout(ctx, np.uint64, sc)
+    d_swords, d_scnt = ctx.alloc(slay.max_arena_words * 8 + 16).zero(), ctx.alloc(len(sc) * 8)
+
+    def sums(k=lkey, v=qty, counts=None, out=d_sums):
+        k.lay.scan_group_sum_dense(k.words, v.lay, v.words, base, span, out, counts, d_lcnt)
+
+    def chain():
+        sums()
+        slay.encode(d_sums, d_swords)
+        slay.scan_select_between(d_swords, Q18_QUANTITY + 1, 0xFFFFFFFFFFFFFFFF, d_set, d_scnt)
+        okey.lay.scan_select_member(okey.words, d_set, base, span, bm_o, d_ocnt)
+
+    want_sums = np.bincount(l_orderkey - base, weights=cols["l_quantity"], minlength=span).astype(np.uint64)
+    large = want_sums[(o_orderkey - base).astype(np.int64)] > Q18_QUANTITY
+    want_days = np.bincount(cols["l_shipdate"] - day0, weights=cols["l_quantity"], minlength=days).astype(np.uint64)
+
+    def parity(when):
+        chain()
+        ctx.sync()
+        assert np.array_equal(d_sums.download(np.uint64, span), want_sums), "Q18 sums parity (%s)" % when
+        got = np.unpackbits(bm_o.download(np.uint64, ow).view(np.uint8), bitorder="little")[:n_orders].astype(bool)
+        assert np.array_equal(got, large), "Q18 orders parity (%s)" % when
+        sums(skey, sqty, None, d_sums2)
+        ship.lay.scan_group_sum_dense(ship.words, qty.lay, qty.words, day0, days, d_day_sums, None, d_lcnt)
+        ctx.sync()
+        assert np.array_equal(d_sums2.download(np.uint64, span), want_sums), "shuffled sums parity (%s)" % when
+        assert np.array_equal(d_day_sums.download(np.uint64, days), want_days), "ship date sums parity (%s)" % when
+
+    parity("before timing")
+
+    def knob(name, value, fn):
+        def run():
+            adac.set_tuning(name, value)
+            fn()
+            adac.set_tuning(name, 1)
+        return run
+
+    def by_day(d0, nd):
+        return lambda: ship.lay.scan_group_sum_dense(ship.words, qty.lay, qty.words, d0, nd, d_day_sums, None, d_lcnt)
+
+    entries = [("q18_chain", chain),
+               ("sum_dense", sums),
+               ("sum_dense_no_combine", knob("group_dense_combine", 0, sums)),
+               ("sum_dense_with_counts", lambda: sums(counts=d_counts)),
+               ("sum_dense_with_counts_no_combine", knob("group_dense_combine", 0, lambda: sums(counts=d_counts))),
+               ("count_dense", lambda: lkey.lay.scan_group_count_dense(lkey.words, base, span, d_counts, d_lcnt)),
+               ("build_member", lambda: lkey.lay.scan_build_member(lkey.words, base, span, d_set, d_lcnt)),
+               ("clear_sums", lambda: d_sums2.zero()),
+               ("unpack_keys", lambda: lkey.lay.unpack(lkey.words, d_out)),
+               ("unpack_values", lambda: qty.lay.unpack(qty.words, d_out)),
+               ("sum_dense_shuffled", lambda: sums(skey, sqty, None, d_sums2)),
+               ("sum_dense_shuffled_no_combine", knob("group_dense_combine", 0, lambda: sums(skey, sqty, None, d_sums2))),
+               ("shipdate_all_days", by_day(day0, days)),
+               ("shipdate_one_year_window", by_day(year0, year)),
+               ("shipdate_one_year_direct", knob("group_dense_window", 0, by_day(year0, year)))]
+    samples = timed_interleaved(ctx, entries)
+    parity("after timing")
+    med = {k: float(np.median(x)) for k, x in samples.items()}
+    unpack = med["unpack_keys"] + med["unpack_values"]
+    kind32 = (4, True)
+
+    def census(k, v, b, nb):
+        fs = forms.dense_form_groups(k.descs, kind32, b, nb, v.descs, kind32)
+        return {f: fs.count(f) for f in sorted(set(fs) - {None})}
+
+    def cell(call):
+        return {"ms": med[call], "over_unpack_of_both": med[call] / unpack, "over_build_member": med[call] / med["build_member"],
+                "rows_per_ns": n / (med[call] * 1e6)}
+
+    out = {"orders": n_orders, "lineitems": n, "key_span": span, "sums_bytes": span * 8,
+           "orders_over_%d" % Q18_QUANTITY: int(large.sum()),
+           "widths": {"l_orderkey": lkey.widths, "l_quantity": qty.widths, "l_orderkey_shuffled": skey.widths,
+                      "l_shipdate": ship.widths, "o_orderkey": okey.widths},
+           "packed_bytes": {"l_orderkey": lkey.nbytes, "l_quantity": qty.nbytes, "l_shipdate": ship.nbytes},
+           "segments_by_form": {"l_orderkey": census(lkey, qty, base, span), "shuffled": census(skey, sqty, base, span),
+                                "shipdate_all_days": census(ship, qty, day0, days),
+                                "shipdate_one_year": census(ship, qty, year0, year)},
+           "ms": med, "q18_chain_ms": med["q18_chain"], "unpack_of_both_ms": unpack,
+           "sum_dense": cell("sum_dense"), "sum_dense_no_combine": cell("sum_dense_no_combine"),
+           "sum_dense_with_counts": cell("sum_dense_with_counts"), "count_dense": cell("count_dense"),
+           "sum_dense_shuffled": cell("sum_dense_shuffled"), "shipdate_all_days": cell("shipdate_all_days"),
+           "combine_gain_sorted": med["sum_dense_no_combine"] / med["sum_dense"],
+           "combine_gain_shuffled": med["sum_dense_shuffled_no_combine"] / med["sum_dense_shuffled"],
+           "window_gain_one_year": med["shipdate_one_year_direct"] / med["shipdate_one_year_window"],
+           "samples_ms": {k: [round(t, 5) for t in x] for k, x in samples.items()},
+           "note": ("Synthetic orders / lineitem at SF10 size.  Every sum_dense* call includes clearing its key_span-word "
+                    "outputs (clear_sums = one such clear alone).  *_no_combine = group_dense_combine 0 (one atomic per "
+                    "row), shipdate_one_year_direct = group_dense_window 0; build_member = adac_scan_build_member over "
+                    "l_orderkey and the same domain; unpack_* = adac_unpack of the column.  "
+                    "Medians of %d interleaved rounds of %d calls each" % (ROUNDS, INNER))}
+    print("q18_packed chain %.4f ms; sum %.4f (no combine %.4f, with counts %.4f, count %.4f, shuffled %.4f); "
+          "build_member %.4f, unpack of both %.4f; ship date %.4f, one year window %.4f / direct %.4f"
+          % (med["q18_chain"], med["sum_dense"], med["sum_dense_no_combine"], med["sum_dense_with_counts"],
+             med["count_dense"], med["sum_dense_shuffled"], med["build_member"], unpack, med["shipdate_all_days"],
+             med["shipdate_one_year_window"], med["shipdate_one_year_direct"]), file=sys.stderr, flush=True)
+    ctx.close()
+    return out
+
+
 def bitpacking_select_gather(adac, n=59_986_052):
     """Filter -> project on DuckDB's own BITPACKING blocks: adac_bp_unpack_selected (values only, then values + ids) of
     l_extendedprice (int32, FOR), the 6-valued uint8 code and a sorted copy of l_partkey (DELTA_FOR) under five bitmaps
@@ -1532,6 +1668,7 @@ def main():
             "q12_bitpacking": lambda: q12_bitpacking(adac),
             "q12_packed": lambda: q12_packed(adac),
             "q4_packed": lambda: q4_packed(adac),
+            "q18_packed": lambda: q18_packed(adac),
             "bitpacking_select_gather": lambda: bitpacking_select_gather(adac),
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "q1_filtered_packed": lambda: q1_filtered_packed(adac),

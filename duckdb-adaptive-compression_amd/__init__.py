@@ -184,6 +184,8 @@ SIGNATURES = {
     "adac_scan_select_member": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "adac_scan_count_member": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp]),
     "adac_scan_build_member": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "adac_scan_group_sum_dense": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "adac_scan_group_count_dense": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "adac_unpack_selected": (_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "adac_scan_count_between_valid": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "adac_bp_layout_create": (_int, [_vp, _int, _vp, _vp, _vp, _u64, _P(_vp)]),
@@ -644,6 +646,21 @@ class Layout:
         holds the value set_base + t; d_counts: the wanted rows per segment whose value lies in the domain."""
         _check(lib().adac_scan_build_member(self._h, _dptr(d_words), _dptr(d_validity), set_base & NO_MIN, int(set_bits),
                                             _dptr(d_set), _dptr(d_counts)), "adac_scan_build_member")
+
+    def scan_group_sum_dense(self, d_key_words, values, d_value_words, key_base, key_span, d_sums, d_counts=None,
+                             d_seg_rows=None, d_validity=None):
+        """SUM(value), COUNT(*) GROUP BY key over the dense domain [key_base, key_base + key_span - 1], called on the KEY
+        layout: d_sums / d_counts (key_span words each, fully written) are indexed by key - key_base; d_seg_rows: the
+        wanted rows per segment whose key lies in the domain; d_validity in the keys' element space."""
+        _check(lib().adac_scan_group_sum_dense(self._h, _dptr(d_key_words), values._h, _dptr(d_value_words),
+                                               _dptr(d_validity), key_base & NO_MIN, int(key_span), _dptr(d_sums),
+                                               _dptr(d_counts), _dptr(d_seg_rows)), "adac_scan_group_sum_dense")
+
+    def scan_group_count_dense(self, d_key_words, key_base, key_span, d_counts, d_seg_rows=None, d_validity=None):
+        """The counts of scan_group_sum_dense alone: no value column is read."""
+        _check(lib().adac_scan_group_count_dense(self._h, _dptr(d_key_words), _dptr(d_validity), key_base & NO_MIN,
+                                                 int(key_span), _dptr(d_counts), _dptr(d_seg_rows)),
+               "adac_scan_group_count_dense")
 
     def unpack_selected(self, d_words, d_bitmap, d_out, d_out_ids=None, want_total=True):
         """Values (and optionally element indices) of the rows whose bitmap bit is set, dense, in row order.

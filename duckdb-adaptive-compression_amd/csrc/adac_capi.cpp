@@ -366,6 +366,8 @@ extern "C" int adac_set_tuning(const char *name, int value) {
 	    {"group_product_rw", &adac::Tuning::group_product_rw, INT_MIN},
 	    {"group_product3_rw", &adac::Tuning::group_product3_rw, INT_MIN},
 	    {"group_q1_rw", &adac::Tuning::group_q1_rw, INT_MIN},
+	    {"group_dense_combine", &adac::Tuning::group_dense_combine, INT_MIN},
+	    {"group_dense_window", &adac::Tuning::group_dense_window, INT_MIN},
 	    {"templated_scan", &adac::Tuning::templated_scan, INT_MIN},
 	    {"scan_tiles_per_wg", &adac::Tuning::scan_tiles_per_wg, 0}, // 0 = by type
 	    {"num_cus", &adac::Tuning::num_cus, 0},                     // 0 = the device's own count
@@ -1253,6 +1255,67 @@ extern "C" adac_status adac_scan_count_member(adac_layout *l, const uint64_t *d_
 extern "C" adac_status adac_scan_build_member(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity,
                                               uint64_t set_base, uint64_t set_bits, uint64_t *d_set, uint64_t *d_counts) {
 	return scan_member(l, d_words, d_validity, d_set, set_base, set_bits, MEMBER_BUILD, nullptr, d_counts);
+}
+
+// Grouped SUM / COUNT by a dense key: what adac_scan_group_sum_dense and adac_scan_group_count_dense (values == null:
+// no value column) share.  Checks the arguments, makes sure `keys` has its scan groups and clears the outputs, whose
+// size comes from key_span (a key layout without segments still gets them zeroed).
+static adac_status scan_group_dense(adac_layout *keys, const uint64_t *d_key_words, bool want_sums, adac_layout *values,
+                                    const uint64_t *d_value_words, const uint64_t *d_validity, uint64_t key_base,
+                                    uint64_t key_span, uint64_t *d_sums, uint64_t *d_counts, uint64_t *d_seg_rows) {
+	if (!keys || (want_sums && !values)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (!want_sums) { // one column: the keys stand in for the values, which nothing reads
+		values = keys;
+		d_value_words = d_key_words;
+	}
+	const ColumnArg cols[] = {{keys, d_key_words}, {values, d_value_words}};
+	if (!same_rows(cols)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (key_span < 1ull || key_span > (1ull << 32)) return ADAC_ERR_INVALID_ARGUMENT;
+	// the domain stays inside the type (scan_member's rule)
+	const adac::TypeWords t = adac::type_words(*keys);
+	if (key_base > t.tmask || t.tmask - (key_base ^ t.sbit) < key_span - 1ull) return ADAC_ERR_INVALID_ARGUMENT;
+	if (want_sums ? !d_sums : !d_counts) return ADAC_ERR_INVALID_ARGUMENT;
+	const struct {
+		const uint64_t *p;
+		uint64_t n;
+	} bufs[] = {{want_sums ? d_sums : nullptr, key_span},
+	            {d_counts, key_span},
+	            {d_seg_rows, keys->nseg},
+	            {d_validity, (keys->value_span + 63) / 64}};
+	for (size_t i = 0; i < 4; i++) {
+		for (size_t j = i + 1; j < 4; j++) {
+			if (words_overlap(bufs[i].p, bufs[i].n, bufs[j].p, bufs[j].n)) return ADAC_ERR_INVALID_ARGUMENT;
+		}
+	}
+	ADAC_HIP(hipSetDevice(keys->ctx->device));
+	hipStream_t stream = keys->ctx->stream;
+	if (keys->nseg) {
+		adac_status st = ensure_scan_groups(keys);
+		if (st != ADAC_OK) return st;
+	}
+	// every run of rows adds its part: the outputs start from zero (this also writes the keys without rows)
+	if (want_sums) ADAC_HIP(hipMemsetAsync(d_sums, 0, key_span * sizeof(uint64_t), stream));
+	if (d_counts) ADAC_HIP(hipMemsetAsync(d_counts, 0, key_span * sizeof(uint64_t), stream));
+	if (d_seg_rows && keys->nseg) ADAC_HIP(hipMemsetAsync(d_seg_rows, 0, keys->nseg * sizeof(uint64_t), stream));
+	if (keys->nseg == 0) return ADAC_OK;
+	ADAC_HIP(adac::launch_group_dense(stream, cols[0], cols[1], scan_work(keys), d_validity, key_base, key_span,
+	                                  want_sums ? d_sums : nullptr, d_counts, d_seg_rows));
+	return ADAC_OK;
+}
+
+extern "C" adac_status adac_scan_group_sum_dense(adac_layout *keys, const uint64_t *d_key_words, adac_layout *values,
+                                                 const uint64_t *d_value_words, const uint64_t *d_validity,
+                                                 uint64_t key_base, uint64_t key_span, uint64_t *d_sums,
+                                                 uint64_t *d_counts, uint64_t *d_seg_rows) {
+	return scan_group_dense(keys, d_key_words, true, values, d_value_words, d_validity, key_base, key_span, d_sums, d_counts,
+	                        d_seg_rows);
+}
+
+extern "C" adac_status adac_scan_group_count_dense(adac_layout *keys, const uint64_t *d_key_words,
+                                                   const uint64_t *d_validity, uint64_t key_base, uint64_t key_span,
+                                                   uint64_t *d_counts, uint64_t *d_seg_rows) {
+	return scan_group_dense(keys, d_key_words, false, nullptr, nullptr, d_validity, key_base, key_span, nullptr, d_counts,
+	                        d_seg_rows);
 }
 
 // SUM(value), COUNT(*) GROUP BY key over two packed columns of one table (Q1's shape, TPCH_runtime.txt:2-6)

@@ -1976,6 +1976,7 @@ bool dispatch_int(int v, F &&f) {
 #include "adac_sum_product.inl"
 #include "adac_scan_compare.inl"
 #include "adac_scan_member.inl"
+#include "adac_group_dense.inl"
 #include "adac_group_product.inl"
 #include "adac_group_product3.inl"
 #include "adac_group_q1.inl"
@@ -2303,6 +2304,23 @@ hipError_t launch_scan_member_build(hipStream_t s, const Column &col, const Scan
 		                   work.d_scan_groups, col.d_words, dom, d_validity, reinterpret_cast<uint32_t *>(d_set),
 		                   reinterpret_cast<unsigned long long *>(d_counts));
 	}, d_validity != nullptr);
+	return hipGetLastError();
+}
+
+hipError_t launch_group_dense(hipStream_t s, const Column &keys, const Column &values, const ScanWork &work,
+                              const uint64_t *d_validity, uint64_t key_base, uint64_t key_span, uint64_t *d_sums,
+                              uint64_t *d_counts, uint64_t *d_seg_rows) {
+	if (work.nscan_groups == 0) return hipSuccess;
+	const MemberDomain dom = member_domain(keys, key_base, key_span);
+	const TypeWords vt = d_sums ? type_words(values) : TypeWords {0ull, 0ull};
+	const uint32_t knobs = (g_tuning.group_dense_combine != 0 ? 1u : 0u) | (g_tuning.group_dense_window != 0 ? 2u : 0u);
+	dispatch_flags([&](auto V, auto SUM) {
+		hipLaunchKernelGGL((k_group_dense<V.value, SUM.value>), dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
+		                   work.d_scan_groups, keys.d_words, SUM.value ? values.d_descs : nullptr,
+		                   SUM.value ? values.d_words : nullptr, dom, vt.tmask, vt.sbit, d_validity,
+		                   reinterpret_cast<unsigned long long *>(d_sums), reinterpret_cast<unsigned long long *>(d_counts),
+		                   reinterpret_cast<unsigned long long *>(d_seg_rows), knobs);
+	}, d_validity != nullptr, d_sums != nullptr);
 	return hipGetLastError();
 }
 

@@ -18,6 +18,9 @@ single values), so that the descriptors alone decide every row.  compare_form_gr
 
 The member scans (k_scan_member / k_scan_member_build, csrc/adac_scan_member.inl) choose a reader and a set access per
 segment from the descriptor, the type and the domain (set_base, set_bits): member_form_groups mirrors member_plan.
+
+The grouped SUM / COUNT by a dense key (k_group_dense, csrc/adac_group_dense.inl) chooses a reader and an accumulator
+per key segment the same way, the walk also asking the value column: dense_form_groups mirrors dense_plan.
 """
 from itertools import repeat
 
@@ -147,4 +150,37 @@ def member_form_groups(descs, type, set_base, set_bits):
         lo, hi = max(bmin - dlo, 0), min(btop, dhi) - dlo + 1   # set bits [lo, hi) are what the segment can reach
         reader = "walk" if value_ok(d, type, 4, False) else "staged"
         out.append(reader + ("-slice" if hi - lo <= MEMBER_SLICE_BITS else "-direct"))
+    return out
+
+
+DENSE_WINDOW = 512   # kDenseWindow
+
+
+def dense_form_groups(descs_k, k_type, key_base, key_span, descs_v=None, v_type=None):
+    """adac_scan_group_sum_dense (descs_v / v_type given) / adac_scan_group_count_dense: dense_plan, per segment
+    "header", "walk-window", "walk-direct", "staged-window" or "staged-direct" (every scan group of a segment takes the
+    same form); None for a segment without rows.  member_plan's rule with DENSE_WINDOW indices for the window, the walk
+    also asking the value column for 1 <= w <= 32, a frame and count * w < 2^31.  Types: (size in bytes, signed);
+    key_base: a bit pattern of the key type."""
+    size, signed = k_type
+    sbit = (1 << (8 * size - 1)) if signed else 0
+    dlo = (int(key_base) ^ sbit)            # biased by the sign bit every interval is one of unsigned numbers
+    dhi = dlo + int(key_span) - 1
+    out = []
+    for d, dv in zip(descs_k, descs_v if descs_v is not None else repeat(None)):
+        if int(d["count"]) == 0:
+            out.append(None)
+            continue
+        m = frame(d, size, signed)
+        if m is None:
+            out.append("staged-direct")
+            continue
+        bmin = m + sbit
+        btop = bmin + (1 << int(d["width"])) - 1
+        if btop < dlo or dhi < bmin:
+            out.append("header")
+            continue
+        lo, hi = max(bmin - dlo, 0), min(btop, dhi) - dlo + 1   # indices [lo, hi) are what the segment can reach
+        walk = value_ok(d, k_type, 4, False) and (dv is None or value_ok(dv, v_type, 1, False))
+        out.append(("walk" if walk else "staged") + ("-window" if hi - lo <= DENSE_WINDOW else "-direct"))
     return out

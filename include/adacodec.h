@@ -141,7 +141,8 @@ uint32_t adac_tile_values(int physical_type);
 /* Launch-shape knobs for in-process A/B measurement: "templated_scan" (0/1), "scan_tiles_per_wg" (tiles per fused-scan
  * workgroup; 0 = chosen by type), "num_cus" (0 = the device's own count), "single_pass_encode" (0 = analyze + plan +
  * pack as three kernels), "encode_big_image", "encode_publish_ahead", "scan_cells", "tile_records", "gather_compact",
- * "group_sum_wide", "group_sum_rw", "group_product_rw", "group_product3_rw", "group_q1_rw", "sel_debug": the table in
+ * "group_sum_wide", "group_sum_rw", "group_product_rw", "group_product3_rw", "group_q1_rw", "group_dense_combine",
+ * "group_dense_window", "sel_debug": the table in
  * adac_set_tuning is the full list, Tuning in
  * csrc/adac_internal.h says what each does.  Decoded values, packed words, widths and mins never depend on them.  One
  * knob changes WHERE adac_encode puts a segment in the arena: "encode_placement" 1 hands out arena space in order of
@@ -560,6 +561,44 @@ adac_status adac_scan_count_member(adac_layout *l, const uint64_t *d_words, cons
                                    const uint64_t *d_set, uint64_t set_base, uint64_t set_bits, uint64_t *d_counts);
 adac_status adac_scan_build_member(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity,
                                    uint64_t set_base, uint64_t set_bits, uint64_t *d_set, uint64_t *d_counts);
+
+/* SUM(value), COUNT(*) GROUP BY a DENSE INTEGER KEY of any cardinality — TPC-H Q18's SUM(l_quantity) GROUP BY
+ * l_orderkey, Q13's COUNT(*) GROUP BY o_custkey, Q3 / Q10's revenue per order or customer, any GROUP BY on a date — on
+ * the packed bytes of both columns, without a hash table: the results are arrays indexed by the key.  Called on the KEY
+ * layout.  The domain is [key_base, key_base + key_span - 1] in the key type's own order, key_base a bit pattern of the
+ * key type, zero-extended, 1 <= key_span <= 2^32, the domain inside the type: adac_scan_build_member's rule.  A key's
+ * index is the member scans' t = (bits(k) ^ sbit) - (bits(key_base) ^ sbit); the key is in the domain iff t < key_span.
+ * A row is wanted iff its bit is set in d_validity, indexed in the KEYS' element space (the keys' val_off + row; NULL:
+ * every row); the value layout's offsets play no part.  Bits of elements that no segment covers never influence a
+ * result, no mask word outside ceil(value_span(keys) / 64) is read, and a bitmap that any select scan wrote on a layout
+ * with the keys' offsets passes straight in.
+ * d_sums[t] = the sum of widen(value) mod 2^64 over the wanted rows whose key has index t, each value widened by the
+ * value column's own signedness (adac_scan_sum's rule); d_counts[t] = the number of those rows.  Both hold key_span
+ * words and are fully written by the call: the caller clears nothing.  d_counts may be NULL in the sum entry.
+ * d_seg_rows[seg] = the wanted rows of the segment whose key lies in the domain (adac_scan_build_member's d_counts):
+ * nseg words, written for segments without rows too; may be NULL.  Wanted rows with a key outside the domain contribute
+ * nowhere.  Because d_sums is a dense uint64 array indexed by key, adac_encode + adac_scan_select_between over it give a
+ * bitmap that is bit for bit a member set over the same domain: the d_set of adac_scan_select_member on the other
+ * table's key (Q18's HAVING SUM(l_quantity) > 300, then the orders).
+ * adac_scan_sum_product's pair rules hold: one context for both layouts and the same row count per segment; types,
+ * widths, placements, encode rules and value offsets may differ; values == keys with the same words is legal.
+ * ADAC_ERR_INVALID_ARGUMENT, on the host before anything is enqueued (the call then writes nothing): a NULL layout;
+ * layouts on different contexts; per-segment counts that differ; key_span outside 1 ... 2^32 or a domain that leaves the
+ * type; NULL d_sums (sum entry) or NULL d_counts (count entry); a NULL or not 16-byte aligned words pointer while there
+ * are rows; any two of d_sums, d_counts, d_seg_rows, d_validity overlapping.  A key layout without segments returns
+ * ADAC_OK and still zero-fills d_sums and d_counts: their size comes from key_span.
+ * Both calls enqueue on the context's stream and synchronise no more than adac_scan_build_member does.
+ * A scan group whose key segment is packed against a frame of reference that stays inside the type, with
+ * [frame, frame + 2^width - 1] apart from the domain, is decided from the descriptor: no packed word of either column
+ * and no mask word is read.  A key segment whose interval reaches at most 512 indices adds up in on-chip memory.  A
+ * lane adds up each run of equal keys among its consecutive rows before it touches memory (sorted keys: one atomic per
+ * run, not per row); the tuning knob "group_dense_combine" 0 turns that off, results never depend on it. */
+adac_status adac_scan_group_sum_dense(adac_layout *keys, const uint64_t *d_key_words, adac_layout *values,
+                                      const uint64_t *d_value_words, const uint64_t *d_validity, uint64_t key_base,
+                                      uint64_t key_span, uint64_t *d_sums, uint64_t *d_counts, uint64_t *d_seg_rows);
+/* the counts alone: no value column is read */
+adac_status adac_scan_group_count_dense(adac_layout *keys, const uint64_t *d_key_words, const uint64_t *d_validity,
+                                        uint64_t key_base, uint64_t key_span, uint64_t *d_counts, uint64_t *d_seg_rows);
 
 /* Materialise only the selected rows: d_out receives, densely and in row order (segment by segment), the values of
  * the rows whose bit is set in d_bitmap (the result of adac_scan_select_between, or any mask over the element index
