@@ -1254,6 +1254,213 @@ def q18_packed(adac, n_orders=15_000_000):
     return out
 
 
+Q5_SUPPLIERS, Q5_NATIONS = 100_000, 25
+Q5_REGION = (8, 9, 12, 18, 21)        # the nations of one region (ASIA)
+Q5_DATES = (8766, 9130)               # o_orderdate in 1994
+
+
+def q5_packed(adac, n=59_986_052, n_orders=15_000_000):
+    """TPC-H Q5's aggregate on packed columns: SUM(l_extendedprice), COUNT(*) GROUP BY the nation of the supplier behind
+    l_suppkey, as adac_scan_group_sum_mapped through a 100 000-byte supplier -> nation map, checked against numpy before
+    and after the timing.  Synthetic tables at SF10 size: 60 M lineitems, l_suppkey uniform in 1 .. 100 000,
+    l_extendedprice; a map of 25 nation codes, and a second map where the suppliers outside five nations carry 255 (the
+    region filter: four rows in five leave through the overflow entry).  Interleaved in the same process: the sum with
+    and without d_counts, the count entry, both maps, group_mapped_copies 0 and 1; the sorted-key case, l_orderkey as in
+    q18_packed against a 60 M-byte order -> nation map that adac_scan_build_map builds from the orders table under a date
+    bitmap (that build timed on its own), on the rows as they are and shuffled; and the comparison points, never the code
+    under test: adac_unpack of the two columns, adac_scan_group_sum_dense over the same keys (what a caller had to use
+    before; its host-side fold through the map is not timed, which favours it) and adac_scan_group_sum_valid over a
+    pre-materialised uint8 code column (the same bins without a look-up: the floor)."""
+    ctx = adac.Context(0)
+    rng = np.random.default_rng(1995)
+    ng = Q5_NATIONS
+    cols = lineitem(rng, n, ("l_extendedprice",))
+    l_suppkey = rng.integers(1, Q5_SUPPLIERS + 1, size=n).astype(np.int32)
+    s_nation = rng.integers(0, ng, size=Q5_SUPPLIERS).astype(np.uint8)
+    s_region = np.where(np.isin(s_nation, Q5_REGION), s_nation, 255).astype(np.uint8)
+    lc = adac.appender_segment_counts(n, 4)
+    price, supp = encode_column(adac, ctx, cols["l_extendedprice"], lc), encode_column(adac, ctx, l_suppkey, lc)
+    code_all = encode_column(adac, ctx, s_nation[l_suppkey - 1], lc)   # the pre-materialised code columns
+    code_reg = encode_column(adac, ctx, s_region[l_suppkey - 1], lc)
+    # the sorted-key case: orders and their lineitems as in q18_packed, the nation of the order's customer per order
+    idx = np.arange(n_orders, dtype=np.int64)
+    o_orderkey = ((idx // 8) * 32 + idx % 8 + 1).astype(np.int32)
+    del idx
+    l_orderkey = np.repeat(o_orderkey, rng.integers(1, 8, size=n_orders))
+    no = len(l_orderkey)
+    o_nation = rng.integers(0, ng, size=n_orders).astype(np.uint8)
+    o_orderdate = rng.integers(8036, 10562, size=n_orders).astype(np.int32)
+    o_price = LINEITEM["l_extendedprice"](rng, no)
+    perm = rng.permutation(no)
+    oc, olc = adac.appender_segment_counts(n_orders, 4), adac.appender_segment_counts(no, 4)
+    okey, onat = encode_column(adac, ctx, o_orderkey, oc), encode_column(adac, ctx, o_nation, oc)
+    odate = encode_column(adac, ctx, o_orderdate, oc)
+    lkey, lprice = encode_column(adac, ctx, l_orderkey, olc), encode_column(adac, ctx, o_price, olc)
+    skey, sprice = encode_column(adac, ctx, l_orderkey[perm], olc), encode_column(adac, ctx, o_price[perm], olc)
+    obase, ospan = 1, int(o_orderkey.max())
+
+    def map_buffer(codes):
+        buf = np.full((len(codes) + 7) // 8 * 8, 255, dtype=np.uint8)
+        buf[:len(codes)] = codes
+        return ctx.upload(buf)
+
+    d_map_all, d_map_reg = map_buffer(s_nation), map_buffer(s_region)
+    d_omap = ctx.alloc((ospan + 7) // 8 * 8)
+    ow, lseg, oseg, olseg = (n_orders + 63) // 64, len(lc), len(oc), len(olc)
+    bm_o, d_ocnt = ctx.alloc(ow * 8 + 8), ctx.alloc(oseg * 8)
+    d_s, d_c, d_s2, d_c2 = (ctx.alloc((ng + 1) * 8) for _ in range(4))
+    d_dense_s, d_dense_c = ctx.alloc(max(Q5_SUPPLIERS, ospan) * 8), ctx.alloc(Q5_SUPPLIERS * 8)
+    d_rows = ctx.alloc(max(lseg, olseg, oseg) * 8)
+    d_out = ctx.alloc(max(n, no) * 4 + 64)
+
+    def mapped(d_map=d_map_all, counts=None, s=d_s):
+        supp.lay.scan_group_sum_mapped(supp.words, price.lay, price.words, d_map, 1, Q5_SUPPLIERS, ng, s, counts, d_rows)
+
+    def count_mapped(d_map=d_map_all):
+        supp.lay.scan_group_count_mapped(supp.words, d_map, 1, Q5_SUPPLIERS, ng, d_c, d_rows)
+
+    def order_select():
+        odate.lay.scan_select_between(odate.words, Q5_DATES[0], Q5_DATES[1], bm_o, d_ocnt)
+
+    def order_build():
+        okey.lay.scan_build_map(okey.words, onat.lay, onat.words, obase, ospan, d_omap, 255, d_rows, bm_o)
+
+    def order_mapped(k=lkey, v=lprice, s=d_s2, c=d_c2):
+        k.lay.scan_group_sum_mapped(k.words, v.lay, v.words, d_omap, obase, ospan, ng, s, c, d_rows)
+
+    def fold(codes, keys, values):
+        g = np.minimum(codes.astype(np.int64), ng)[keys]
+        return (np.bincount(g, weights=values.astype(np.float64), minlength=ng + 1).astype(np.uint64),
+                np.bincount(g, minlength=ng + 1).astype(np.uint64))
+
+    # (sums below 2^53: 60 M rows of at most 10 495 000 add up to 6.3e14, exact in the float64 weights of bincount)
+    want_all, want_reg = (fold(m, l_suppkey - 1, cols["l_extendedprice"]) for m in (s_nation, s_region))
+    year = (o_orderdate >= Q5_DATES[0]) & (o_orderdate <= Q5_DATES[1])
+    omap = np.full(ospan, 255, dtype=np.uint8)
+    omap[(o_orderkey[year] - obase).astype(np.int64)] = o_nation[year]
+    want_ord = fold(omap, (l_orderkey - obase).astype(np.int64), o_price)
+
+    def outputs(s, c):
+        return s.download(np.uint64, ng + 1), c.download(np.uint64, ng + 1)
+
+    def parity(when):
+        for d_map, want, name in ((d_map_all, want_all, "nations"), (d_map_reg, want_reg, "region")):
+            for copies in (0, 1):
+                adac.set_tuning("group_mapped_copies", copies)
+                mapped(d_map, d_c)
+                count_mapped(d_map)
+                adac.set_tuning("group_mapped_copies", 0)
+                ctx.sync()
+                got = outputs(d_s, d_c)
+                assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), \
+                    "Q5 %s parity, copies %d (%s)" % (name, copies, when)
+        order_select()
+        order_build()
+        ctx.sync()
+        assert np.array_equal(d_omap.download(np.uint8, ospan), omap), "order map parity (%s)" % when
+        for k, v, name in ((lkey, lprice, "sorted"), (skey, sprice, "shuffled")):
+            order_mapped(k, v)
+            ctx.sync()
+            got = outputs(d_s2, d_c2)
+            assert np.array_equal(got[0], want_ord[0]) and np.array_equal(got[1], want_ord[1]), \
+                "Q5 through the orders, %s (%s)" % (name, when)
+
+    parity("before timing")
+
+    def one_copy(fn):
+        def run():
+            adac.set_tuning("group_mapped_copies", 1)
+            fn()
+            adac.set_tuning("group_mapped_copies", 0)
+        return run
+
+    def dense(k, v, b, nb):
+        return lambda: k.lay.scan_group_sum_dense(k.words, v.lay, v.words, b, nb, d_dense_s, None, d_rows)
+
+    def valid(v, k):
+        return lambda: v.lay.scan_group_sum_valid(v.words, k.lay, k.words, None, ng, d_s2, d_c2)
+
+    entries = [("sum_mapped", mapped),
+               ("sum_mapped_with_counts", lambda: mapped(counts=d_c)),
+               ("count_mapped", count_mapped),
+               ("sum_mapped_region", lambda: mapped(d_map_reg)),
+               ("sum_mapped_region_with_counts", lambda: mapped(d_map_reg, d_c)),
+               ("count_mapped_region", lambda: count_mapped(d_map_reg)),
+               ("sum_mapped_one_copy", one_copy(mapped)),
+               ("sum_mapped_region_one_copy", one_copy(lambda: mapped(d_map_reg))),
+               ("unpack_suppkey", lambda: supp.lay.unpack(supp.words, d_out)),
+               ("unpack_price", lambda: price.lay.unpack(price.words, d_out)),
+               ("sum_dense_suppkey", dense(supp, price, 1, Q5_SUPPLIERS)),
+               ("sum_valid_codes", valid(price, code_all)),
+               ("sum_valid_codes_region", valid(price, code_reg)),
+               ("orders_select_dates", order_select),
+               ("orders_build_map", order_build),
+               ("sum_mapped_orderkey", order_mapped),
+               ("sum_mapped_orderkey_shuffled", lambda: order_mapped(skey, sprice)),
+               ("unpack_orderkey", lambda: lkey.lay.unpack(lkey.words, d_out)),
+               ("unpack_order_price", lambda: lprice.lay.unpack(lprice.words, d_out)),
+               ("sum_dense_orderkey", dense(lkey, lprice, obase, ospan)),
+               ("sum_dense_orderkey_shuffled", dense(skey, sprice, obase, ospan))]
+    samples = timed_interleaved(ctx, entries)
+    parity("after timing")
+    med = {k: float(np.median(x)) for k, x in samples.items()}
+    unpack_supp = med["unpack_suppkey"] + med["unpack_price"]
+    unpack_ord = med["unpack_orderkey"] + med["unpack_order_price"]
+    kind32 = (4, True)
+
+    def census(k, v, b, nb):
+        fs = forms.mapped_form_groups(k.descs, kind32, b, nb, v.descs, kind32)
+        return {f: fs.count(f) for f in sorted(set(fs) - {None})}
+
+    def cell(call, rows, unpack, dense_call, floor=None):
+        c = {"ms": med[call], "rows_per_ns": rows / (med[call] * 1e6), "over_unpack_of_both": med[call] / unpack,
+             "over_sum_dense": med[call] / med[dense_call]}
+        if floor:
+            c["over_sum_valid_on_codes"] = med[call] / med[floor]
+        return c
+
+    s5 = ("sum_dense_suppkey",)
+    out = {"lineitems": n, "suppliers": Q5_SUPPLIERS, "nations": ng, "orders": n_orders, "order_lineitems": no,
+           "order_key_span": ospan, "orders_in_dates": int(year.sum()),
+           "rows_kept_by_region": int(want_reg[1][:ng].sum()),
+           "widths": {"l_suppkey": supp.widths, "l_extendedprice": price.widths, "l_orderkey": lkey.widths,
+                      "l_orderkey_shuffled": skey.widths, "o_orderkey": okey.widths},
+           "packed_bytes": {"l_suppkey": supp.nbytes, "l_extendedprice": price.nbytes, "l_orderkey": lkey.nbytes},
+           "segments_by_form": {"l_suppkey": census(supp, price, 1, Q5_SUPPLIERS),
+                                "l_orderkey": census(lkey, lprice, obase, ospan),
+                                "l_orderkey_shuffled": census(skey, sprice, obase, ospan)},
+           "ms": med, "unpack_of_both_ms": {"l_suppkey": unpack_supp, "l_orderkey": unpack_ord},
+           "sum_mapped": cell("sum_mapped", n, unpack_supp, *s5, "sum_valid_codes"),
+           "sum_mapped_with_counts": cell("sum_mapped_with_counts", n, unpack_supp, *s5, "sum_valid_codes"),
+           "count_mapped": cell("count_mapped", n, unpack_supp, *s5),
+           "sum_mapped_region": cell("sum_mapped_region", n, unpack_supp, *s5, "sum_valid_codes_region"),
+           "sum_mapped_region_with_counts": cell("sum_mapped_region_with_counts", n, unpack_supp, *s5,
+                                                 "sum_valid_codes_region"),
+           "sum_mapped_orderkey": cell("sum_mapped_orderkey", no, unpack_ord, "sum_dense_orderkey"),
+           "sum_mapped_orderkey_shuffled": cell("sum_mapped_orderkey_shuffled", no, unpack_ord,
+                                                "sum_dense_orderkey_shuffled"),
+           "copies_gain": med["sum_mapped_one_copy"] / med["sum_mapped"],
+           "copies_gain_region": med["sum_mapped_region_one_copy"] / med["sum_mapped_region"],
+           "orders_build_map_ms": med["orders_build_map"],
+           "samples_ms": {k: [round(t, 5) for t in x] for k, x in samples.items()},
+           "note": ("Synthetic lineitem / orders at SF10 size.  sum_dense_* = adac_scan_group_sum_dense over the same keys "
+                    "(its host-side fold through the map is not timed); sum_valid_codes* = adac_scan_group_sum_valid over a "
+                    "pre-materialised uint8 code column; *_one_copy = group_mapped_copies 1; unpack_* = adac_unpack of the "
+                    "column; orders_build_map = adac_scan_build_map over o_orderkey / the nation codes under the date "
+                    "bitmap, its %d-byte fill included.  "
+                    "Medians of %d interleaved rounds of %d calls each" % ((ospan + 7) // 8 * 8, ROUNDS, INNER))}
+    print("q5_packed sum_mapped %.4f ms (with counts %.4f, count %.4f; region %.4f; one copy %.4f / %.4f); unpack of both "
+          "%.4f, sum_dense %.4f, sum_valid on codes %.4f / %.4f; through the orders %.4f (shuffled %.4f), unpack %.4f, "
+          "sum_dense %.4f (shuffled %.4f); build_map %.4f"
+          % (med["sum_mapped"], med["sum_mapped_with_counts"], med["count_mapped"], med["sum_mapped_region"],
+             med["sum_mapped_one_copy"], med["sum_mapped_region_one_copy"], unpack_supp, med["sum_dense_suppkey"],
+             med["sum_valid_codes"], med["sum_valid_codes_region"], med["sum_mapped_orderkey"],
+             med["sum_mapped_orderkey_shuffled"], unpack_ord, med["sum_dense_orderkey"],
+             med["sum_dense_orderkey_shuffled"], med["orders_build_map"]), file=sys.stderr, flush=True)
+    ctx.close()
+    return out
+
+
 def bitpacking_select_gather(adac, n=59_986_052):
     """Filter -> project on DuckDB's own BITPACKING blocks: adac_bp_unpack_selected (values only, then values + ids) of
     l_extendedprice (int32, FOR), the 6-valued uint8 code and a sorted copy of l_partkey (DELTA_FOR) under five bitmaps
@@ -1669,6 +1876,7 @@ def main():
             "q12_packed": lambda: q12_packed(adac),
             "q4_packed": lambda: q4_packed(adac),
             "q18_packed": lambda: q18_packed(adac),
+            "q5_packed": lambda: q5_packed(adac),
             "bitpacking_select_gather": lambda: bitpacking_select_gather(adac),
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "q1_filtered_packed": lambda: q1_filtered_packed(adac),

@@ -186,6 +186,9 @@ SIGNATURES = {
     "adac_scan_build_member": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "adac_scan_group_sum_dense": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "adac_scan_group_count_dense": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "adac_scan_group_sum_mapped": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp]),
+    "adac_scan_group_count_mapped": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp]),
+    "adac_scan_build_map": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp]),
     "adac_unpack_selected": (_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "adac_scan_count_between_valid": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "adac_bp_layout_create": (_int, [_vp, _int, _vp, _vp, _vp, _u64, _P(_vp)]),
@@ -661,6 +664,33 @@ class Layout:
         _check(lib().adac_scan_group_count_dense(self._h, _dptr(d_key_words), _dptr(d_validity), key_base & NO_MIN,
                                                  int(key_span), _dptr(d_counts), _dptr(d_seg_rows)),
                "adac_scan_group_count_dense")
+
+    def scan_group_sum_mapped(self, d_key_words, values, d_value_words, d_map, key_base, key_span, ngroups, d_sums,
+                              d_counts=None, d_seg_rows=None, d_validity=None):
+        """SUM(value), COUNT(*) GROUP BY d_map[key - key_base], called on the KEY layout: d_map holds one byte per key of
+        the dense domain [key_base, key_base + key_span - 1] (key_span rounded up to a multiple of 8 bytes, 8-byte
+        aligned); d_sums / d_counts (ngroups + 1 words each, fully written) are indexed by min(code, ngroups);
+        d_seg_rows: the wanted rows per segment whose key lies in the domain; d_validity in the keys' element space."""
+        _check(lib().adac_scan_group_sum_mapped(self._h, _dptr(d_key_words), values._h, _dptr(d_value_words),
+                                                _dptr(d_validity), _dptr(d_map), key_base & NO_MIN, int(key_span),
+                                                int(ngroups), _dptr(d_sums), _dptr(d_counts), _dptr(d_seg_rows)),
+               "adac_scan_group_sum_mapped")
+
+    def scan_group_count_mapped(self, d_key_words, d_map, key_base, key_span, ngroups, d_counts, d_seg_rows=None,
+                                d_validity=None):
+        """The counts of scan_group_sum_mapped alone: no value column is read."""
+        _check(lib().adac_scan_group_count_mapped(self._h, _dptr(d_key_words), _dptr(d_validity), _dptr(d_map),
+                                                  key_base & NO_MIN, int(key_span), int(ngroups), _dptr(d_counts),
+                                                  _dptr(d_seg_rows)), "adac_scan_group_count_mapped")
+
+    def scan_build_map(self, d_key_words, codes, d_code_words, key_base, key_span, d_map, fill=255, d_seg_rows=None,
+                       d_validity=None):
+        """The build side, called on the dimension table's KEY layout: d_map (key_span rounded up to a multiple of 8
+        bytes, fully written) = `fill` everywhere, except d_map[key - key_base] = min(code, 255) for every row wanted by
+        d_validity whose key lies in the domain; `codes`: a Layout over the same rows."""
+        _check(lib().adac_scan_build_map(self._h, _dptr(d_key_words), codes._h, _dptr(d_code_words), _dptr(d_validity),
+                                         key_base & NO_MIN, int(key_span), int(fill), _dptr(d_map), _dptr(d_seg_rows)),
+               "adac_scan_build_map")
 
     def unpack_selected(self, d_words, d_bitmap, d_out, d_out_ids=None, want_total=True):
         """Values (and optionally element indices) of the rows whose bitmap bit is set, dense, in row order.

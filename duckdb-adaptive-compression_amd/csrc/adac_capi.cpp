@@ -368,6 +368,7 @@ extern "C" int adac_set_tuning(const char *name, int value) {
 	    {"group_q1_rw", &adac::Tuning::group_q1_rw, INT_MIN},
 	    {"group_dense_combine", &adac::Tuning::group_dense_combine, INT_MIN},
 	    {"group_dense_window", &adac::Tuning::group_dense_window, INT_MIN},
+	    {"group_mapped_copies", &adac::Tuning::group_mapped_copies, 0}, // 0 = as many as fit
 	    {"templated_scan", &adac::Tuning::templated_scan, INT_MIN},
 	    {"scan_tiles_per_wg", &adac::Tuning::scan_tiles_per_wg, 0}, // 0 = by type
 	    {"num_cus", &adac::Tuning::num_cus, 0},                     // 0 = the device's own count
@@ -1316,6 +1317,116 @@ extern "C" adac_status adac_scan_group_count_dense(adac_layout *keys, const uint
                                                    uint64_t *d_counts, uint64_t *d_seg_rows) {
 	return scan_group_dense(keys, d_key_words, false, nullptr, nullptr, d_validity, key_base, key_span, nullptr, d_counts,
 	                        d_seg_rows);
+}
+
+// Grouped SUM / COUNT by a code looked up through a dense key, and the scan that builds the map.  What the three entry
+// points share: the pair rules, the domain (scan_member's rule) and the map's allocation, key_span rounded up to whole
+// 64-bit words, 8-byte aligned.
+static bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+static bool mapped_domain_ok(adac_layout *keys, uint64_t key_base, uint64_t key_span) {
+	if (key_span < 1ull || key_span > (1ull << 32)) return false;
+	const adac::TypeWords t = adac::type_words(*keys);
+	return key_base <= t.tmask && t.tmask - (key_base ^ t.sbit) >= key_span - 1ull;
+}
+
+struct WordRange {
+	const uint64_t *p;
+	uint64_t n;
+};
+template <size_t N>
+static bool any_overlap(const WordRange (&bufs)[N]) {
+	for (size_t i = 0; i < N; i++) {
+		for (size_t j = i + 1; j < N; j++) {
+			if (words_overlap(bufs[i].p, bufs[i].n, bufs[j].p, bufs[j].n)) return true;
+		}
+	}
+	return false;
+}
+
+// values == null: no value column (the count entry).  Clears the outputs, whose size comes from ngroups (a key layout
+// without segments still gets them zeroed).
+static adac_status scan_group_mapped(adac_layout *keys, const uint64_t *d_key_words, bool want_sums, adac_layout *values,
+                                     const uint64_t *d_value_words, const uint64_t *d_validity, const uint8_t *d_map,
+                                     uint64_t key_base, uint64_t key_span, uint32_t ngroups, uint64_t *d_sums,
+                                     uint64_t *d_counts, uint64_t *d_seg_rows) {
+	if (!keys || (want_sums && !values)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (!want_sums) { // one column: the keys stand in for the values, which nothing reads
+		values = keys;
+		d_value_words = d_key_words;
+	}
+	const ColumnArg cols[] = {{keys, d_key_words}, {values, d_value_words}};
+	if (!same_rows(cols) || !mapped_domain_ok(keys, key_base, key_span)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (ngroups < 1u || ngroups > 256u || !d_map || !aligned8(d_map)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (want_sums ? !d_sums : !d_counts) return ADAC_ERR_INVALID_ARGUMENT;
+	const uint64_t nout = (uint64_t)ngroups + 1ull, map_words = (key_span + 7ull) / 8ull;
+	const WordRange outs[] = {{want_sums ? d_sums : nullptr, nout},
+	                          {d_counts, nout},
+	                          {d_seg_rows, keys->nseg},
+	                          {d_validity, (keys->value_span + 63) / 64}};
+	if (any_overlap(outs)) return ADAC_ERR_INVALID_ARGUMENT;
+	const uint64_t *map_w = reinterpret_cast<const uint64_t *>(d_map);
+	for (size_t i = 0; i < 3; i++) { // the map and an output
+		if (words_overlap(map_w, map_words, outs[i].p, outs[i].n)) return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	ADAC_HIP(hipSetDevice(keys->ctx->device));
+	hipStream_t stream = keys->ctx->stream;
+	if (keys->nseg) {
+		adac_status st = ensure_scan_groups(keys);
+		if (st != ADAC_OK) return st;
+	}
+	// every workgroup adds its part: the outputs start from zero (this also writes the groups without rows)
+	if (want_sums) ADAC_HIP(hipMemsetAsync(d_sums, 0, nout * sizeof(uint64_t), stream));
+	if (d_counts) ADAC_HIP(hipMemsetAsync(d_counts, 0, nout * sizeof(uint64_t), stream));
+	if (d_seg_rows && keys->nseg) ADAC_HIP(hipMemsetAsync(d_seg_rows, 0, keys->nseg * sizeof(uint64_t), stream));
+	if (keys->nseg == 0) return ADAC_OK;
+	ADAC_HIP(adac::launch_group_mapped(stream, cols[0], cols[1], scan_work(keys), d_validity, d_map, key_base, key_span,
+	                                   ngroups, want_sums ? d_sums : nullptr, d_counts, d_seg_rows));
+	return ADAC_OK;
+}
+
+extern "C" adac_status adac_scan_group_sum_mapped(adac_layout *keys, const uint64_t *d_key_words, adac_layout *values,
+                                                  const uint64_t *d_value_words, const uint64_t *d_validity,
+                                                  const uint8_t *d_map, uint64_t key_base, uint64_t key_span,
+                                                  uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts,
+                                                  uint64_t *d_seg_rows) {
+	return scan_group_mapped(keys, d_key_words, true, values, d_value_words, d_validity, d_map, key_base, key_span, ngroups,
+	                         d_sums, d_counts, d_seg_rows);
+}
+
+extern "C" adac_status adac_scan_group_count_mapped(adac_layout *keys, const uint64_t *d_key_words,
+                                                    const uint64_t *d_validity, const uint8_t *d_map, uint64_t key_base,
+                                                    uint64_t key_span, uint32_t ngroups, uint64_t *d_counts,
+                                                    uint64_t *d_seg_rows) {
+	return scan_group_mapped(keys, d_key_words, false, nullptr, nullptr, d_validity, d_map, key_base, key_span, ngroups,
+	                         nullptr, d_counts, d_seg_rows);
+}
+
+// The build side: the map is filled with `fill` first, pad included, in stream order; the rows then store their codes.
+extern "C" adac_status adac_scan_build_map(adac_layout *keys, const uint64_t *d_key_words, adac_layout *codes,
+                                           const uint64_t *d_code_words, const uint64_t *d_validity, uint64_t key_base,
+                                           uint64_t key_span, uint32_t fill, uint8_t *d_map, uint64_t *d_seg_rows) {
+	if (!keys || !codes) return ADAC_ERR_INVALID_ARGUMENT;
+	const ColumnArg cols[] = {{keys, d_key_words}, {codes, d_code_words}};
+	if (!same_rows(cols) || !mapped_domain_ok(keys, key_base, key_span)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (fill > 255u || !d_map || !aligned8(d_map)) return ADAC_ERR_INVALID_ARGUMENT;
+	const uint64_t map_words = (key_span + 7ull) / 8ull;
+	const WordRange bufs[] = {{reinterpret_cast<const uint64_t *>(d_map), map_words},
+	                          {d_seg_rows, keys->nseg},
+	                          {d_validity, (keys->value_span + 63) / 64}};
+	if (any_overlap(bufs)) return ADAC_ERR_INVALID_ARGUMENT;
+	ADAC_HIP(hipSetDevice(keys->ctx->device));
+	hipStream_t stream = keys->ctx->stream;
+	if (keys->nseg) {
+		adac_status st = ensure_scan_groups(keys);
+		if (st != ADAC_OK) return st;
+	}
+	ADAC_HIP(hipMemsetAsync(d_map, (int)fill, map_words * 8ull, stream));
+	if (d_seg_rows && keys->nseg) ADAC_HIP(hipMemsetAsync(d_seg_rows, 0, keys->nseg * sizeof(uint64_t), stream));
+	if (keys->nseg == 0) return ADAC_OK;
+	ADAC_HIP(adac::launch_build_map(stream, cols[0], cols[1], scan_work(keys), d_validity, key_base, key_span, d_map,
+	                                d_seg_rows));
+	return ADAC_OK;
 }
 
 // SUM(value), COUNT(*) GROUP BY key over two packed columns of one table (Q1's shape, TPCH_runtime.txt:2-6)

@@ -1977,6 +1977,7 @@ bool dispatch_int(int v, F &&f) {
 #include "adac_scan_compare.inl"
 #include "adac_scan_member.inl"
 #include "adac_group_dense.inl"
+#include "adac_group_mapped.inl"
 #include "adac_group_product.inl"
 #include "adac_group_product3.inl"
 #include "adac_group_q1.inl"
@@ -2321,6 +2322,37 @@ hipError_t launch_group_dense(hipStream_t s, const Column &keys, const Column &v
 		                   reinterpret_cast<unsigned long long *>(d_sums), reinterpret_cast<unsigned long long *>(d_counts),
 		                   reinterpret_cast<unsigned long long *>(d_seg_rows), knobs);
 	}, d_validity != nullptr, d_sums != nullptr);
+	return hipGetLastError();
+}
+
+hipError_t launch_group_mapped(hipStream_t s, const Column &keys, const Column &values, const ScanWork &work,
+                               const uint64_t *d_validity, const uint8_t *d_map, uint64_t key_base, uint64_t key_span,
+                               uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts, uint64_t *d_seg_rows) {
+	if (work.nscan_groups == 0) return hipSuccess;
+	const MemberDomain dom = member_domain(keys, key_base, key_span);
+	const TypeWords vt = d_sums ? type_words(values) : TypeWords {0ull, 0ull};
+	const uint32_t copies = mapped_copies(ngroups, g_tuning.group_mapped_copies);
+	dispatch_flags([&](auto V, auto SUM) {
+		hipLaunchKernelGGL((k_group_mapped<V.value, SUM.value>), dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
+		                   work.d_scan_groups, keys.d_words, SUM.value ? values.d_descs : nullptr,
+		                   SUM.value ? values.d_words : nullptr, dom, vt.tmask, vt.sbit, d_validity, d_map, ngroups, copies,
+		                   reinterpret_cast<unsigned long long *>(d_sums), reinterpret_cast<unsigned long long *>(d_counts),
+		                   reinterpret_cast<unsigned long long *>(d_seg_rows));
+	}, d_validity != nullptr, d_sums != nullptr);
+	return hipGetLastError();
+}
+
+hipError_t launch_build_map(hipStream_t s, const Column &keys, const Column &codes, const ScanWork &work,
+                            const uint64_t *d_validity, uint64_t key_base, uint64_t key_span, uint8_t *d_map,
+                            uint64_t *d_seg_rows) {
+	if (work.nscan_groups == 0) return hipSuccess;
+	const MemberDomain dom = member_domain(keys, key_base, key_span);
+	const TypeWords ct = type_words(codes);
+	dispatch_flags([&](auto V) {
+		hipLaunchKernelGGL(k_build_map<V.value>, dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
+		                   work.d_scan_groups, keys.d_words, codes.d_descs, codes.d_words, dom, ct.tmask, ct.sbit, d_validity,
+		                   d_map, reinterpret_cast<unsigned long long *>(d_seg_rows));
+	}, d_validity != nullptr);
 	return hipGetLastError();
 }
 

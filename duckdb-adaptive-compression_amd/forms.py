@@ -21,6 +21,9 @@ segment from the descriptor, the type and the domain (set_base, set_bits): membe
 
 The grouped SUM / COUNT by a dense key (k_group_dense, csrc/adac_group_dense.inl) chooses a reader and an accumulator
 per key segment the same way, the walk also asking the value column: dense_form_groups mirrors dense_plan.
+
+The grouped SUM / COUNT by a code looked up through a dense key (k_group_mapped, csrc/adac_group_mapped.inl) takes the
+same readers and, instead of the window, an on-chip slice of the map: mapped_form_groups mirrors mapped_plan.
 """
 from itertools import repeat
 
@@ -154,14 +157,13 @@ def member_form_groups(descs, type, set_base, set_bits):
 
 
 DENSE_WINDOW = 512   # kDenseWindow
+MAPPED_SLICE = 2048  # kMappedSlice
 
 
-def dense_form_groups(descs_k, k_type, key_base, key_span, descs_v=None, v_type=None):
-    """adac_scan_group_sum_dense (descs_v / v_type given) / adac_scan_group_count_dense: dense_plan, per segment
-    "header", "walk-window", "walk-direct", "staged-window" or "staged-direct" (every scan group of a segment takes the
-    same form); None for a segment without rows.  member_plan's rule with DENSE_WINDOW indices for the window, the walk
-    also asking the value column for 1 <= w <= 32, a frame and count * w < 2^31.  Types: (size in bytes, signed);
-    key_base: a bit pattern of the key type."""
+def _reach_form_groups(descs_k, k_type, key_base, key_span, descs_v, v_type, limit, near):
+    """dense_plan per segment: the reader ("header", "walk" or "staged"; the walk also asks the value column, when there
+    is one, for 1 <= w <= 32, a frame and count * w < 2^31) and, for the other two, "-" + near when the indices the
+    segment can reach number at most `limit`, "-direct" otherwise; None for a segment without rows."""
     size, signed = k_type
     sbit = (1 << (8 * size - 1)) if signed else 0
     dlo = (int(key_base) ^ sbit)            # biased by the sign bit every interval is one of unsigned numbers
@@ -182,5 +184,22 @@ def dense_form_groups(descs_k, k_type, key_base, key_span, descs_v=None, v_type=
             continue
         lo, hi = max(bmin - dlo, 0), min(btop, dhi) - dlo + 1   # indices [lo, hi) are what the segment can reach
         walk = value_ok(d, k_type, 4, False) and (dv is None or value_ok(dv, v_type, 1, False))
-        out.append(("walk" if walk else "staged") + ("-window" if hi - lo <= DENSE_WINDOW else "-direct"))
+        out.append(("walk" if walk else "staged") + ("-" + near if hi - lo <= limit else "-direct"))
     return out
+
+
+def dense_form_groups(descs_k, k_type, key_base, key_span, descs_v=None, v_type=None):
+    """adac_scan_group_sum_dense (descs_v / v_type given) / adac_scan_group_count_dense: dense_plan, per segment
+    "header", "walk-window", "walk-direct", "staged-window" or "staged-direct" (every scan group of a segment takes the
+    same form); None for a segment without rows.  member_plan's rule with DENSE_WINDOW indices for the window, the walk
+    also asking the value column for 1 <= w <= 32, a frame and count * w < 2^31.  Types: (size in bytes, signed);
+    key_base: a bit pattern of the key type."""
+    return _reach_form_groups(descs_k, k_type, key_base, key_span, descs_v, v_type, DENSE_WINDOW, "window")
+
+
+def mapped_form_groups(descs_k, k_type, key_base, key_span, descs_v=None, v_type=None):
+    """adac_scan_group_sum_mapped / adac_scan_build_map (descs_v / v_type: the value or the codes column) /
+    adac_scan_group_count_mapped: mapped_plan (csrc/adac_group_mapped.inl), per segment "header", "walk-slice",
+    "walk-direct", "staged-slice" or "staged-direct"; None for a segment without rows.  dense_form_groups' rule with
+    MAPPED_SLICE indices for the on-chip copy of the map (the build has no such copy: only its reader matters)."""
+    return _reach_form_groups(descs_k, k_type, key_base, key_span, descs_v, v_type, MAPPED_SLICE, "slice")

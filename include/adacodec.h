@@ -142,7 +142,8 @@ uint32_t adac_tile_values(int physical_type);
  * workgroup; 0 = chosen by type), "num_cus" (0 = the device's own count), "single_pass_encode" (0 = analyze + plan +
  * pack as three kernels), "encode_big_image", "encode_publish_ahead", "scan_cells", "tile_records", "gather_compact",
  * "group_sum_wide", "group_sum_rw", "group_product_rw", "group_product3_rw", "group_q1_rw", "group_dense_combine",
- * "group_dense_window", "sel_debug": the table in
+ * "group_dense_window", "group_mapped_copies" (copies of the mapped scans' on-chip bins; 0 = as many as fit),
+ * "sel_debug": the table in
  * adac_set_tuning is the full list, Tuning in
  * csrc/adac_internal.h says what each does.  Decoded values, packed words, widths and mins never depend on them.  One
  * knob changes WHERE adac_encode puts a segment in the arena: "encode_placement" 1 hands out arena space in order of
@@ -599,6 +600,62 @@ adac_status adac_scan_group_sum_dense(adac_layout *keys, const uint64_t *d_key_w
 /* the counts alone: no value column is read */
 adac_status adac_scan_group_count_dense(adac_layout *keys, const uint64_t *d_key_words, const uint64_t *d_validity,
                                         uint64_t key_base, uint64_t key_span, uint64_t *d_counts, uint64_t *d_seg_rows);
+
+/* SUM(value), COUNT(*) GROUP BY A CODE LOOKED UP THROUGH A DENSE KEY — the star-join aggregate: TPC-H Q5 / Q7 / Q8 / Q9's
+ * revenue by the nation of the supplier behind l_suppkey, Q10 / Q3 by an attribute of the customer or order behind
+ * o_custkey / l_orderkey, Q14 / Q19 by an attribute of the part behind l_partkey — on the packed bytes of both columns,
+ * without a hash table, a materialised code column or a global atomic per row.  Called on the KEY layout.
+ * Domain and mask: the domain [key_base, key_base + key_span - 1], a key's index t = (bits(k) ^ sbit) - (bits(key_base)
+ * ^ sbit), "in the domain iff t < key_span" and the check that the domain stays inside the key type are exactly
+ * adac_scan_group_sum_dense's; 1 <= key_span <= 2^32.  A row is wanted iff its bit is set in d_validity, indexed in the
+ * KEYS' element space (NULL: every row); bits of elements that no segment covers never influence a result and no mask
+ * word outside ceil(value_span(keys) / 64) is read.
+ * The map: d_map holds one byte per index of the domain, in an allocation of key_span rounded up to a multiple of 8
+ * bytes, 8-byte aligned (the member set's word rule).  Bytes at indices >= key_span may hold anything and never influence
+ * a result; no byte outside that allocation is read; a byte is read only at an index some wanted row inside the domain
+ * has, or as part of an on-chip copy of the window a segment can reach.
+ * Probe (sum / count): a wanted row whose key has index t in the domain has group g = d_map[t]; it adds widen(value) (the
+ * value column's own signedness, mod 2^64) to d_sums[min(g, ngroups)] and 1 to d_counts[min(g, ngroups)].  Entry
+ * [ngroups] is adac_scan_group_sum's overflow entry: it is how the caller drops the dimension rows a filter removed, by
+ * giving them code 255.  1 <= ngroups <= 256.  d_sums and d_counts hold ngroups + 1 words and are fully written by the
+ * call: the caller clears nothing.  d_counts may be NULL in the sum entry.  Wanted rows with a key outside the domain
+ * contribute nowhere.  d_seg_rows[seg] = the wanted rows of the segment whose key lies in the domain: nseg words, written
+ * for segments without rows too; may be NULL.  The ngroups + 1 counts add up to the sum of d_seg_rows.
+ * adac_scan_sum_product's pair rules hold: one context for both layouts and the same row count per segment; types,
+ * widths, placements, encode rules and value offsets may differ; values == keys with the same words is legal.
+ * ADAC_ERR_INVALID_ARGUMENT, on the host before anything is enqueued (the call then writes nothing): a NULL layout;
+ * layouts on different contexts; per-segment counts that differ; key_span outside 1 ... 2^32 or a domain that leaves the
+ * type; ngroups outside 1 ... 256; NULL d_map or d_map not 8-byte aligned; NULL d_sums (sum entry) or NULL d_counts
+ * (count entry); a NULL or not 16-byte aligned words pointer while there are rows; any two of d_sums, d_counts,
+ * d_seg_rows, d_validity overlapping; d_map overlapping d_sums, d_counts or d_seg_rows.  A key layout without segments
+ * returns ADAC_OK and still zero-fills d_sums and d_counts.
+ * Both calls enqueue on the context's stream and synchronise no more than adac_scan_group_sum_dense does.
+ * A scan group whose key segment is packed against a frame of reference that stays inside the type, with
+ * [frame, frame + 2^width - 1] apart from the domain, is decided from the descriptor: no packed word of either column,
+ * no mask word and no map byte is read.  A key segment whose interval reaches at most 2048 indices (every width up to
+ * 11, every domain of at most 2048 keys) looks its rows up in an on-chip copy of that window of the map.  Rows of the
+ * groups below ngroups add up in replicated on-chip bins, rows of the overflow entry in registers; the tuning knob
+ * "group_mapped_copies" (0 = as many copies as fit, n = at most n) never changes a result. */
+adac_status adac_scan_group_sum_mapped(adac_layout *keys, const uint64_t *d_key_words, adac_layout *values,
+                                       const uint64_t *d_value_words, const uint64_t *d_validity, const uint8_t *d_map,
+                                       uint64_t key_base, uint64_t key_span, uint32_t ngroups, uint64_t *d_sums,
+                                       uint64_t *d_counts, uint64_t *d_seg_rows);
+/* the counts alone: no value column is read */
+adac_status adac_scan_group_count_mapped(adac_layout *keys, const uint64_t *d_key_words, const uint64_t *d_validity,
+                                         const uint8_t *d_map, uint64_t key_base, uint64_t key_span, uint32_t ngroups,
+                                         uint64_t *d_counts, uint64_t *d_seg_rows);
+/* the build side: d_map[key - key_base] = code of that row.  `keys` and `codes` are two columns of the dimension table
+ * (the pair rules above); domain, mask and d_seg_rows as above.  d_map (the rounded-up allocation, pad bytes included)
+ * is fully written by the call: every byte is `fill` (0 ... 255), except that for each wanted row of `keys` whose key is
+ * in the domain d_map[t] = min(code, 255), the code being the `codes` column's value as an unsigned number of its own
+ * width (adac_scan_group_sum's key rule: a negative code of a signed type saturates).  If several wanted rows share an
+ * index and disagree on the code, the entry holds one of their codes, unspecified which; primary keys never do.
+ * ADAC_ERR_INVALID_ARGUMENT as above, with fill above 255 and d_map overlapping d_seg_rows or d_validity; a key layout
+ * without segments still fills d_map.  For a dimension whose key is dense in row order (supplier, customer, part)
+ * adac_unpack of a uint8 code column already IS the map, with key_base the first key: no build is needed. */
+adac_status adac_scan_build_map(adac_layout *keys, const uint64_t *d_key_words, adac_layout *codes,
+                                const uint64_t *d_code_words, const uint64_t *d_validity, uint64_t key_base,
+                                uint64_t key_span, uint32_t fill, uint8_t *d_map, uint64_t *d_seg_rows);
 
 /* Materialise only the selected rows: d_out receives, densely and in row order (segment by segment), the values of
  * the rows whose bit is set in d_bitmap (the result of adac_scan_select_between, or any mask over the element index
