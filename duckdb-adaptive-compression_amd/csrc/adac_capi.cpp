@@ -70,6 +70,10 @@ struct adac_layout {
 	std::vector<uint64_t> val_offs;
 	adac_segment_desc *d_descs = nullptr;
 	TileRef *d_tiles = nullptr;
+	// the decode's own tiles, cut on 128-byte lines of the output (adac_tile_cut.h): adac_unpack walks these, everything
+	// else the segment-relative d_tiles
+	TileRef *d_unpack_tiles = nullptr;
+	uint64_t n_unpack_tiles = 0;
 	uint64_t *d_minmax = nullptr;
 	// fused-scan work items (see ScanGroup): built lazily for the current scan_tiles_per_wg, re-expanded when
 	// the descriptors changed
@@ -569,18 +573,26 @@ extern "C" adac_status adac_layout_create(adac_ctx *c, int type, const uint32_t 
 	}
 	l->max_arena_words = arena;
 	l->ntiles = tiles.size();
-	if (l->ntiles >= 0x7fffffffull) { // grid.x limit
+	const std::vector<TileRef> unpack_tiles =
+	    adac::cut_tiles_on_lines(l->type_size, l->counts.data(), l->val_offs.data(), nseg);
+	l->n_unpack_tiles = unpack_tiles.size();
+	if (l->ntiles >= 0x7fffffffull || l->n_unpack_tiles >= 0x7fffffffull) { // grid.x limit
 		adac_layout_destroy(l);
 		return ADAC_ERR_INVALID_ARGUMENT;
 	}
 	hipError_t e = hipSetDevice(c->device);
 	if (e == hipSuccess) e = hipMalloc((void **)&l->d_descs, (nseg ? nseg : 1) * sizeof(adac_segment_desc));
 	if (e == hipSuccess) e = hipMalloc((void **)&l->d_tiles, (l->ntiles ? l->ntiles : 1) * sizeof(TileRef));
+	if (e == hipSuccess)
+		e = hipMalloc((void **)&l->d_unpack_tiles, (l->n_unpack_tiles ? l->n_unpack_tiles : 1) * sizeof(TileRef));
 	if (e == hipSuccess) e = hipMalloc((void **)&l->d_minmax, (nseg ? nseg : 1) * 2 * sizeof(uint64_t));
 	if (e == hipSuccess && nseg)
 		e = hipMemcpyAsync(l->d_descs, descs.data(), nseg * sizeof(adac_segment_desc), hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess && l->ntiles)
 		e = hipMemcpyAsync(l->d_tiles, tiles.data(), l->ntiles * sizeof(TileRef), hipMemcpyHostToDevice, c->stream);
+	if (e == hipSuccess && l->n_unpack_tiles)
+		e = hipMemcpyAsync(l->d_unpack_tiles, unpack_tiles.data(), l->n_unpack_tiles * sizeof(TileRef),
+		                   hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess) e = adac::launch_minmax_init(c->stream, l->d_minmax, nseg);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // descs/tiles are stack-local
 	if (e != hipSuccess) {
@@ -597,6 +609,7 @@ extern "C" void adac_layout_destroy(adac_layout *l) {
 	(void)hipSetDevice(l->ctx->device);
 	if (l->d_descs) (void)hipFree(l->d_descs);
 	if (l->d_tiles) (void)hipFree(l->d_tiles);
+	if (l->d_unpack_tiles) (void)hipFree(l->d_unpack_tiles);
 	if (l->d_minmax) (void)hipFree(l->d_minmax);
 	if (l->d_tile_cnt) (void)hipFree(l->d_tile_cnt);
 	if (l->d_tile_off) (void)hipFree(l->d_tile_off);
@@ -862,7 +875,13 @@ extern "C" adac_status adac_unpack(adac_layout *l, const uint64_t *d_words, void
 		adac_status st = tile_records(l, &recs);
 		if (st != ADAC_OK) return st;
 	}
-	ADAC_HIP(adac::launch_unpack(l->ctx->stream, ColumnArg {l, d_words}, l->d_tiles, l->ntiles, d_out, recs));
+	if (recs) { // the A/B form keeps the segment-relative table its records were expanded from
+		ADAC_HIP(adac::launch_unpack(l->ctx->stream, ColumnArg {l, d_words}, l->d_tiles, l->ntiles, d_out, recs));
+		return ADAC_OK;
+	}
+	// tiles cut on 128-byte lines of the output (by element index: address alignment when d_out is 128-byte aligned)
+	ADAC_HIP(adac::launch_unpack(l->ctx->stream, ColumnArg {l, d_words}, l->d_unpack_tiles, l->n_unpack_tiles, d_out,
+	                             nullptr));
 	return ADAC_OK;
 }
 

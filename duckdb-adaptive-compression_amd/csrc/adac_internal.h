@@ -6,18 +6,19 @@
 #include <stdint.h>
 
 #include "adacodec.h"
+#include "adac_tile_cut.h"
 
 namespace adac {
 
 constexpr int kWorkgroup = 256;       // 4 wavefronts of 64 lanes
 constexpr int kTileBytes = 16384;     // decoded bytes per tile: tile = 16 KiB / sizeof(T) values
 constexpr uint32_t kNoTile = 0xffffffffu;
+constexpr int kLineBytes = 128;       // one cache line of the output: the decode's tiles are cut on them
+static_assert(kCutTileBytes == (uint32_t)kTileBytes && kCutLineBytes == (uint32_t)kLineBytes, "adac_tile_cut.h");
 
-// One tile of one segment: `first` is a multiple of the type's tile size.
-struct TileRef {
-	uint32_t seg;
-	uint32_t first;
-};
+// TileRef (adac_tile_cut.h): one tile of one segment.  A layout keeps two tables of them: the segment-relative one
+// (`first` a multiple of the type's tile size; analyze, pack, the gather, the scan groups, the expanded records) and the
+// decode's, cut on lines of the output (cut_tiles_on_lines; adac_unpack only).
 
 // A tile with its segment's CURRENT descriptor folded in (rebuilt whenever descriptors change, like the scan groups): the
 // gather (k_gather_c) reads ONE 32-byte record before its first data load instead of the dependent chain tile entry ->
@@ -172,8 +173,9 @@ hipError_t launch_plan(hipStream_t s, uint32_t type_size, int rule, int pad_to_b
 hipError_t launch_pack(hipStream_t s, uint32_t type_size, uint64_t null_bits, const adac_segment_desc *d_descs,
                        const TileRef *d_tiles, uint64_t ntiles, const void *d_vals, const uint64_t *d_validity,
                        uint64_t *d_words);
-// decode of a packed column to d_out: every tile (d_recs: the expanded tile records, or null), one range of one segment,
-// and the n rows (d_segs[i], d_rows[i])
+// decode of a packed column to d_out: every tile (d_recs null: d_tiles is the layout's LINE-CUT table; d_recs the expanded
+// records: d_tiles is the segment-relative table they were made from), one range of one segment, and the n rows
+// (d_segs[i], d_rows[i])
 hipError_t launch_unpack(hipStream_t s, const Column &col, const TileRef *d_tiles, uint64_t ntiles, void *d_out,
                          const TileRec *d_recs);
 hipError_t launch_unpack_range(hipStream_t s, const Column &col, RangeArgs range, void *d_out);

@@ -119,6 +119,26 @@ __device__ __forceinline__ TileCtx resolve_tile(const adac_segment_desc *__restr
 	return t;
 }
 
+// The same for the decode's own table (adac_tile_cut.h: cut_tiles_on_lines): tiles cut on 128-byte lines of the output,
+// so a tile ends where the TILE rows that begin at the line of its first element end — cut_tile_rows, for TILE and
+// LINE = 128 / sizeof(T) rows.  Every tile but a segment's first starts on a line and every one but its last and an
+// off-line first one is full: the tiles of a segment that starts at an odd element take decode_full_tile and store whole
+// lines like everybody else's.
+template <int TILE, int LINE>
+__device__ __forceinline__ TileCtx resolve_unpack_tile(const adac_segment_desc *__restrict__ descs,
+                                                       const TileRef *__restrict__ tiles) {
+	TileCtx t;
+	const TileRef r = tiles[blockIdx.x];
+	t.seg = r.seg;
+	t.first = r.first;
+	t.d = descs[r.seg]; // field by field on purpose: see load_desc
+	t.elem0 = t.d.val_off + r.first;
+	const uint32_t left = t.d.count - r.first;
+	const uint32_t room = (uint32_t)TILE - ((uint32_t)t.elem0 & (uint32_t)(LINE - 1));
+	t.n = left < room ? left : room;
+	return t;
+}
+
 __device__ __forceinline__ uint64_t effective_add(const adac_segment_desc &d);
 
 // An expanded tile record at a wave-uniform address through the scalar unit: eight dwords, taken apart with scalar
@@ -336,6 +356,9 @@ __device__ __forceinline__ uint64_t effective_add(const adac_segment_desc &d) {
 
 // ---------------------------------------------------------------------------------------------
 // k_unpack — decode.  LDS: the packed image of one tile (<= 16 KiB + 32 B).
+// Three forms: the whole layout through its line-cut tile table (resolve_unpack_tile; `tiles` must be that table), one
+// range of one segment (RANGE: implicit tiles from range.start, the caller's output offset), and the A/B form through the
+// expanded records of the segment-relative table (REC).
 // ---------------------------------------------------------------------------------------------
 template <typename U>
 struct StoreSink {
@@ -388,7 +411,7 @@ __global__ __launch_bounds__(kWorkgroup) void k_unpack(const adac_segment_desc *
 		n = left < (uint32_t)TILE ? left : (uint32_t)TILE;
 		elem0 = range.out_off + done;
 	} else {
-		const TileCtx t = resolve_tile<TILE>(descs, tiles);
+		const TileCtx t = resolve_unpack_tile<TILE, kLineBytes / (int)sizeof(U)>(descs, tiles); // the line-cut table
 		d = t.d;
 		first = t.first;
 		n = t.n;

@@ -282,7 +282,11 @@ adac_status adac_reencode(adac_layout *src, const uint64_t *d_src_words, const u
 /* Decode every segment: out[val_off + i] = T(read_int(words, i*w, w) + min).  Replaces SuccinctScanPartial
  * over a whole column (succinct.cpp:123-144) and ColumnSegment::UncompressSuccinct (column_segment.cpp:458-506).
  * Unpacked segments are copied without the min add (SURVEY.md §8a parity domain (iii)).
- * d_out must be 16-byte aligned. */
+ * d_out must be 16-byte aligned.
+ * The decode's work units are cut on 128-byte lines of the output BY ELEMENT INDEX (val_off + row): each unit but a
+ * segment's first starts at an element index that is a multiple of 128 / sizeof(T).  That is alignment of the stored
+ * addresses, and whole-line stores, when d_out itself is 128-byte aligned, as the blocks of a device allocator are; any
+ * 16-byte-aligned d_out decodes to the same values.  adac_layout_ntiles keeps counting the segment-relative tiles. */
 adac_status adac_unpack(adac_layout *l, const uint64_t *d_words, void *d_out);
 
 /* Decode `count` values of ONE segment starting at row `start` to d_out[out_off ...]: the scan_vector /
