@@ -1461,6 +1461,197 @@ def q5_packed(adac, n=59_986_052, n_orders=15_000_000):
     return out
 
 
+def q5_revenue_packed(adac, n=59_986_052, n_orders=15_000_000, profile=None):
+    """TPC-H Q5's revenue on packed columns: SUM(l_extendedprice * l_discount), SUM(l_extendedprice), COUNT(*) GROUP BY the
+    nation of the supplier behind l_suppkey from ONE adac_scan_group_sum_product_mapped, so that revenue =
+    100 * sums_a - sums_ab = SUM(price * (100 - discount)); checked against numpy before and after the timing.
+    q5_packed's tables plus l_discount: 60 M lineitems through the 100 000-byte supplier -> nation map with and without
+    the region filter, and the sorted and the shuffled l_orderkey through the 60 M-byte order -> nation map that
+    adac_scan_build_map builds under the date bitmap.  Interleaved in the same process: the call with every output and
+    with d_sums_a and d_counts NULL, and the comparison points, never the code under test: adac_unpack of the three
+    columns, adac_scan_group_sum_mapped on the price alone (the same scan minus b and the product: a floor) and
+    adac_scan_group_sum_product over a pre-materialised uint8 code column (the same arithmetic minus the look-up).  The
+    results go to profiles/r17_group_product_mapped.json (`profile`: another path) as well as to the caller."""
+    ctx = adac.Context(0)
+    rng = np.random.default_rng(1997)
+    ng = Q5_NATIONS
+    cols = lineitem(rng, n, ("l_extendedprice", "l_discount"))
+    l_suppkey = rng.integers(1, Q5_SUPPLIERS + 1, size=n).astype(np.int32)
+    s_nation = rng.integers(0, ng, size=Q5_SUPPLIERS).astype(np.uint8)
+    s_region = np.where(np.isin(s_nation, Q5_REGION), s_nation, 255).astype(np.uint8)
+    lc = adac.appender_segment_counts(n, 4)
+    price, disc = (encode_column(adac, ctx, cols[c], lc) for c in ("l_extendedprice", "l_discount"))
+    supp = encode_column(adac, ctx, l_suppkey, lc)
+    code_all = encode_column(adac, ctx, s_nation[l_suppkey - 1], lc)   # the pre-materialised code columns
+    code_reg = encode_column(adac, ctx, s_region[l_suppkey - 1], lc)
+    # the sorted-key case: orders and their lineitems as in q5_packed
+    idx = np.arange(n_orders, dtype=np.int64)
+    o_orderkey = ((idx // 8) * 32 + idx % 8 + 1).astype(np.int32)
+    del idx
+    l_orderkey = np.repeat(o_orderkey, rng.integers(1, 8, size=n_orders))
+    no = len(l_orderkey)
+    o_nation = rng.integers(0, ng, size=n_orders).astype(np.uint8)
+    o_orderdate = rng.integers(8036, 10562, size=n_orders).astype(np.int32)
+    o_cols = lineitem(rng, no, ("l_extendedprice", "l_discount"))
+    perm = rng.permutation(no)
+    oc, olc = adac.appender_segment_counts(n_orders, 4), adac.appender_segment_counts(no, 4)
+    okey, onat = encode_column(adac, ctx, o_orderkey, oc), encode_column(adac, ctx, o_nation, oc)
+    odate = encode_column(adac, ctx, o_orderdate, oc)
+    obase, ospan = 1, int(o_orderkey.max())
+    year = (o_orderdate >= Q5_DATES[0]) & (o_orderdate <= Q5_DATES[1])
+    omap = np.full(ospan, 255, dtype=np.uint8)
+    omap[(o_orderkey[year] - obase).astype(np.int64)] = o_nation[year]
+    o_code = omap[(l_orderkey - obase).astype(np.int64)]
+    Side = namedtuple("Side", "key price disc code")
+    sorted_, shuffled = (Side(*(encode_column(adac, ctx, v if sel is None else v[sel], olc)
+                                for v in (l_orderkey, o_cols["l_extendedprice"], o_cols["l_discount"], o_code)))
+                         for sel in (None, perm))
+
+    def map_buffer(codes):
+        buf = np.full((len(codes) + 7) // 8 * 8, 255, dtype=np.uint8)
+        buf[:len(codes)] = codes
+        return ctx.upload(buf)
+
+    d_map_all, d_map_reg = map_buffer(s_nation), map_buffer(s_region)
+    d_omap = ctx.alloc((ospan + 7) // 8 * 8)
+    ow, lseg, oseg, olseg = (n_orders + 63) // 64, len(lc), len(oc), len(olc)
+    bm_o, d_ocnt = ctx.alloc(ow * 8 + 8), ctx.alloc(oseg * 8)
+    d_ab, d_a, d_c, d_s2, d_c2 = (ctx.alloc((ng + 1) * 8) for _ in range(5))
+    d_rows = ctx.alloc(max(lseg, olseg, oseg) * 8)
+    d_out = ctx.alloc(max(n, no) * 4 + 64)
+
+    def revenue(d_map=d_map_all, every=True):
+        supp.lay.scan_group_sum_product_mapped(supp.words, price.lay, price.words, disc.lay, disc.words, d_map, 1,
+                                               Q5_SUPPLIERS, ng, d_ab, d_a if every else None, d_c if every else None,
+                                               d_rows if every else None)
+
+    def order_revenue(t=sorted_, every=True):
+        t.key.lay.scan_group_sum_product_mapped(t.key.words, t.price.lay, t.price.words, t.disc.lay, t.disc.words, d_omap,
+                                                obase, ospan, ng, d_ab, d_a if every else None, d_c if every else None,
+                                                d_rows if every else None)
+
+    def fold(codes, p, d):
+        g = np.minimum(codes.astype(np.int64), ng)
+        p = p.astype(np.float64)
+        return tuple(np.bincount(g, weights=w, minlength=ng + 1).astype(np.uint64)
+                     for w in (p * d.astype(np.float64), p, None))
+
+    # (sums below 2^53: 60 M rows of at most 10 495 000 x 10 add up to 6.3e15, exact in the float64 weights of bincount)
+    want_all = fold(s_nation[l_suppkey - 1], cols["l_extendedprice"], cols["l_discount"])
+    want_reg = fold(s_region[l_suppkey - 1], cols["l_extendedprice"], cols["l_discount"])
+    want_ord = fold(o_code, o_cols["l_extendedprice"], o_cols["l_discount"])
+
+    def outputs():
+        return tuple(b.download(np.uint64, ng + 1) for b in (d_ab, d_a, d_c))
+
+    def same(got, want, what):
+        assert all(np.array_equal(g, w) for g, w in zip(got, want)), what
+        # the query's own form: SUM(price * (100 - discount)) per group
+        assert np.array_equal(np.uint64(100) * got[1] - got[0], np.uint64(100) * want[1] - want[0]), what
+
+    def parity(when):
+        odate.lay.scan_select_between(odate.words, Q5_DATES[0], Q5_DATES[1], bm_o, d_ocnt)
+        okey.lay.scan_build_map(okey.words, onat.lay, onat.words, obase, ospan, d_omap, 255, d_rows, bm_o)
+        ctx.sync()
+        assert np.array_equal(d_omap.download(np.uint8, ospan), omap), "order map parity (%s)" % when
+        for copies in (0, 1):
+            adac.set_tuning("group_mapped_copies", copies)
+            for run, want, name in ((revenue, want_all, "nations"), (lambda **k: revenue(d_map_reg, **k), want_reg, "region"),
+                                    (order_revenue, want_ord, "sorted orders"),
+                                    (lambda **k: order_revenue(shuffled, **k), want_ord, "shuffled orders")):
+                run()
+                ctx.sync()
+                same(outputs(), want, "Q5 revenue, %s, copies %d (%s)" % (name, copies, when))
+                run(every=False)
+                ctx.sync()
+                assert np.array_equal(d_ab.download(np.uint64, ng + 1), want[0]), (name, copies, when, "sums_ab alone")
+            adac.set_tuning("group_mapped_copies", 0)
+
+    parity("before timing")
+
+    def sum_mapped(k, v, d_map, b, nb):
+        return lambda: k.lay.scan_group_sum_mapped(k.words, v.lay, v.words, d_map, b, nb, ng, d_s2, d_c2, d_rows)
+
+    def product_on_codes(a, b, k):
+        return lambda: a.lay.scan_group_sum_product(a.words, b.lay, b.words, k.lay, k.words, ng, d_s2, d_c2)
+
+    def unpack(c):
+        return lambda: c.lay.unpack(c.words, d_out)
+
+    entries = [("revenue", revenue),
+               ("revenue_ab_only", lambda: revenue(every=False)),
+               ("revenue_region", lambda: revenue(d_map_reg)),
+               ("revenue_region_ab_only", lambda: revenue(d_map_reg, every=False)),
+               ("unpack_suppkey", unpack(supp)), ("unpack_price", unpack(price)), ("unpack_discount", unpack(disc)),
+               ("sum_mapped_price", sum_mapped(supp, price, d_map_all, 1, Q5_SUPPLIERS)),
+               ("sum_mapped_price_region", sum_mapped(supp, price, d_map_reg, 1, Q5_SUPPLIERS)),
+               ("product_on_codes", product_on_codes(price, disc, code_all)),
+               ("product_on_codes_region", product_on_codes(price, disc, code_reg)),
+               ("revenue_orderkey", order_revenue),
+               ("revenue_orderkey_ab_only", lambda: order_revenue(every=False)),
+               ("revenue_orderkey_shuffled", lambda: order_revenue(shuffled)),
+               ("revenue_orderkey_shuffled_ab_only", lambda: order_revenue(shuffled, every=False)),
+               ("unpack_orderkey", unpack(sorted_.key)), ("unpack_order_price", unpack(sorted_.price)),
+               ("unpack_order_discount", unpack(sorted_.disc)),
+               ("sum_mapped_orderkey", sum_mapped(sorted_.key, sorted_.price, d_omap, obase, ospan)),
+               ("sum_mapped_orderkey_shuffled", sum_mapped(shuffled.key, shuffled.price, d_omap, obase, ospan)),
+               ("product_on_order_codes", product_on_codes(sorted_.price, sorted_.disc, sorted_.code)),
+               ("product_on_order_codes_shuffled", product_on_codes(shuffled.price, shuffled.disc, shuffled.code))]
+    samples = timed_interleaved(ctx, entries)
+    parity("after timing")
+    med = {k: float(np.median(x)) for k, x in samples.items()}
+    unpack_supp = med["unpack_suppkey"] + med["unpack_price"] + med["unpack_discount"]
+    unpack_ord = med["unpack_orderkey"] + med["unpack_order_price"] + med["unpack_order_discount"]
+    kind32 = (4, True)
+
+    def census(k, a, b, base, nb):
+        fs = forms.mapped_product_form_groups(k.descs, kind32, base, nb, a.descs, kind32, b.descs, kind32)
+        return {f: fs.count(f) for f in sorted(set(fs) - {None})}
+
+    def cell(call, rows, unpack3, floor, codes):
+        return {"ms": med[call], "rows_per_ns": rows / (med[call] * 1e6), "over_unpack_of_three": med[call] / unpack3,
+                "over_sum_mapped_on_price": med[call] / med[floor], "over_sum_product_on_codes": med[call] / med[codes],
+                "ab_only_over_every_output": med[call + "_ab_only"] / med[call]}
+
+    out = {"lineitems": n, "suppliers": Q5_SUPPLIERS, "nations": ng, "orders": n_orders, "order_lineitems": no,
+           "order_key_span": ospan, "orders_in_dates": int(year.sum()),
+           "rows_kept_by_region": int(want_reg[2][:ng].sum()), "rows_kept_by_dates": int(want_ord[2][:ng].sum()),
+           "widths": {"l_suppkey": supp.widths, "l_extendedprice": price.widths, "l_discount": disc.widths,
+                      "l_orderkey": sorted_.key.widths, "l_orderkey_shuffled": shuffled.key.widths},
+           "packed_bytes": {"l_suppkey": supp.nbytes, "l_extendedprice": price.nbytes, "l_discount": disc.nbytes,
+                            "l_orderkey": sorted_.key.nbytes},
+           "segments_by_form": {"l_suppkey": census(supp, price, disc, 1, Q5_SUPPLIERS),
+                                "l_orderkey": census(sorted_.key, sorted_.price, sorted_.disc, obase, ospan),
+                                "l_orderkey_shuffled": census(shuffled.key, shuffled.price, shuffled.disc, obase, ospan)},
+           "ms": med, "unpack_of_three_ms": {"l_suppkey": unpack_supp, "l_orderkey": unpack_ord},
+           "revenue": cell("revenue", n, unpack_supp, "sum_mapped_price", "product_on_codes"),
+           "revenue_region": cell("revenue_region", n, unpack_supp, "sum_mapped_price_region", "product_on_codes_region"),
+           "revenue_orderkey": cell("revenue_orderkey", no, unpack_ord, "sum_mapped_orderkey", "product_on_order_codes"),
+           "revenue_orderkey_shuffled": cell("revenue_orderkey_shuffled", no, unpack_ord, "sum_mapped_orderkey_shuffled",
+                                             "product_on_order_codes_shuffled"),
+           "samples_ms": {k: [round(t, 5) for t in x] for k, x in samples.items()},
+           "note": ("Synthetic lineitem / orders at SF10 size; one run on one MI355X.  revenue* = "
+                    "adac_scan_group_sum_product_mapped with d_sums_a, d_counts and d_seg_rows (*_ab_only: all three NULL); "
+                    "sum_mapped_* = adac_scan_group_sum_mapped on the price with counts (the same scan minus b and the "
+                    "product); product_on_*codes* = adac_scan_group_sum_product over a pre-materialised uint8 code column "
+                    "(the same arithmetic minus the look-up); unpack_* = adac_unpack of the column.  "
+                    "Medians of %d interleaved rounds of %d calls each" % (ROUNDS, INNER))}
+    print("q5_revenue_packed: suppliers %.4f ms (ab only %.4f), region %.4f (%.4f); unpack of three %.4f, sum_mapped on the "
+          "price %.4f / %.4f, product on codes %.4f / %.4f; through the orders %.4f (shuffled %.4f), unpack of three %.4f, "
+          "sum_mapped %.4f (%.4f), product on codes %.4f (%.4f)"
+          % (med["revenue"], med["revenue_ab_only"], med["revenue_region"], med["revenue_region_ab_only"], unpack_supp,
+             med["sum_mapped_price"], med["sum_mapped_price_region"], med["product_on_codes"],
+             med["product_on_codes_region"], med["revenue_orderkey"], med["revenue_orderkey_shuffled"], unpack_ord,
+             med["sum_mapped_orderkey"], med["sum_mapped_orderkey_shuffled"], med["product_on_order_codes"],
+             med["product_on_order_codes_shuffled"]), file=sys.stderr, flush=True)
+    ctx.close()
+    path = profile or os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r17_group_product_mapped.json")
+    with open(path, "w") as f:
+        json.dump({"q5_revenue_packed": out}, f, indent=1, sort_keys=True)
+        f.write("\n")
+    return out
+
+
 def bitpacking_select_gather(adac, n=59_986_052):
     """Filter -> project on DuckDB's own BITPACKING blocks: adac_bp_unpack_selected (values only, then values + ids) of
     l_extendedprice (int32, FOR), the 6-valued uint8 code and a sorted copy of l_partkey (DELTA_FOR) under five bitmaps
@@ -1877,6 +2068,7 @@ def main():
             "q4_packed": lambda: q4_packed(adac),
             "q18_packed": lambda: q18_packed(adac),
             "q5_packed": lambda: q5_packed(adac),
+            "q5_revenue_packed": lambda: q5_revenue_packed(adac),
             "bitpacking_select_gather": lambda: bitpacking_select_gather(adac),
             "q6_product_packed": lambda: q6_product_packed(adac), "q1_packed": lambda: q1_packed(adac),
             "q1_filtered_packed": lambda: q1_filtered_packed(adac),

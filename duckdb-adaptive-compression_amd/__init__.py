@@ -189,6 +189,8 @@ SIGNATURES = {
     "adac_scan_group_sum_mapped": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp]),
     "adac_scan_group_count_mapped": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp]),
     "adac_scan_build_map": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp]),
+    "adac_scan_group_sum_product_mapped": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp,
+                                                  _vp]),
     "adac_unpack_selected": (_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "adac_scan_count_between_valid": (_int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "adac_bp_layout_create": (_int, [_vp, _int, _vp, _vp, _vp, _u64, _P(_vp)]),
@@ -691,6 +693,18 @@ class Layout:
         _check(lib().adac_scan_build_map(self._h, _dptr(d_key_words), codes._h, _dptr(d_code_words), _dptr(d_validity),
                                          key_base & NO_MIN, int(key_span), int(fill), _dptr(d_map), _dptr(d_seg_rows)),
                "adac_scan_build_map")
+
+    def scan_group_sum_product_mapped(self, d_key_words, a, d_a_words, b, d_b_words, d_map, key_base, key_span, ngroups,
+                                      d_sums_ab, d_sums_a=None, d_counts=None, d_seg_rows=None, d_validity=None):
+        """SUM(a * b), SUM(a), COUNT(*) GROUP BY d_map[key - key_base] from one scan, called on the KEY layout; `a` and
+        `b`: Layouts over the same rows.  d_sums_ab / d_sums_a / d_counts (ngroups + 1 words each, fully written) are
+        indexed by min(code, ngroups); the rest as scan_group_sum_mapped.  Q5's revenue with integer decimals:
+        100 * d_sums_a - d_sums_ab."""
+        _check(lib().adac_scan_group_sum_product_mapped(self._h, _dptr(d_key_words), a._h, _dptr(d_a_words), b._h,
+                                                        _dptr(d_b_words), _dptr(d_validity), _dptr(d_map),
+                                                        key_base & NO_MIN, int(key_span), int(ngroups), _dptr(d_sums_ab),
+                                                        _dptr(d_sums_a), _dptr(d_counts), _dptr(d_seg_rows)),
+               "adac_scan_group_sum_product_mapped")
 
     def unpack_selected(self, d_words, d_bitmap, d_out, d_out_ids=None, want_total=True):
         """Values (and optionally element indices) of the rows whose bitmap bit is set, dense, in row order.

@@ -1421,6 +1421,45 @@ extern "C" adac_status adac_scan_group_count_mapped(adac_layout *keys, const uin
 	                         nullptr, d_counts, d_seg_rows);
 }
 
+// SUM(a * b), SUM(a), COUNT(*) through the map: scan_group_mapped's checks applied to three columns and three outputs.
+extern "C" adac_status adac_scan_group_sum_product_mapped(adac_layout *keys, const uint64_t *d_key_words, adac_layout *a,
+                                                          const uint64_t *d_a_words, adac_layout *b,
+                                                          const uint64_t *d_b_words, const uint64_t *d_validity,
+                                                          const uint8_t *d_map, uint64_t key_base, uint64_t key_span,
+                                                          uint32_t ngroups, uint64_t *d_sums_ab, uint64_t *d_sums_a,
+                                                          uint64_t *d_counts, uint64_t *d_seg_rows) {
+	if (!keys || !a || !b) return ADAC_ERR_INVALID_ARGUMENT;
+	const ColumnArg cols[] = {{keys, d_key_words}, {a, d_a_words}, {b, d_b_words}};
+	if (!same_rows(cols) || !mapped_domain_ok(keys, key_base, key_span)) return ADAC_ERR_INVALID_ARGUMENT;
+	if (ngroups < 1u || ngroups > 256u || !d_map || !aligned8(d_map) || !d_sums_ab) return ADAC_ERR_INVALID_ARGUMENT;
+	const uint64_t nout = (uint64_t)ngroups + 1ull, map_words = (key_span + 7ull) / 8ull;
+	const WordRange outs[] = {{d_sums_ab, nout},
+	                          {d_sums_a, nout},
+	                          {d_counts, nout},
+	                          {d_seg_rows, keys->nseg},
+	                          {d_validity, (keys->value_span + 63) / 64}};
+	if (any_overlap(outs)) return ADAC_ERR_INVALID_ARGUMENT;
+	const uint64_t *map_w = reinterpret_cast<const uint64_t *>(d_map);
+	for (size_t i = 0; i < 4; i++) { // the map and an output
+		if (words_overlap(map_w, map_words, outs[i].p, outs[i].n)) return ADAC_ERR_INVALID_ARGUMENT;
+	}
+	ADAC_HIP(hipSetDevice(keys->ctx->device));
+	hipStream_t stream = keys->ctx->stream;
+	if (keys->nseg) {
+		adac_status st = ensure_scan_groups(keys);
+		if (st != ADAC_OK) return st;
+	}
+	// every workgroup adds its part: the outputs start from zero (this also writes the groups without rows)
+	ADAC_HIP(hipMemsetAsync(d_sums_ab, 0, nout * sizeof(uint64_t), stream));
+	if (d_sums_a) ADAC_HIP(hipMemsetAsync(d_sums_a, 0, nout * sizeof(uint64_t), stream));
+	if (d_counts) ADAC_HIP(hipMemsetAsync(d_counts, 0, nout * sizeof(uint64_t), stream));
+	if (d_seg_rows && keys->nseg) ADAC_HIP(hipMemsetAsync(d_seg_rows, 0, keys->nseg * sizeof(uint64_t), stream));
+	if (keys->nseg == 0) return ADAC_OK;
+	ADAC_HIP(adac::launch_group_mapped_product(stream, cols[0], cols[1], cols[2], scan_work(keys), d_validity, d_map,
+	                                           key_base, key_span, ngroups, d_sums_ab, d_sums_a, d_counts, d_seg_rows));
+	return ADAC_OK;
+}
+
 // The build side: the map is filled with `fill` first, pad included, in stream order; the rows then store their codes.
 extern "C" adac_status adac_scan_build_map(adac_layout *keys, const uint64_t *d_key_words, adac_layout *codes,
                                            const uint64_t *d_code_words, const uint64_t *d_validity, uint64_t key_base,

@@ -106,7 +106,7 @@ struct Tuning {
 	int group_q1_rw = 1;        // A/B: 0 = adac_scan_group_sum_q1 without the register-walk kernel (k_group_q1 only)
 	int group_dense_combine = 1; // A/B: 0 = adac_scan_group_sum_dense / _count_dense with one atomic per row (no run combining in the walk)
 	int group_dense_window = 1;  // A/B: 0 = the same two without the LDS window (every add goes to global memory)
-	int group_mapped_copies = 0; // adac_scan_group_sum_mapped / _count_mapped: copies of the LDS bins; 0 = as many as fit, n = at most n (1 = one copy)
+	int group_mapped_copies = 0; // adac_scan_group_sum_mapped / _count_mapped / _sum_product_mapped: copies of the LDS bins; 0 = as many as fit, n = at most n (1 = one copy)
 	int encode_placement = 0;   // single-pass encode: 0 = arena order is segment order (look-back), 1 = order of completion
 	int encode_big_image = 1;   // single-pass encode, ordered placement: a segment whose packed words fit the LDS pool is packed there whole and publishes the NEXT footprint before it waits (A/B: 0)
 	int encode_publish_ahead = 1; // single-pass encode, ordered placement: the parked flow publishes the NEXT footprint before it waits (A/B: 0)
@@ -238,6 +238,12 @@ hipError_t launch_group_dense(hipStream_t s, const Column &keys, const Column &v
 hipError_t launch_group_mapped(hipStream_t s, const Column &keys, const Column &values, const ScanWork &work,
                                const uint64_t *d_validity, const uint8_t *d_map, uint64_t key_base, uint64_t key_span,
                                uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts, uint64_t *d_seg_rows);
+// SUM(a * b), SUM(a), COUNT(*) GROUP BY d_map[key - key_base]: d_sums_ab, d_sums_a (may be null) and d_counts (may be
+// null), ngroups + 1 words each; everything else as launch_group_mapped (adac_group_mapped_product.inl)
+hipError_t launch_group_mapped_product(hipStream_t s, const Column &keys, const Column &a, const Column &b,
+                                       const ScanWork &work, const uint64_t *d_validity, const uint8_t *d_map,
+                                       uint64_t key_base, uint64_t key_span, uint32_t ngroups, uint64_t *d_sums_ab,
+                                       uint64_t *d_sums_a, uint64_t *d_counts, uint64_t *d_seg_rows);
 // d_map[key - key_base] = min(code, 255) for every wanted row inside the domain; the caller has filled d_map
 hipError_t launch_build_map(hipStream_t s, const Column &keys, const Column &codes, const ScanWork &work,
                             const uint64_t *d_validity, uint64_t key_base, uint64_t key_span, uint8_t *d_map,

@@ -2001,6 +2001,7 @@ bool dispatch_int(int v, F &&f) {
 #include "adac_scan_member.inl"
 #include "adac_group_dense.inl"
 #include "adac_group_mapped.inl"
+#include "adac_group_mapped_product.inl"
 #include "adac_group_product.inl"
 #include "adac_group_product3.inl"
 #include "adac_group_q1.inl"
@@ -2362,6 +2363,24 @@ hipError_t launch_group_mapped(hipStream_t s, const Column &keys, const Column &
 		                   reinterpret_cast<unsigned long long *>(d_sums), reinterpret_cast<unsigned long long *>(d_counts),
 		                   reinterpret_cast<unsigned long long *>(d_seg_rows));
 	}, d_validity != nullptr, d_sums != nullptr);
+	return hipGetLastError();
+}
+
+hipError_t launch_group_mapped_product(hipStream_t s, const Column &keys, const Column &a, const Column &b,
+                                       const ScanWork &work, const uint64_t *d_validity, const uint8_t *d_map,
+                                       uint64_t key_base, uint64_t key_span, uint32_t ngroups, uint64_t *d_sums_ab,
+                                       uint64_t *d_sums_a, uint64_t *d_counts, uint64_t *d_seg_rows) {
+	if (work.nscan_groups == 0) return hipSuccess;
+	const MemberDomain dom = member_domain(keys, key_base, key_span);
+	const ProductTypes ty = product_types(type_words(a), type_words(b));
+	const uint32_t copies = mapped_product_copies(ngroups, g_tuning.group_mapped_copies);
+	dispatch_flags([&](auto V, auto A) {
+		hipLaunchKernelGGL((k_group_mapped_product<V.value, A.value>), dim3((unsigned)work.nscan_groups), dim3(kWorkgroup),
+		                   0, s, work.d_scan_groups, keys.d_words, a.d_descs, a.d_words, b.d_descs, b.d_words, dom, ty,
+		                   d_validity, d_map, ngroups, copies, reinterpret_cast<unsigned long long *>(d_sums_ab),
+		                   reinterpret_cast<unsigned long long *>(d_sums_a), reinterpret_cast<unsigned long long *>(d_counts),
+		                   reinterpret_cast<unsigned long long *>(d_seg_rows));
+	}, d_validity != nullptr, d_sums_a != nullptr);
 	return hipGetLastError();
 }
 

@@ -24,6 +24,9 @@ per key segment the same way, the walk also asking the value column: dense_form_
 
 The grouped SUM / COUNT by a code looked up through a dense key (k_group_mapped, csrc/adac_group_mapped.inl) takes the
 same readers and, instead of the window, an on-chip slice of the map: mapped_form_groups mirrors mapped_plan.
+
+The grouped SUM(a * b) through the map (k_group_mapped_product, csrc/adac_group_mapped_product.inl) asks BOTH value
+columns before it walks: mapped_product_form_groups mirrors mapped_product_plan.
 """
 from itertools import repeat
 
@@ -203,3 +206,15 @@ def mapped_form_groups(descs_k, k_type, key_base, key_span, descs_v=None, v_type
     "walk-direct", "staged-slice" or "staged-direct"; None for a segment without rows.  dense_form_groups' rule with
     MAPPED_SLICE indices for the on-chip copy of the map (the build has no such copy: only its reader matters)."""
     return _reach_form_groups(descs_k, k_type, key_base, key_span, descs_v, v_type, MAPPED_SLICE, "slice")
+
+
+def mapped_product_form_groups(descs_k, k_type, key_base, key_span, descs_a, a_type, descs_b, b_type):
+    """adac_scan_group_sum_product_mapped: mapped_product_plan (csrc/adac_group_mapped_product.inl), per segment the five
+    names of mapped_form_groups.  The key side, the header and the slice are that function's; the walk needs BOTH a and b
+    at 1 <= w <= 32 with a frame and count * w < 2^31, and either of them can send the segment to the staged reader."""
+    out = []
+    for f, da, db in zip(mapped_form_groups(descs_k, k_type, key_base, key_span), descs_a, descs_b):
+        if f is not None and f.startswith("walk") and not (value_ok(da, a_type, 1, False) and value_ok(db, b_type, 1, False)):
+            f = "staged" + f[len("walk"):]
+        out.append(f)
+    return out

@@ -661,6 +661,45 @@ adac_status adac_scan_build_map(adac_layout *keys, const uint64_t *d_key_words, 
                                 const uint64_t *d_code_words, const uint64_t *d_validity, uint64_t key_base,
                                 uint64_t key_span, uint32_t fill, uint8_t *d_map, uint64_t *d_seg_rows);
 
+/* SUM(a * b), SUM(a), COUNT(*) GROUP BY A CODE LOOKED UP THROUGH A DENSE KEY, from one scan of three packed columns of
+ * one table — what TPC-H's revenue, SUM(l_extendedprice * (1 - l_discount)), needs per group in Q5 / Q7 / Q8 / Q9 / Q10 /
+ * Q3 / Q14 / Q19.  Recipe for Q5 with integer decimals (price in cents, discount in hundredths): keys = l_suppkey,
+ * a = l_extendedprice, b = l_discount, d_map = the supplier's nation (255 for suppliers the region filter drops); then
+ *     revenue[g] = 100 * d_sums_a[g] - d_sums_ab[g]      (mod 2^64, in units of 1/10000)
+ * for g < ngroups, and entry [ngroups] holds what the filter removed.  Called on the KEY layout.
+ * Domain, index, mask and map are exactly adac_scan_group_sum_mapped's: the domain [key_base, key_base + key_span - 1],
+ * t = (bits(k) ^ sbit) - (bits(key_base) ^ sbit), "in the domain iff t < key_span", 1 <= key_span <= 2^32, the domain
+ * inside the key type; d_validity indexed in the KEYS' element space (NULL: every row), no mask word outside
+ * ceil(value_span(keys) / 64) read, bits of uncovered elements never matter; d_map one byte per index in an allocation
+ * of key_span rounded up to a multiple of 8 bytes, 8-byte aligned, pad bytes and bytes at indices >= key_span never
+ * influence a result, no byte outside the allocation is read.
+ * Contributions: a wanted row inside the domain with g = d_map[t] adds widen(a) * widen(b) to d_sums_ab[min(g, ngroups)],
+ * widen(a) to d_sums_a[min(g, ngroups)] and 1 to d_counts[min(g, ngroups)].  Each factor is widened to 64 bits by its own
+ * column's signedness; the product and the sums are taken mod 2^64 (adac_scan_sum_product's rule).  1 <= ngroups <= 256.
+ * The three arrays hold ngroups + 1 words and are fully written by the call: the caller clears nothing.  d_sums_a and
+ * d_counts may each be NULL; d_sums_ab may not.  d_seg_rows (nseg words, may be NULL) as in adac_scan_group_sum_mapped.
+ * Pair rules: a, b and keys are on one context with the same row count per segment; types, widths, placements, encode
+ * rules and value offsets may differ.  a == b with the same words is legal (the per-code sum of squares); a or b may be
+ * the key layout itself.
+ * ADAC_ERR_INVALID_ARGUMENT, on the host before anything is enqueued (the call then writes nothing): a NULL layout (any
+ * of the three); layouts on different contexts; per-segment counts that differ between any two of them; key_span outside
+ * 1 ... 2^32 or a domain that leaves the type; ngroups outside 1 ... 256; NULL d_map or d_map not 8-byte aligned; NULL
+ * d_sums_ab; a NULL or not 16-byte aligned words pointer of any of the three columns while there are rows; any two of
+ * d_sums_ab, d_sums_a, d_counts, d_seg_rows, d_validity overlapping; d_map overlapping d_sums_ab, d_sums_a, d_counts or
+ * d_seg_rows.  A key layout without segments returns ADAC_OK and still zero-fills the outputs that were given.
+ * The call enqueues on the context's stream and synchronises no more than adac_scan_group_sum_mapped does.
+ * A scan group whose key segment is packed against a frame of reference that stays inside the type, with
+ * [frame, frame + 2^width - 1] apart from the domain, is decided from the descriptor: no packed word of any of the three
+ * columns, no mask word and no map byte is read.  The on-chip window of the map (2048 indices) and the replicated
+ * on-chip bins are adac_scan_group_sum_mapped's; the tuning knob "group_mapped_copies" applies here too and never
+ * changes a result.  a and b are read in registers-and-LDS form while both are at most 32 bits wide and packed against
+ * a frame that stays inside their types; any other segment takes a slower staged reader with the same results. */
+adac_status adac_scan_group_sum_product_mapped(adac_layout *keys, const uint64_t *d_key_words, adac_layout *a,
+                                               const uint64_t *d_a_words, adac_layout *b, const uint64_t *d_b_words,
+                                               const uint64_t *d_validity, const uint8_t *d_map, uint64_t key_base,
+                                               uint64_t key_span, uint32_t ngroups, uint64_t *d_sums_ab,
+                                               uint64_t *d_sums_a, uint64_t *d_counts, uint64_t *d_seg_rows);
+
 /* Materialise only the selected rows: d_out receives, densely and in row order (segment by segment), the values of
  * the rows whose bit is set in d_bitmap (the result of adac_scan_select_between, or any mask over the element index
  * space); d_out_ids, if not NULL, receives their element indices (val_off + row).  *total_out, if not NULL, is set

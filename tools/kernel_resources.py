@@ -31,7 +31,7 @@ FIELDS = {
 # the kernels whose registers / occupancy decide a measured throughput; matched as prefixes of the
 # short name below
 BUDGETED = ("k_unpack<", "k_unpack_jobs<", "k_scan_agg<", "k_encode_1p<", "k_repack_g<", "k_analyze_packed_g<",
-            "k_group_sum", "k_group_product", "k_group_product3", "k_group_q1", "k_scan_product", "k_scan_compare<", "k_scan_member<", "k_scan_member_build<", "k_group_dense<", "k_group_mapped<", "k_build_map<", "k_gather<", "k_gather_c<", "k_pack<", "k_analyze<", "k_bp_unpack<",
+            "k_group_sum", "k_group_product", "k_group_product3", "k_group_q1", "k_scan_product", "k_scan_compare<", "k_scan_member<", "k_scan_member_build<", "k_group_dense<", "k_group_mapped<", "k_group_mapped_product<", "k_build_map<", "k_gather<", "k_gather_c<", "k_pack<", "k_analyze<", "k_bp_unpack<",
             "k_bp_scan<", "k_bp_scan_pair_sum<", "k_bp_scan_pair_gsum<", "k_bp_scan_pair_cmp<",
             "k_bp_gather<", "k_bp_group_popc")
 
