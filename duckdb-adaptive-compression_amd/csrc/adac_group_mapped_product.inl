@@ -4,8 +4,11 @@
 //   revenue[g] = 100 * SUM(price)[g] - SUM(price * disc)[g] = 100 * d_sums_a[g] - d_sums_ab[g]   (mod 2^64),
 // both sums from ONE scan.  Nothing is decoded to memory, there is no hash table, no materialised code column and no
 // global atomic per row.  Included into adac_kernels.hip inside namespace adac::{anonymous}, after adac_group_mapped.inl,
-// whose plan (mapped_plan: header / walk / staged and slice / direct), slice fill, copies rule's shape and rows per
-// segment are used as they are; no kernel of that file calls into this one or is changed by it.
+// whose plan (mapped_plan: header / walk / staged and slice / direct), slice fill and copies rule (mapped_copies against
+// kMappedProductBins) are used as they are, as are adac_dense_read.inl's rows per segment (dense_key_seg_rows).  The
+// readers are this file's own: that file's walk and staged pair reader have ONE value column, and a walk is never
+// templated over the number of columns (adac_group_rw_walk.inl), so the walk with two staged columns and the staged
+// reader with three are functions of their own here, and their sink's row() takes both values.
 //
 // Semantics: k_group_mapped's with the value replaced by a product.  Each factor is widened to 64 bits by its own
 // column's signedness, the product and the sums are taken mod 2^64 (adac_scan_sum_product's rule); a wanted row inside
@@ -23,7 +26,7 @@
 //            each column's chunk index is clamped against its own last chunk.  Per row t = field_key + delta, the
 //            domain test, va = field_a + frame_a and vb = field_b + frame_b as 64-bit two's-complement numbers, va * vb.
 //   staged   everything else: the whole workgroup, the three columns in double-buffered stages of packed bytes
-//            (mapped_staged_pair with a third column), per_stage from the widest of the three.
+//            (dense_key_staged_pair with a third column), per_stage from the widest of the three.
 //   slice / direct for the look-up: unchanged (mapped_plan).
 //
 // Bins: ngroups x copies entries of {sum_ab, sum_a: 64 bits, count: 32 bits} in LDS, the copy chosen by lane id, so that
@@ -54,14 +57,6 @@ constexpr uint32_t kMappedProductLds = 2u * kCmpLdsChunks * 16u + kMappedSliceWo
 static_assert(kMappedProductBins >= 2u * 256u, "two copies of the most groups");
 static_assert(kMappedProductLds * kMappedProductResident <= 160u * 1024u, "stages + slice + bins: five workgroups per CU");
 static_assert(6u * kCmpStageChunks <= 2u * kCmpLdsChunks, "the staged reader's six buffers fit the walk's block");
-
-// mapped_copies' rule against this kernel's bins (host; the knob group_mapped_copies caps it)
-inline uint32_t mapped_product_copies(uint32_t ngroups, int knob) {
-	uint32_t c = 1;
-	while (c * 2u * ngroups <= kMappedProductBins && c * 2u <= kMappedMaxCopies) c *= 2u;
-	const uint32_t k = mapped_copies(1u, knob); // the knob as a power of two, at most kMappedMaxCopies
-	return c < k ? c : k;
-}
 
 struct MappedProductPlan {
 	MappedPlan m;    // reader (with a as the value column: p.vframe is a's frame), delta, slice
@@ -111,7 +106,7 @@ struct MappedProductBins {
 	}
 };
 
-// Reader "walk": mapped_walk with a second staged column.  Rows [r0, r1) of the segment triple, walked by ONE wave.
+// Reader "walk": dense_key_walk with a second staged column.  Rows [r0, r1) of the segment triple, walked by ONE wave.
 // `rows` gains the lane's wanted rows inside the domain.
 template <int W, bool V, class Sink>
 __device__ __forceinline__ void mapped_product_walk(uint32_t r0, uint32_t r1, const adac_segment_desc &kd,
@@ -149,7 +144,7 @@ __device__ __forceinline__ void mapped_product_walk(uint32_t r0, uint32_t r1, co
 		s0 = (lo * w) >> 7;
 		ns = hi > lo ? ((hi * w + 127u) >> 7) - s0 : 0u;
 	};
-	// (two named chunks per column, not arrays of two: dense_walk records that as an array they went to scratch)
+	// (two named chunks per column, not arrays of two: dense_key_walk records that as an array they went to scratch)
 	auto load_s = [&](const uint4 *__restrict__ seg16, uint32_t s0, uint32_t slast, uint4 &v0, uint4 &v1) {
 		const uint32_t c = s0 + lane; // unconditional, index clamped into the column's own segment
 		v0 = seg16[c < slast ? c : slast];
@@ -215,7 +210,7 @@ struct MappedProductStage {
 	uint32_t kbit0, abit0, bbit0, kchunks, achunks, bchunks, row0, m;
 };
 
-// Reader "staged": mapped_staged_pair with a third column.  Every thread runs every barrier.
+// Reader "staged": dense_key_staged_pair with a third column.  Every thread runs every barrier.
 template <bool V, class Sink>
 __device__ __forceinline__ uint32_t mapped_product_staged(const ScanGroup &g, const adac_segment_desc &ad,
                                                           const adac_segment_desc &bd,
@@ -312,7 +307,7 @@ __device__ __forceinline__ uint32_t mapped_product_staged(const ScanGroup &g, co
 }
 
 // V: a mask is given; A: d_sums_a is wanted.  copies: a power of two with copies * ngroups <= kMappedProductBins
-// (mapped_product_copies).
+// (mapped_copies).
 template <bool V, bool A>
 __global__ __launch_bounds__(kWorkgroup, kMappedProductResident) void k_group_mapped_product(
     const ScanGroup *__restrict__ kgroups, const uint64_t *__restrict__ kwords,
@@ -364,7 +359,7 @@ __global__ __launch_bounds__(kWorkgroup, kMappedProductResident) void k_group_ma
 	} else if (reader == kMemStaged) {
 		rows = mapped_product_staged<V>(g, ad, bd, kwords, awords, bwords, dom, ty, validity, lds, sink);
 	}
-	mapped_seg_rows(seg_rows, g.seg, rows);
+	dense_key_seg_rows(seg_rows, g.seg, rows);
 	// the overflow entry: one reduction per wave
 	const uint64_t osum_ab = wave_sum(sink.osum_ab);
 	const uint64_t osum_a = A ? wave_sum(sink.osum_a) : 0ull;

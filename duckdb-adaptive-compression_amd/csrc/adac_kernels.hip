@@ -1999,7 +1999,7 @@ bool dispatch_int(int v, F &&f) {
 #include "adac_sum_product.inl"
 #include "adac_scan_compare.inl"
 #include "adac_scan_member.inl"
-#include "adac_group_dense.inl"
+#include "adac_group_dense.inl" // includes adac_dense_read.inl after its plan
 #include "adac_group_mapped.inl"
 #include "adac_group_mapped_product.inl"
 #include "adac_group_product.inl"
@@ -2355,7 +2355,7 @@ hipError_t launch_group_mapped(hipStream_t s, const Column &keys, const Column &
 	if (work.nscan_groups == 0) return hipSuccess;
 	const MemberDomain dom = member_domain(keys, key_base, key_span);
 	const TypeWords vt = d_sums ? type_words(values) : TypeWords {0ull, 0ull};
-	const uint32_t copies = mapped_copies(ngroups, g_tuning.group_mapped_copies);
+	const uint32_t copies = mapped_copies(ngroups, kMappedBins, g_tuning.group_mapped_copies);
 	dispatch_flags([&](auto V, auto SUM) {
 		hipLaunchKernelGGL((k_group_mapped<V.value, SUM.value>), dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
 		                   work.d_scan_groups, keys.d_words, SUM.value ? values.d_descs : nullptr,
@@ -2373,7 +2373,7 @@ hipError_t launch_group_mapped_product(hipStream_t s, const Column &keys, const 
 	if (work.nscan_groups == 0) return hipSuccess;
 	const MemberDomain dom = member_domain(keys, key_base, key_span);
 	const ProductTypes ty = product_types(type_words(a), type_words(b));
-	const uint32_t copies = mapped_product_copies(ngroups, g_tuning.group_mapped_copies);
+	const uint32_t copies = mapped_copies(ngroups, kMappedProductBins, g_tuning.group_mapped_copies);
 	dispatch_flags([&](auto V, auto A) {
 		hipLaunchKernelGGL((k_group_mapped_product<V.value, A.value>), dim3((unsigned)work.nscan_groups), dim3(kWorkgroup),
 		                   0, s, work.d_scan_groups, keys.d_words, a.d_descs, a.d_words, b.d_descs, b.d_words, dom, ty,
