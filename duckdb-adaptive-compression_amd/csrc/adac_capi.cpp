@@ -1213,33 +1213,58 @@ extern "C" adac_status adac_scan_count_compare(adac_layout *a, const uint64_t *d
 	return scan_compare(a, d_a_words, b, d_b_words, d_validity, cmp, false, nullptr, d_counts);
 }
 
+// The member scans and the dense-key scans work on a domain [base, base + span - 1] of the key type.  The rule, stated
+// once: 1 <= span <= 2^32, and the domain stays inside the type, i.e. in T's order (bits ^ sign bit) its last value is
+// at most the type's maximum.  Yields the biased domain the launchers take.
+static bool key_domain(const adac_layout *l, uint64_t base, uint64_t span, adac::KeyDomain *dom) {
+	if (span < 1ull || span > (1ull << 32)) return false;
+	const adac::TypeWords t = adac::type_words(*l);
+	if (base > t.tmask || t.tmask - (base ^ t.sbit) < span - 1ull) return false;
+	*dom = {t.tmask, t.sbit, base ^ t.sbit, span};
+	return true;
+}
+
+// 64-bit words of device memory a call reads or writes.  An empty or absent range overlaps nothing.
+struct WordRange {
+	const uint64_t *p;
+	uint64_t n;
+};
+static bool words_overlap(const WordRange &a, const WordRange &b) {
+	return a.p && b.p && a.n && b.n && a.p < b.p + b.n && b.p < a.p + a.n;
+}
+// Does a range of `apart` overlap another of them, or one of `shared`?  (The ranges of `shared` may overlap one another:
+// what a call only reads.)
+template <size_t N, size_t M>
+static bool any_overlap(const WordRange (&apart)[N], const WordRange (&shared)[M]) {
+	for (size_t i = 0; i < N; i++) {
+		for (size_t j = i + 1; j < N; j++) {
+			if (words_overlap(apart[i], apart[j])) return true;
+		}
+		for (const WordRange &r : shared) {
+			if (words_overlap(apart[i], r)) return true;
+		}
+	}
+	return false;
+}
+
 // Member scans: what adac_scan_select_member, adac_scan_count_member (probe) and adac_scan_build_member share.  Checks
 // the arguments, makes sure `l` has its scan groups, clears the outputs and, for the build, the set (groups OR into the
 // words they share).
 enum MemberCall { MEMBER_SELECT, MEMBER_COUNT, MEMBER_BUILD };
 
-static bool words_overlap(const uint64_t *p, uint64_t np, const uint64_t *q, uint64_t nq) {
-	return p && q && np && nq && p < q + nq && q < p + np;
-}
-
 static adac_status scan_member(adac_layout *l, const uint64_t *d_words, const uint64_t *d_validity, uint64_t *d_set,
                                uint64_t set_base, uint64_t set_bits, MemberCall call, uint64_t *d_bitmap,
                                uint64_t *d_counts) {
-	if (!l) return ADAC_ERR_INVALID_ARGUMENT;
-	if (set_bits < 1ull || set_bits > (1ull << 32)) return ADAC_ERR_INVALID_ARGUMENT;
-	// the domain stays inside the type: in T's order (bits ^ sign bit) its last value is at most the type's maximum
-	const adac::TypeWords t = adac::type_words(*l);
-	if (set_base > t.tmask) return ADAC_ERR_INVALID_ARGUMENT;
-	const uint64_t bbase = set_base ^ t.sbit;
-	if (t.tmask - bbase < set_bits - 1ull) return ADAC_ERR_INVALID_ARGUMENT;
+	adac::KeyDomain dom;
+	if (!l || !key_domain(l, set_base, set_bits, &dom)) return ADAC_ERR_INVALID_ARGUMENT;
 	const SelectOutputs out {l->nseg, l->value_span, call == MEMBER_SELECT, d_bitmap, d_counts};
 	if (!out.ok(d_validity) || !d_set) return ADAC_ERR_INVALID_ARGUMENT;
 	if ((l->total_values && !d_words) || !aligned16(d_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	// the set is neither the bitmap (which only a select call has) nor the mask, and overlaps neither; the pointers are
+	// compared too, since an empty range overlaps nothing
 	const uint64_t span_words = (l->value_span + 63) / 64, set_words = (set_bits + 63) / 64;
-	if (call == MEMBER_SELECT && (d_set == d_bitmap || words_overlap(d_set, set_words, d_bitmap, span_words))) {
-		return ADAC_ERR_INVALID_ARGUMENT;
-	}
-	if (d_set == d_validity || words_overlap(d_set, set_words, d_validity, span_words)) return ADAC_ERR_INVALID_ARGUMENT;
+	const WordRange set[] = {{d_set, set_words}}, others[] = {{d_bitmap, span_words}, {d_validity, span_words}};
+	if (d_set == d_bitmap || d_set == d_validity || any_overlap(set, others)) return ADAC_ERR_INVALID_ARGUMENT;
 	if (l->nseg == 0) return ADAC_OK; // no counts, no elements, no rows
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	adac_status st = ensure_scan_groups(l);
@@ -1248,13 +1273,11 @@ static adac_status scan_member(adac_layout *l, const uint64_t *d_words, const ui
 	const adac::Column col = ColumnArg {l, d_words};
 	if (call == MEMBER_BUILD) {
 		ADAC_HIP(hipMemsetAsync(d_set, 0, set_words * sizeof(uint64_t), l->ctx->stream));
-		ADAC_HIP(adac::launch_scan_member_build(l->ctx->stream, col, scan_work(l), d_validity, set_base, set_bits, d_set,
-		                                        d_counts));
+		ADAC_HIP(adac::launch_scan_member_build(l->ctx->stream, col, scan_work(l), d_validity, dom, d_set, d_counts));
 		return ADAC_OK;
 	}
 	if (call == MEMBER_SELECT && !d_bitmap) return ADAC_OK; // no element, so no row
-	ADAC_HIP(adac::launch_scan_member(l->ctx->stream, col, scan_work(l), d_validity, d_set, set_base, set_bits,
-	                                  out.bitmap(), d_counts));
+	ADAC_HIP(adac::launch_scan_member(l->ctx->stream, col, scan_work(l), d_validity, d_set, dom, out.bitmap(), d_counts));
 	return ADAC_OK;
 }
 
@@ -1277,49 +1300,77 @@ extern "C" adac_status adac_scan_build_member(adac_layout *l, const uint64_t *d_
 	return scan_member(l, d_words, d_validity, d_set, set_base, set_bits, MEMBER_BUILD, nullptr, d_counts);
 }
 
-// Grouped SUM / COUNT by a dense key: what adac_scan_group_sum_dense and adac_scan_group_count_dense (values == null:
-// no value column) share.  Checks the arguments, makes sure `keys` has its scan groups and clears the outputs, whose
-// size comes from key_span (a key layout without segments still gets them zeroed).
-static adac_status scan_group_dense(adac_layout *keys, const uint64_t *d_key_words, bool want_sums, adac_layout *values,
-                                    const uint64_t *d_value_words, const uint64_t *d_validity, uint64_t key_base,
-                                    uint64_t key_span, uint64_t *d_sums, uint64_t *d_counts, uint64_t *d_seg_rows) {
-	if (!keys || (want_sums && !values)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (!want_sums) { // one column: the keys stand in for the values, which nothing reads
-		values = keys;
-		d_value_words = d_key_words;
+// Dense-key scans: grouped SUM / COUNT by a dense key or by the code a map gives for it, and the scan that builds such
+// a map.  An output of theirs starts from `words` 64-bit words of the byte `fill` (every run of rows, or workgroup, adds
+// its part; this also writes the keys or groups without rows).  Not given: refused if `required`, else left out.
+struct ClearedOutput {
+	uint64_t *p;
+	uint64_t words;
+	int fill;
+	bool required;
+};
+// The map: one byte per index of the domain, allocated to whole 64-bit words, 8-byte aligned; 1 ... 256 codes are binned.
+static bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+static bool map_ok(const uint8_t *d_map, uint32_t ngroups) {
+	return ngroups >= 1u && ngroups <= 256u && d_map && aligned8(d_map);
+}
+static WordRange map_range(const uint8_t *d_map, uint64_t key_span) {
+	return {reinterpret_cast<const uint64_t *>(d_map), (key_span + 7ull) / 8ull};
+}
+
+// What the dense-key entry points share.  cols: the call's columns, the keys first; map_in: the map where the call
+// reads it (else empty).  Checks the arguments: the columns of one table, the domain, the required outputs, and that no
+// output overlaps another, d_seg_rows, the mask or map_in (those two are only read and may share words).  Then selects
+// the device, makes sure the key layout has its scan groups and clears the outputs and d_seg_rows.  A key layout
+// without segments still gets its outputs cleared, their sizes do not come from it, but has nothing to launch.
+template <size_t N, size_t C>
+static adac_status dense_scan_begin(const ColumnArg (&cols)[N], const uint64_t *d_validity, uint64_t key_base,
+                                    uint64_t key_span, const ClearedOutput (&outs)[C], const WordRange &map_in,
+                                    uint64_t *d_seg_rows, adac::DenseScan *scan, bool *launch) {
+	adac::KeyDomain dom;
+	if (!same_rows(cols) || !key_domain(cols[0].l, key_base, key_span, &dom)) return ADAC_ERR_INVALID_ARGUMENT;
+	adac_layout *keys = cols[0].l;
+	WordRange written[C + 1];
+	for (size_t i = 0; i < C; i++) {
+		if (outs[i].required && !outs[i].p) return ADAC_ERR_INVALID_ARGUMENT;
+		written[i] = {outs[i].p, outs[i].words};
 	}
-	const ColumnArg cols[] = {{keys, d_key_words}, {values, d_value_words}};
-	if (!same_rows(cols)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (key_span < 1ull || key_span > (1ull << 32)) return ADAC_ERR_INVALID_ARGUMENT;
-	// the domain stays inside the type (scan_member's rule)
-	const adac::TypeWords t = adac::type_words(*keys);
-	if (key_base > t.tmask || t.tmask - (key_base ^ t.sbit) < key_span - 1ull) return ADAC_ERR_INVALID_ARGUMENT;
-	if (want_sums ? !d_sums : !d_counts) return ADAC_ERR_INVALID_ARGUMENT;
-	const struct {
-		const uint64_t *p;
-		uint64_t n;
-	} bufs[] = {{want_sums ? d_sums : nullptr, key_span},
-	            {d_counts, key_span},
-	            {d_seg_rows, keys->nseg},
-	            {d_validity, (keys->value_span + 63) / 64}};
-	for (size_t i = 0; i < 4; i++) {
-		for (size_t j = i + 1; j < 4; j++) {
-			if (words_overlap(bufs[i].p, bufs[i].n, bufs[j].p, bufs[j].n)) return ADAC_ERR_INVALID_ARGUMENT;
-		}
-	}
+	written[C] = {d_seg_rows, keys->nseg};
+	const WordRange read[] = {{d_validity, (keys->value_span + 63) / 64}, map_in};
+	if (any_overlap(written, read)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(keys->ctx->device));
 	hipStream_t stream = keys->ctx->stream;
 	if (keys->nseg) {
 		adac_status st = ensure_scan_groups(keys);
 		if (st != ADAC_OK) return st;
 	}
-	// every run of rows adds its part: the outputs start from zero (this also writes the keys without rows)
-	if (want_sums) ADAC_HIP(hipMemsetAsync(d_sums, 0, key_span * sizeof(uint64_t), stream));
-	if (d_counts) ADAC_HIP(hipMemsetAsync(d_counts, 0, key_span * sizeof(uint64_t), stream));
+	for (const ClearedOutput &o : outs) {
+		if (o.p) ADAC_HIP(hipMemsetAsync(o.p, o.fill, o.words * sizeof(uint64_t), stream));
+	}
 	if (d_seg_rows && keys->nseg) ADAC_HIP(hipMemsetAsync(d_seg_rows, 0, keys->nseg * sizeof(uint64_t), stream));
-	if (keys->nseg == 0) return ADAC_OK;
-	ADAC_HIP(adac::launch_group_dense(stream, cols[0], cols[1], scan_work(keys), d_validity, key_base, key_span,
-	                                  want_sums ? d_sums : nullptr, d_counts, d_seg_rows));
+	*scan = {cols[0], scan_work(keys), d_validity, dom, d_seg_rows};
+	*launch = keys->nseg != 0;
+	return ADAC_OK;
+}
+
+// Grouped SUM / COUNT by a dense key (outputs of key_span words) or, `mapped`, by the code looked up through it (ngroups
+// + 1 words): the four entry points below.  A count entry (want_sums false) has no value column and no d_sums.
+static adac_status scan_group_keyed(bool mapped, bool want_sums, ColumnArg keys, ColumnArg values,
+                                    const uint64_t *d_validity, const uint8_t *d_map, uint64_t key_base, uint64_t key_span,
+                                    uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts, uint64_t *d_seg_rows) {
+	if (mapped && !map_ok(d_map, ngroups)) return ADAC_ERR_INVALID_ARGUMENT;
+	// a count entry has one column: the keys stand in for the values, which nothing reads
+	const ColumnArg cols[] = {keys, want_sums ? values : keys};
+	const uint64_t nout = mapped ? (uint64_t)ngroups + 1ull : key_span;
+	const ClearedOutput outs[] = {{d_sums, nout, 0, want_sums}, {d_counts, nout, 0, !want_sums}};
+	adac::MappedScan m {{}, d_map, ngroups};
+	bool launch;
+	adac_status st = dense_scan_begin(cols, d_validity, key_base, key_span, outs,
+	                                  mapped ? map_range(d_map, key_span) : WordRange {}, d_seg_rows, &m.scan, &launch);
+	if (st != ADAC_OK || !launch) return st;
+	hipStream_t stream = keys.l->ctx->stream;
+	ADAC_HIP(mapped ? adac::launch_group_mapped(stream, m, cols[1], d_sums, d_counts)
+	                : adac::launch_group_dense(stream, m.scan, cols[1], d_sums, d_counts));
 	return ADAC_OK;
 }
 
@@ -1327,81 +1378,15 @@ extern "C" adac_status adac_scan_group_sum_dense(adac_layout *keys, const uint64
                                                  const uint64_t *d_value_words, const uint64_t *d_validity,
                                                  uint64_t key_base, uint64_t key_span, uint64_t *d_sums,
                                                  uint64_t *d_counts, uint64_t *d_seg_rows) {
-	return scan_group_dense(keys, d_key_words, true, values, d_value_words, d_validity, key_base, key_span, d_sums, d_counts,
-	                        d_seg_rows);
+	return scan_group_keyed(false, true, {keys, d_key_words}, {values, d_value_words}, d_validity, nullptr, key_base,
+	                        key_span, 0u, d_sums, d_counts, d_seg_rows);
 }
 
 extern "C" adac_status adac_scan_group_count_dense(adac_layout *keys, const uint64_t *d_key_words,
                                                    const uint64_t *d_validity, uint64_t key_base, uint64_t key_span,
                                                    uint64_t *d_counts, uint64_t *d_seg_rows) {
-	return scan_group_dense(keys, d_key_words, false, nullptr, nullptr, d_validity, key_base, key_span, nullptr, d_counts,
-	                        d_seg_rows);
-}
-
-// Grouped SUM / COUNT by a code looked up through a dense key, and the scan that builds the map.  What the three entry
-// points share: the pair rules, the domain (scan_member's rule) and the map's allocation, key_span rounded up to whole
-// 64-bit words, 8-byte aligned.
-static bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
-static bool mapped_domain_ok(adac_layout *keys, uint64_t key_base, uint64_t key_span) {
-	if (key_span < 1ull || key_span > (1ull << 32)) return false;
-	const adac::TypeWords t = adac::type_words(*keys);
-	return key_base <= t.tmask && t.tmask - (key_base ^ t.sbit) >= key_span - 1ull;
-}
-
-struct WordRange {
-	const uint64_t *p;
-	uint64_t n;
-};
-template <size_t N>
-static bool any_overlap(const WordRange (&bufs)[N]) {
-	for (size_t i = 0; i < N; i++) {
-		for (size_t j = i + 1; j < N; j++) {
-			if (words_overlap(bufs[i].p, bufs[i].n, bufs[j].p, bufs[j].n)) return true;
-		}
-	}
-	return false;
-}
-
-// values == null: no value column (the count entry).  Clears the outputs, whose size comes from ngroups (a key layout
-// without segments still gets them zeroed).
-static adac_status scan_group_mapped(adac_layout *keys, const uint64_t *d_key_words, bool want_sums, adac_layout *values,
-                                     const uint64_t *d_value_words, const uint64_t *d_validity, const uint8_t *d_map,
-                                     uint64_t key_base, uint64_t key_span, uint32_t ngroups, uint64_t *d_sums,
-                                     uint64_t *d_counts, uint64_t *d_seg_rows) {
-	if (!keys || (want_sums && !values)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (!want_sums) { // one column: the keys stand in for the values, which nothing reads
-		values = keys;
-		d_value_words = d_key_words;
-	}
-	const ColumnArg cols[] = {{keys, d_key_words}, {values, d_value_words}};
-	if (!same_rows(cols) || !mapped_domain_ok(keys, key_base, key_span)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (ngroups < 1u || ngroups > 256u || !d_map || !aligned8(d_map)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (want_sums ? !d_sums : !d_counts) return ADAC_ERR_INVALID_ARGUMENT;
-	const uint64_t nout = (uint64_t)ngroups + 1ull, map_words = (key_span + 7ull) / 8ull;
-	const WordRange outs[] = {{want_sums ? d_sums : nullptr, nout},
-	                          {d_counts, nout},
-	                          {d_seg_rows, keys->nseg},
-	                          {d_validity, (keys->value_span + 63) / 64}};
-	if (any_overlap(outs)) return ADAC_ERR_INVALID_ARGUMENT;
-	const uint64_t *map_w = reinterpret_cast<const uint64_t *>(d_map);
-	for (size_t i = 0; i < 3; i++) { // the map and an output
-		if (words_overlap(map_w, map_words, outs[i].p, outs[i].n)) return ADAC_ERR_INVALID_ARGUMENT;
-	}
-	ADAC_HIP(hipSetDevice(keys->ctx->device));
-	hipStream_t stream = keys->ctx->stream;
-	if (keys->nseg) {
-		adac_status st = ensure_scan_groups(keys);
-		if (st != ADAC_OK) return st;
-	}
-	// every workgroup adds its part: the outputs start from zero (this also writes the groups without rows)
-	if (want_sums) ADAC_HIP(hipMemsetAsync(d_sums, 0, nout * sizeof(uint64_t), stream));
-	if (d_counts) ADAC_HIP(hipMemsetAsync(d_counts, 0, nout * sizeof(uint64_t), stream));
-	if (d_seg_rows && keys->nseg) ADAC_HIP(hipMemsetAsync(d_seg_rows, 0, keys->nseg * sizeof(uint64_t), stream));
-	if (keys->nseg == 0) return ADAC_OK;
-	ADAC_HIP(adac::launch_group_mapped(stream, cols[0], cols[1], scan_work(keys), d_validity, d_map, key_base, key_span,
-	                                   ngroups, want_sums ? d_sums : nullptr, d_counts, d_seg_rows));
-	return ADAC_OK;
+	return scan_group_keyed(false, false, {keys, d_key_words}, {}, d_validity, nullptr, key_base, key_span, 0u, nullptr,
+	                        d_counts, d_seg_rows);
 }
 
 extern "C" adac_status adac_scan_group_sum_mapped(adac_layout *keys, const uint64_t *d_key_words, adac_layout *values,
@@ -1409,81 +1394,51 @@ extern "C" adac_status adac_scan_group_sum_mapped(adac_layout *keys, const uint6
                                                   const uint8_t *d_map, uint64_t key_base, uint64_t key_span,
                                                   uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts,
                                                   uint64_t *d_seg_rows) {
-	return scan_group_mapped(keys, d_key_words, true, values, d_value_words, d_validity, d_map, key_base, key_span, ngroups,
-	                         d_sums, d_counts, d_seg_rows);
+	return scan_group_keyed(true, true, {keys, d_key_words}, {values, d_value_words}, d_validity, d_map, key_base, key_span,
+	                        ngroups, d_sums, d_counts, d_seg_rows);
 }
 
 extern "C" adac_status adac_scan_group_count_mapped(adac_layout *keys, const uint64_t *d_key_words,
                                                     const uint64_t *d_validity, const uint8_t *d_map, uint64_t key_base,
                                                     uint64_t key_span, uint32_t ngroups, uint64_t *d_counts,
                                                     uint64_t *d_seg_rows) {
-	return scan_group_mapped(keys, d_key_words, false, nullptr, nullptr, d_validity, d_map, key_base, key_span, ngroups,
-	                         nullptr, d_counts, d_seg_rows);
+	return scan_group_keyed(true, false, {keys, d_key_words}, {}, d_validity, d_map, key_base, key_span, ngroups, nullptr,
+	                        d_counts, d_seg_rows);
 }
 
-// SUM(a * b), SUM(a), COUNT(*) through the map: scan_group_mapped's checks applied to three columns and three outputs.
+// SUM(a * b), SUM(a), COUNT(*) through the map
 extern "C" adac_status adac_scan_group_sum_product_mapped(adac_layout *keys, const uint64_t *d_key_words, adac_layout *a,
                                                           const uint64_t *d_a_words, adac_layout *b,
                                                           const uint64_t *d_b_words, const uint64_t *d_validity,
                                                           const uint8_t *d_map, uint64_t key_base, uint64_t key_span,
                                                           uint32_t ngroups, uint64_t *d_sums_ab, uint64_t *d_sums_a,
                                                           uint64_t *d_counts, uint64_t *d_seg_rows) {
-	if (!keys || !a || !b) return ADAC_ERR_INVALID_ARGUMENT;
+	if (!map_ok(d_map, ngroups)) return ADAC_ERR_INVALID_ARGUMENT;
 	const ColumnArg cols[] = {{keys, d_key_words}, {a, d_a_words}, {b, d_b_words}};
-	if (!same_rows(cols) || !mapped_domain_ok(keys, key_base, key_span)) return ADAC_ERR_INVALID_ARGUMENT;
-	if (ngroups < 1u || ngroups > 256u || !d_map || !aligned8(d_map) || !d_sums_ab) return ADAC_ERR_INVALID_ARGUMENT;
-	const uint64_t nout = (uint64_t)ngroups + 1ull, map_words = (key_span + 7ull) / 8ull;
-	const WordRange outs[] = {{d_sums_ab, nout},
-	                          {d_sums_a, nout},
-	                          {d_counts, nout},
-	                          {d_seg_rows, keys->nseg},
-	                          {d_validity, (keys->value_span + 63) / 64}};
-	if (any_overlap(outs)) return ADAC_ERR_INVALID_ARGUMENT;
-	const uint64_t *map_w = reinterpret_cast<const uint64_t *>(d_map);
-	for (size_t i = 0; i < 4; i++) { // the map and an output
-		if (words_overlap(map_w, map_words, outs[i].p, outs[i].n)) return ADAC_ERR_INVALID_ARGUMENT;
-	}
-	ADAC_HIP(hipSetDevice(keys->ctx->device));
-	hipStream_t stream = keys->ctx->stream;
-	if (keys->nseg) {
-		adac_status st = ensure_scan_groups(keys);
-		if (st != ADAC_OK) return st;
-	}
-	// every workgroup adds its part: the outputs start from zero (this also writes the groups without rows)
-	ADAC_HIP(hipMemsetAsync(d_sums_ab, 0, nout * sizeof(uint64_t), stream));
-	if (d_sums_a) ADAC_HIP(hipMemsetAsync(d_sums_a, 0, nout * sizeof(uint64_t), stream));
-	if (d_counts) ADAC_HIP(hipMemsetAsync(d_counts, 0, nout * sizeof(uint64_t), stream));
-	if (d_seg_rows && keys->nseg) ADAC_HIP(hipMemsetAsync(d_seg_rows, 0, keys->nseg * sizeof(uint64_t), stream));
-	if (keys->nseg == 0) return ADAC_OK;
-	ADAC_HIP(adac::launch_group_mapped_product(stream, cols[0], cols[1], cols[2], scan_work(keys), d_validity, d_map,
-	                                           key_base, key_span, ngroups, d_sums_ab, d_sums_a, d_counts, d_seg_rows));
+	const uint64_t nout = (uint64_t)ngroups + 1ull;
+	const ClearedOutput outs[] = {{d_sums_ab, nout, 0, true}, {d_sums_a, nout, 0, false}, {d_counts, nout, 0, false}};
+	adac::MappedScan m {{}, d_map, ngroups};
+	bool launch;
+	adac_status st = dense_scan_begin(cols, d_validity, key_base, key_span, outs, map_range(d_map, key_span), d_seg_rows,
+	                                  &m.scan, &launch);
+	if (st != ADAC_OK || !launch) return st;
+	ADAC_HIP(adac::launch_group_mapped_product(keys->ctx->stream, m, cols[1], cols[2], d_sums_ab, d_sums_a, d_counts));
 	return ADAC_OK;
 }
 
-// The build side: the map is filled with `fill` first, pad included, in stream order; the rows then store their codes.
+// The build side: the map is an output, filled with `fill` first, pad included, in stream order; the rows then store
+// their codes.
 extern "C" adac_status adac_scan_build_map(adac_layout *keys, const uint64_t *d_key_words, adac_layout *codes,
                                            const uint64_t *d_code_words, const uint64_t *d_validity, uint64_t key_base,
                                            uint64_t key_span, uint32_t fill, uint8_t *d_map, uint64_t *d_seg_rows) {
-	if (!keys || !codes) return ADAC_ERR_INVALID_ARGUMENT;
-	const ColumnArg cols[] = {{keys, d_key_words}, {codes, d_code_words}};
-	if (!same_rows(cols) || !mapped_domain_ok(keys, key_base, key_span)) return ADAC_ERR_INVALID_ARGUMENT;
 	if (fill > 255u || !d_map || !aligned8(d_map)) return ADAC_ERR_INVALID_ARGUMENT;
-	const uint64_t map_words = (key_span + 7ull) / 8ull;
-	const WordRange bufs[] = {{reinterpret_cast<const uint64_t *>(d_map), map_words},
-	                          {d_seg_rows, keys->nseg},
-	                          {d_validity, (keys->value_span + 63) / 64}};
-	if (any_overlap(bufs)) return ADAC_ERR_INVALID_ARGUMENT;
-	ADAC_HIP(hipSetDevice(keys->ctx->device));
-	hipStream_t stream = keys->ctx->stream;
-	if (keys->nseg) {
-		adac_status st = ensure_scan_groups(keys);
-		if (st != ADAC_OK) return st;
-	}
-	ADAC_HIP(hipMemsetAsync(d_map, (int)fill, map_words * 8ull, stream));
-	if (d_seg_rows && keys->nseg) ADAC_HIP(hipMemsetAsync(d_seg_rows, 0, keys->nseg * sizeof(uint64_t), stream));
-	if (keys->nseg == 0) return ADAC_OK;
-	ADAC_HIP(adac::launch_build_map(stream, cols[0], cols[1], scan_work(keys), d_validity, key_base, key_span, d_map,
-	                                d_seg_rows));
+	const ColumnArg cols[] = {{keys, d_key_words}, {codes, d_code_words}};
+	const ClearedOutput outs[] = {{reinterpret_cast<uint64_t *>(d_map), (key_span + 7ull) / 8ull, (int)fill, true}};
+	adac::DenseScan scan;
+	bool launch;
+	adac_status st = dense_scan_begin(cols, d_validity, key_base, key_span, outs, WordRange {}, d_seg_rows, &scan, &launch);
+	if (st != ADAC_OK || !launch) return st;
+	ADAC_HIP(adac::launch_build_map(keys->ctx->stream, scan, cols[1], d_map));
 	return ADAC_OK;
 }
 

@@ -163,6 +163,28 @@ inline TypeWords type_words(const C &col) {
 	return {type_mask(col.type_size), type_sign_bit(col.type_size, col.is_signed)};
 }
 
+// The domain [base, base + span - 1] of a member or dense-key scan in the biased form the kernels work in (MemberDomain,
+// adac_scan_member.inl): the key type's words, bits(base) ^ sbit and the span, 1 ... 2^32 with bbase + span - 1 <= tmask.
+// The entry points check that rule and make the domain, once per call.
+struct KeyDomain {
+	uint64_t tmask, sbit, bbase, span;
+};
+// What every dense-key scan takes: the key column, its layout's work items, the selection (may be null), the domain
+// and the rows inside the domain per segment (d_seg_rows, may be null); the caller has cleared every output.
+struct DenseScan {
+	Column keys;
+	ScanWork work;
+	const uint64_t *d_validity;
+	KeyDomain dom;
+	uint64_t *d_seg_rows;
+};
+// ... and the mapped scans with it: one byte per index of the domain, and the codes they bin (1 ... 256)
+struct MappedScan {
+	DenseScan scan;
+	const uint8_t *d_map;
+	uint32_t ngroups;
+};
+
 // type_size in {1,2,4,8}; every launcher returns the hipError_t of the launch.
 hipError_t launch_analyze(hipStream_t s, uint32_t type_size, bool sign_extend, uint64_t null_bits, int rule,
                           const adac_segment_desc *d_descs, const TileRef *d_tiles, uint64_t ntiles,
@@ -216,38 +238,26 @@ hipError_t launch_scan_sum_product(hipStream_t s, const Column &a, const Column 
 // space (adac_scan_compare.inl)
 hipError_t launch_scan_compare(hipStream_t s, const Column &a, const Column &b, const ScanWork &work,
                                const uint64_t *d_validity, uint32_t cmp, uint64_t *d_bitmap, uint64_t *d_counts);
-// rows whose value is a member of the bit set d_set over [set_base, set_base + set_bits - 1], which the caller has checked
-// against the type: d_counts and, unless null, their d_bitmap; and the set built from the wanted rows of a column, with
-// the rows inside the domain in d_counts (adac_scan_member.inl)
+// rows whose value is a member of the bit set d_set over `dom`: d_counts and, unless null, their d_bitmap; and the set built
+// from the wanted rows of a column, with the rows inside the domain in d_counts (adac_scan_member.inl)
 hipError_t launch_scan_member(hipStream_t s, const Column &col, const ScanWork &work, const uint64_t *d_validity,
-                              const uint64_t *d_set, uint64_t set_base, uint64_t set_bits, uint64_t *d_bitmap,
-                              uint64_t *d_counts);
+                              const uint64_t *d_set, const KeyDomain &dom, uint64_t *d_bitmap, uint64_t *d_counts);
 hipError_t launch_scan_member_build(hipStream_t s, const Column &col, const ScanWork &work, const uint64_t *d_validity,
-                                    uint64_t set_base, uint64_t set_bits, uint64_t *d_set, uint64_t *d_counts);
-// SUM(value), COUNT(*) GROUP BY key over the domain [key_base, key_base + key_span - 1], which the caller has checked
-// against the key type: d_sums (null: no value column is read, `values` is not looked at) and d_counts (may be null with
-// d_sums), key_span words each, and the rows inside the domain per segment in d_seg_rows (may be null); `work`: the KEY
-// layout's (adac_group_dense.inl)
-hipError_t launch_group_dense(hipStream_t s, const Column &keys, const Column &values, const ScanWork &work,
-                              const uint64_t *d_validity, uint64_t key_base, uint64_t key_span, uint64_t *d_sums,
-                              uint64_t *d_counts, uint64_t *d_seg_rows);
-// SUM(value), COUNT(*) GROUP BY d_map[key - key_base] (one byte per index of the domain, which the caller has checked
-// against the key type): d_sums (null: no value column is read) and d_counts (may be null with d_sums), ngroups + 1
-// words each, entry [ngroups] for the codes >= ngroups; the rows inside the domain per segment in d_seg_rows (may be
-// null); `work`: the KEY layout's (adac_group_mapped.inl)
-hipError_t launch_group_mapped(hipStream_t s, const Column &keys, const Column &values, const ScanWork &work,
-                               const uint64_t *d_validity, const uint8_t *d_map, uint64_t key_base, uint64_t key_span,
-                               uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts, uint64_t *d_seg_rows);
+                                    const KeyDomain &dom, uint64_t *d_set, uint64_t *d_counts);
+// SUM(value), COUNT(*) GROUP BY key over scan.dom: d_sums (null: no value column is read, `values` is not looked at) and
+// d_counts (may be null with d_sums), dom.span words each (adac_group_dense.inl)
+hipError_t launch_group_dense(hipStream_t s, const DenseScan &scan, const Column &values, uint64_t *d_sums,
+                              uint64_t *d_counts);
+// SUM(value), COUNT(*) GROUP BY d_map[key - key_base]: d_sums (null: no value column is read) and d_counts (may be null
+// with d_sums), ngroups + 1 words each, entry [ngroups] for the codes >= ngroups (adac_group_mapped.inl)
+hipError_t launch_group_mapped(hipStream_t s, const MappedScan &scan, const Column &values, uint64_t *d_sums,
+                               uint64_t *d_counts);
 // SUM(a * b), SUM(a), COUNT(*) GROUP BY d_map[key - key_base]: d_sums_ab, d_sums_a (may be null) and d_counts (may be
-// null), ngroups + 1 words each; everything else as launch_group_mapped (adac_group_mapped_product.inl)
-hipError_t launch_group_mapped_product(hipStream_t s, const Column &keys, const Column &a, const Column &b,
-                                       const ScanWork &work, const uint64_t *d_validity, const uint8_t *d_map,
-                                       uint64_t key_base, uint64_t key_span, uint32_t ngroups, uint64_t *d_sums_ab,
-                                       uint64_t *d_sums_a, uint64_t *d_counts, uint64_t *d_seg_rows);
+// null), ngroups + 1 words each (adac_group_mapped_product.inl)
+hipError_t launch_group_mapped_product(hipStream_t s, const MappedScan &scan, const Column &a, const Column &b,
+                                       uint64_t *d_sums_ab, uint64_t *d_sums_a, uint64_t *d_counts);
 // d_map[key - key_base] = min(code, 255) for every wanted row inside the domain; the caller has filled d_map
-hipError_t launch_build_map(hipStream_t s, const Column &keys, const Column &codes, const ScanWork &work,
-                            const uint64_t *d_validity, uint64_t key_base, uint64_t key_span, uint8_t *d_map,
-                            uint64_t *d_seg_rows);
+hipError_t launch_build_map(hipStream_t s, const DenseScan &scan, const Column &codes, uint8_t *d_map);
 hipError_t launch_encode_1p(hipStream_t s, uint32_t type_size, bool sign_extend, uint64_t null_bits, int rule,
                             int pad_to_byte, adac_segment_desc *d_descs, uint64_t nseg, const void *d_vals,
                             const uint64_t *d_validity, uint64_t *d_minmax, void *d_scan_state, uint64_t *d_words);

@@ -2300,17 +2300,13 @@ hipError_t launch_scan_compare(hipStream_t s, const Column &a, const Column &b, 
 	return hipGetLastError();
 }
 
-// the domain [set_base, set_base + set_bits - 1] of a member scan in the biased form the kernels work in
-static MemberDomain member_domain(const Column &col, uint64_t set_base, uint64_t set_bits) {
-	const TypeWords t = type_words(col);
-	return {t.tmask, t.sbit, set_base ^ t.sbit, set_bits};
-}
+// the only place a MemberDomain is made: the kernels' form of the domain the entry point checked
+static MemberDomain member_domain(const KeyDomain &d) { return {d.tmask, d.sbit, d.bbase, d.span}; }
 
 hipError_t launch_scan_member(hipStream_t s, const Column &col, const ScanWork &work, const uint64_t *d_validity,
-                              const uint64_t *d_set, uint64_t set_base, uint64_t set_bits, uint64_t *d_bitmap,
-                              uint64_t *d_counts) {
+                              const uint64_t *d_set, const KeyDomain &kd, uint64_t *d_bitmap, uint64_t *d_counts) {
 	if (work.nscan_groups == 0) return hipSuccess;
-	const MemberDomain dom = member_domain(col, set_base, set_bits);
+	const MemberDomain dom = member_domain(kd);
 	uint32_t *set32 = reinterpret_cast<uint32_t *>(const_cast<uint64_t *>(d_set)); // the probe only reads it
 	dispatch_flags([&](auto V, auto SEL) {
 		hipLaunchKernelGGL((k_scan_member<V.value, SEL.value>), dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
@@ -2321,9 +2317,9 @@ hipError_t launch_scan_member(hipStream_t s, const Column &col, const ScanWork &
 }
 
 hipError_t launch_scan_member_build(hipStream_t s, const Column &col, const ScanWork &work, const uint64_t *d_validity,
-                                    uint64_t set_base, uint64_t set_bits, uint64_t *d_set, uint64_t *d_counts) {
+                                    const KeyDomain &kd, uint64_t *d_set, uint64_t *d_counts) {
 	if (work.nscan_groups == 0) return hipSuccess;
-	const MemberDomain dom = member_domain(col, set_base, set_bits);
+	const MemberDomain dom = member_domain(kd);
 	dispatch_flags([&](auto V) {
 		hipLaunchKernelGGL(k_scan_member_build<V.value>, dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
 		                   work.d_scan_groups, col.d_words, dom, d_validity, reinterpret_cast<uint32_t *>(d_set),
@@ -2332,69 +2328,70 @@ hipError_t launch_scan_member_build(hipStream_t s, const Column &col, const Scan
 	return hipGetLastError();
 }
 
-hipError_t launch_group_dense(hipStream_t s, const Column &keys, const Column &values, const ScanWork &work,
-                              const uint64_t *d_validity, uint64_t key_base, uint64_t key_span, uint64_t *d_sums,
-                              uint64_t *d_counts, uint64_t *d_seg_rows) {
+hipError_t launch_group_dense(hipStream_t s, const DenseScan &scan, const Column &values, uint64_t *d_sums,
+                              uint64_t *d_counts) {
+	const ScanWork &work = scan.work;
 	if (work.nscan_groups == 0) return hipSuccess;
-	const MemberDomain dom = member_domain(keys, key_base, key_span);
+	const MemberDomain dom = member_domain(scan.dom);
 	const TypeWords vt = d_sums ? type_words(values) : TypeWords {0ull, 0ull};
 	const uint32_t knobs = (g_tuning.group_dense_combine != 0 ? 1u : 0u) | (g_tuning.group_dense_window != 0 ? 2u : 0u);
 	dispatch_flags([&](auto V, auto SUM) {
 		hipLaunchKernelGGL((k_group_dense<V.value, SUM.value>), dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
-		                   work.d_scan_groups, keys.d_words, SUM.value ? values.d_descs : nullptr,
-		                   SUM.value ? values.d_words : nullptr, dom, vt.tmask, vt.sbit, d_validity,
+		                   work.d_scan_groups, scan.keys.d_words, SUM.value ? values.d_descs : nullptr,
+		                   SUM.value ? values.d_words : nullptr, dom, vt.tmask, vt.sbit, scan.d_validity,
 		                   reinterpret_cast<unsigned long long *>(d_sums), reinterpret_cast<unsigned long long *>(d_counts),
-		                   reinterpret_cast<unsigned long long *>(d_seg_rows), knobs);
-	}, d_validity != nullptr, d_sums != nullptr);
+		                   reinterpret_cast<unsigned long long *>(scan.d_seg_rows), knobs);
+	}, scan.d_validity != nullptr, d_sums != nullptr);
 	return hipGetLastError();
 }
 
-hipError_t launch_group_mapped(hipStream_t s, const Column &keys, const Column &values, const ScanWork &work,
-                               const uint64_t *d_validity, const uint8_t *d_map, uint64_t key_base, uint64_t key_span,
-                               uint32_t ngroups, uint64_t *d_sums, uint64_t *d_counts, uint64_t *d_seg_rows) {
+hipError_t launch_group_mapped(hipStream_t s, const MappedScan &m, const Column &values, uint64_t *d_sums,
+                               uint64_t *d_counts) {
+	const DenseScan &scan = m.scan;
+	const ScanWork &work = scan.work;
 	if (work.nscan_groups == 0) return hipSuccess;
-	const MemberDomain dom = member_domain(keys, key_base, key_span);
+	const MemberDomain dom = member_domain(scan.dom);
 	const TypeWords vt = d_sums ? type_words(values) : TypeWords {0ull, 0ull};
-	const uint32_t copies = mapped_copies(ngroups, kMappedBins, g_tuning.group_mapped_copies);
+	const uint32_t copies = mapped_copies(m.ngroups, kMappedBins, g_tuning.group_mapped_copies);
 	dispatch_flags([&](auto V, auto SUM) {
 		hipLaunchKernelGGL((k_group_mapped<V.value, SUM.value>), dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
-		                   work.d_scan_groups, keys.d_words, SUM.value ? values.d_descs : nullptr,
-		                   SUM.value ? values.d_words : nullptr, dom, vt.tmask, vt.sbit, d_validity, d_map, ngroups, copies,
-		                   reinterpret_cast<unsigned long long *>(d_sums), reinterpret_cast<unsigned long long *>(d_counts),
-		                   reinterpret_cast<unsigned long long *>(d_seg_rows));
-	}, d_validity != nullptr, d_sums != nullptr);
+		                   work.d_scan_groups, scan.keys.d_words, SUM.value ? values.d_descs : nullptr,
+		                   SUM.value ? values.d_words : nullptr, dom, vt.tmask, vt.sbit, scan.d_validity, m.d_map, m.ngroups,
+		                   copies, reinterpret_cast<unsigned long long *>(d_sums),
+		                   reinterpret_cast<unsigned long long *>(d_counts),
+		                   reinterpret_cast<unsigned long long *>(scan.d_seg_rows));
+	}, scan.d_validity != nullptr, d_sums != nullptr);
 	return hipGetLastError();
 }
 
-hipError_t launch_group_mapped_product(hipStream_t s, const Column &keys, const Column &a, const Column &b,
-                                       const ScanWork &work, const uint64_t *d_validity, const uint8_t *d_map,
-                                       uint64_t key_base, uint64_t key_span, uint32_t ngroups, uint64_t *d_sums_ab,
-                                       uint64_t *d_sums_a, uint64_t *d_counts, uint64_t *d_seg_rows) {
+hipError_t launch_group_mapped_product(hipStream_t s, const MappedScan &m, const Column &a, const Column &b,
+                                       uint64_t *d_sums_ab, uint64_t *d_sums_a, uint64_t *d_counts) {
+	const DenseScan &scan = m.scan;
+	const ScanWork &work = scan.work;
 	if (work.nscan_groups == 0) return hipSuccess;
-	const MemberDomain dom = member_domain(keys, key_base, key_span);
+	const MemberDomain dom = member_domain(scan.dom);
 	const ProductTypes ty = product_types(type_words(a), type_words(b));
-	const uint32_t copies = mapped_copies(ngroups, kMappedProductBins, g_tuning.group_mapped_copies);
+	const uint32_t copies = mapped_copies(m.ngroups, kMappedProductBins, g_tuning.group_mapped_copies);
 	dispatch_flags([&](auto V, auto A) {
 		hipLaunchKernelGGL((k_group_mapped_product<V.value, A.value>), dim3((unsigned)work.nscan_groups), dim3(kWorkgroup),
-		                   0, s, work.d_scan_groups, keys.d_words, a.d_descs, a.d_words, b.d_descs, b.d_words, dom, ty,
-		                   d_validity, d_map, ngroups, copies, reinterpret_cast<unsigned long long *>(d_sums_ab),
+		                   0, s, work.d_scan_groups, scan.keys.d_words, a.d_descs, a.d_words, b.d_descs, b.d_words, dom, ty,
+		                   scan.d_validity, m.d_map, m.ngroups, copies, reinterpret_cast<unsigned long long *>(d_sums_ab),
 		                   reinterpret_cast<unsigned long long *>(d_sums_a), reinterpret_cast<unsigned long long *>(d_counts),
-		                   reinterpret_cast<unsigned long long *>(d_seg_rows));
-	}, d_validity != nullptr, d_sums_a != nullptr);
+		                   reinterpret_cast<unsigned long long *>(scan.d_seg_rows));
+	}, scan.d_validity != nullptr, d_sums_a != nullptr);
 	return hipGetLastError();
 }
 
-hipError_t launch_build_map(hipStream_t s, const Column &keys, const Column &codes, const ScanWork &work,
-                            const uint64_t *d_validity, uint64_t key_base, uint64_t key_span, uint8_t *d_map,
-                            uint64_t *d_seg_rows) {
+hipError_t launch_build_map(hipStream_t s, const DenseScan &scan, const Column &codes, uint8_t *d_map) {
+	const ScanWork &work = scan.work;
 	if (work.nscan_groups == 0) return hipSuccess;
-	const MemberDomain dom = member_domain(keys, key_base, key_span);
+	const MemberDomain dom = member_domain(scan.dom);
 	const TypeWords ct = type_words(codes);
 	dispatch_flags([&](auto V) {
 		hipLaunchKernelGGL(k_build_map<V.value>, dim3((unsigned)work.nscan_groups), dim3(kWorkgroup), 0, s,
-		                   work.d_scan_groups, keys.d_words, codes.d_descs, codes.d_words, dom, ct.tmask, ct.sbit, d_validity,
-		                   d_map, reinterpret_cast<unsigned long long *>(d_seg_rows));
-	}, d_validity != nullptr);
+		                   work.d_scan_groups, scan.keys.d_words, codes.d_descs, codes.d_words, dom, ct.tmask, ct.sbit,
+		                   scan.d_validity, d_map, reinterpret_cast<unsigned long long *>(scan.d_seg_rows));
+	}, scan.d_validity != nullptr);
 	return hipGetLastError();
 }
 

@@ -472,6 +472,8 @@ def test_argument_errors_write_nothing(adac, gpu_ctx):
     _, _, inside = check_mapped(gpu_ctx, keys, vals, klay, kwords, vlay, vwords, counts, mc.draw_map(rng, span2, ng), base,
                                 span2, ng, what="afterwards")
     assert inside.any()
+    # the largest legal domain: the build over one that ends exactly at the key type's maximum is not refused
+    check_build(gpu_ctx, keys, vals, klay, kwords, vlay, vwords, counts, i32max - 10, 11, 255, what="up to the type's maximum")
     far.close()
     ctx2.close()
 

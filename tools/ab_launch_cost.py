@@ -40,7 +40,7 @@ def binding(name, lib_path):
 
 
 class Calls:
-    """the five entry points on one library: name -> (call, its output buffer, words to compare)"""
+    """the timed entry points on one library: name -> (call, its output buffer, words to compare)"""
 
     def __init__(self, adac):
         self.ctx = ctx = adac.Context(0)
@@ -48,8 +48,8 @@ class Calls:
         counts = np.array([ROWS], dtype=np.uint32)
         self.keep = []
 
-        def col(lo, hi, dtype):
-            v = rng.integers(lo, hi, size=ROWS).astype(dtype)
+        def col(lo, hi, dtype, v=None):
+            v = rng.integers(lo, hi, size=ROWS).astype(dtype) if v is None else v
             lay = adac.Layout(ctx, dtype, counts)
             d_words = ctx.alloc(lay.max_arena_words * 8 + 128).zero()
             d_vals = ctx.upload(v)
@@ -59,7 +59,7 @@ class Calls:
             return lay, d_words, v
 
         (a, wa, _), (b, wb, _), (c, wc, _) = col(900, 105000, np.int32), col(0, 11, np.uint8), col(-3, 9, np.int16)
-        (q, wq, _), (k, wk, _), (d, wd, _) = col(1, 51, np.uint32), col(0, NGROUPS, np.uint8), col(0, 105000, np.int32)
+        (q, wq, qv), (k, wk, _), (d, wd, _) = col(1, 51, np.uint32), col(0, NGROUPS, np.uint8), col(0, 105000, np.int32)
         mask = ctx.upload(rng.integers(0, 2 ** 63, size=ROWS // 64 + 1, dtype=np.uint64))
         member_set = ctx.upload(rng.integers(0, 2 ** 63, size=2, dtype=np.uint64))
         out_q1, out_p3 = ctx.alloc(8 * 7 * (NGROUPS + 1)), ctx.alloc(8 * (NGROUPS + 1))
@@ -72,7 +72,14 @@ class Calls:
         ctx.sync()
         bp_counts = np.array([plan.segment(i)[1] for i in range(plan.nseg)], dtype=np.uint32)
         bp = adac.BitpackingLayout(ctx, v.dtype, np.arange(plan.nseg, dtype=np.uint64) * plan.BLOCK_STRIDE, bp_counts)
-        self.keep += [mask, member_set, d_blocks, bp, plan]
+        # the dense-key scans: q is the key, [1, 50] its domain of 56 map bytes; a key's code is a function of the key,
+        # so that the build stores the same byte whichever row comes last
+        code, wcode, _ = col(0, 0, np.uint8, (qv % NGROUPS).astype(np.uint8))
+        d_map = ctx.upload(rng.integers(0, NGROUPS + 1, size=56).astype(np.uint8))
+        built, seg = ctx.alloc(56), ctx.alloc(8)
+        dn_s, dn_c = ctx.alloc(8 * 50), ctx.alloc(8 * 50)
+        mp_s, mp_c, pm_ab, pm_a, pm_c = (ctx.alloc(8 * (NGROUPS + 1)) for _ in range(5))
+        self.keep += [mask, member_set, d_blocks, bp, plan, d_map]
         self.calls = {
             "adac_scan_group_sum_q1": (lambda: a.scan_group_sum_q1(wa, b, wb, c, wc, q, wq, k, wk, NGROUPS, out_q1, mask),
                                        out_q1, 7 * (NGROUPS + 1)),
@@ -83,6 +90,12 @@ class Calls:
             "adac_scan_select_member": (lambda: b.scan_select_member(wb, member_set, 0, 11, bm, cnt, mask), bm, ROWS // 64),
             "adac_bp_scan_select_between": (lambda: bp.scan_select_between(d_blocks, 100, 2000, bm, cnt, mask),
                                             bm, ROWS // 64),
+            "adac_scan_group_sum_dense": (lambda: q.scan_group_sum_dense(wq, a, wa, 1, 50, dn_s, dn_c, seg, mask), dn_s, 50),
+            "adac_scan_group_sum_mapped": (lambda: q.scan_group_sum_mapped(wq, a, wa, d_map, 1, 50, NGROUPS, mp_s, mp_c,
+                                                                          seg, mask), mp_s, NGROUPS + 1),
+            "adac_scan_group_sum_product_mapped": (lambda: q.scan_group_sum_product_mapped(
+                wq, a, wa, b, wb, d_map, 1, 50, NGROUPS, pm_ab, pm_a, pm_c, seg, mask), pm_ab, NGROUPS + 1),
+            "adac_scan_build_map": (lambda: q.scan_build_map(wq, code, wcode, 1, 50, built, 255, seg, mask), built, 7),
         }
 
     def time(self, name, calls):
