@@ -1,10 +1,20 @@
 """One segment at and past 2^31 / 2^32 bits.
 
-The C ABI does not assume DuckDB's 256 KiB blocks, and five kernels hand over from the width-templated register walk to
-the LDS form at exactly count * w == 2^31 bits (k_scan_agg, k_repack_g, k_analyze_packed_g, the register-walk plan of
-the grouped scan, the product plan); the rest of the family mixes 64-bit bit positions with 32-bit row, chunk and dword
-arithmetic.  The columns here are the smallest that cross those sizes (input bytes ~ packed bytes ~ 256 MiB per 2^31
-bits):
+The C ABI does not assume DuckDB's 256 KiB blocks, and every kernel with a width-templated register walk hands over to
+its staged (LDS) form at exactly count * w == 2^31 bits; everything else about long segments mixes 64-bit bit positions
+with 32-bit row, chunk and dword arithmetic.  The hand-overs, and the file that runs each on such a segment:
+
+  here                              k_scan_agg (SUM, COUNT(range), the selection scan), k_repack_g and
+                                    k_analyze_packed_g (re-encode), the register-walk plan of the grouped scan
+                                    (scan_group_sum), the product plan (scan_sum_product); encode, decode, ranges, jobs,
+                                    row fetches and unpack_selected round the thresholds
+  test_gpu_big_segment_scans.py     scan_group_sum_valid, scan_group_sum_product, scan_group_sum_product3,
+                                    scan_group_sum_q1, the compare scans (compare_plan), the member scans (member_plan),
+                                    the dense-key scans (dense_plan), the mapped scans and the map build (mapped_plan),
+                                    scan_group_sum_product_mapped (mapped_product_plan); big_scan_cases.py holds its
+                                    cells and test_big_scan_census.py states on the CPU what they rely on
+
+The columns here are the smallest that cross those sizes (input bytes ~ packed bytes ~ 256 MiB per 2^31 bits):
 
   u32 / w 31   S0 = floor((2^31 - 1) / 31) rows (count * w < 2^31), S1 = ceil(2^31 / 31) rows (count * w >= 2^31) and a
                small S2 whose word_off lies past 2^26 words = 2^32 bits of arena: both sides of every hand-over
@@ -80,9 +90,8 @@ class Column:
     pass
 
 
-def make_column(name):
+def column_from(name, dtype, spec, big):
     """The values of a column and what an encode must find, by numpy (min / max) alone."""
-    dtype, spec = COLUMNS[name]
     c = Column()
     c.name, c.dtype = name, np.dtype(dtype)
     c.tile = TILE_BYTES // c.dtype.itemsize
@@ -96,8 +105,13 @@ def make_column(name):
     c.segs = [c.vals[o:o + int(n)] for o, n in zip(c.offs, c.counts)]
     # min / max as the append rule orders them: sign-extended to 64 bits
     c.minmax = [(int(v.min()) & U64, int(v.max()) & U64) for v in c.segs]
-    c.big = BIG[name]
+    c.big = big
     return c
+
+
+def make_column(name):
+    dtype, spec = COLUMNS[name]
+    return column_from(name, dtype, spec, BIG[name])
 
 
 def threshold_rows(count, w):
@@ -145,9 +159,8 @@ def memset(adac, ctx, buf, byte):
     assert adac.lib().adac_dev_memset(ctx._h, buf.ptr, byte, buf.nbytes) == 0
 
 
-@pytest.fixture(scope="module", params=list(COLUMNS))
-def column(request, adac, gpu_ctx):
-    c = make_column(request.param)
+def encoded(adac, gpu_ctx, c):
+    """The column on the device: uploaded, encoded, its descriptors read back; freed after the module's last test."""
     assert adac.tile_values(c.dtype) == c.tile
     c.lay = adac.Layout(gpu_ctx, c.dtype, c.counts)
     assert c.lay.value_span == c.n
@@ -160,6 +173,11 @@ def column(request, adac, gpu_ctx):
     c.lay.close()
     c.d_vals.free()
     c.d_words.free()
+
+
+@pytest.fixture(scope="module", params=list(COLUMNS))
+def column(request, adac, gpu_ctx):
+    yield from encoded(adac, gpu_ctx, make_column(request.param))
 
 
 def check_descs(adac, c, descs, mm, widths=None, packed=None):
@@ -467,16 +485,22 @@ def test_reencode_across_the_hand_over(adac, oracle, gpu_ctx, column):
         b.free()
 
 
+def small_keys(n, ngroups):
+    """n uint8 group keys below `ngroups`: a second hash of the row number."""
+    keys = np.empty(n, dtype=np.uint8)
+    for lo in range(0, n, 1 << 22):
+        hi = min(n, lo + (1 << 22))
+        x = np.arange(lo, hi, dtype=np.uint32)
+        x *= np.uint32(0x85EBCA6B)
+        keys[lo:hi] = (x >> np.uint32(16)) % np.uint32(ngroups)
+    return keys
+
+
 @gpu
 @only_u32
 def test_group_sum_across_the_hand_over(adac, gpu_ctx, column):
     c = column
-    keys = np.empty(c.n, dtype=np.uint8)
-    for lo in range(0, c.n, 1 << 22):
-        hi = min(c.n, lo + (1 << 22))
-        x = np.arange(lo, hi, dtype=np.uint32)
-        x *= np.uint32(0x85EBCA6B)
-        keys[lo:hi] = (x >> np.uint32(16)) % np.uint32(6)
+    keys = small_keys(c.n, 6)
     klay = adac.Layout(gpu_ctx, np.uint8, c.counts)
     d_keys = gpu_ctx.upload(keys)
     d_kwords = gpu_ctx.alloc(klay.max_arena_words * 8 + 16).zero()
