@@ -74,13 +74,14 @@ def numpy_dtype(ptype):
 
 
 def kernel_source_sha256():
-    """Hash of EVERY device source of libadacodec (adac_kernels.hip, adac_internal.h and each csrc/*.inl it includes):
+    """Hash of EVERY device source of libadacodec (adac_kernels.hip, adac_internal.h with the two host-only headers it
+    takes device records from, adac_scan_deal.h and adac_tile_cut.h, and each csrc/*.inl it includes):
     a PMC traffic record belongs to the kernels it was measured on, and bench.py attaches one only while this hash
     equals the record's (profiles/summarize.py writes the same hash)."""
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     h = hashlib.sha256()
-    for f in ["adac_kernels.hip", "adac_internal.h"] + sorted(x for x in os.listdir(csrc) if x.endswith(".inl")):
+    for f in ["adac_kernels.hip", "adac_internal.h", "adac_scan_deal.h", "adac_tile_cut.h"] + sorted(x for x in os.listdir(csrc) if x.endswith(".inl")):
         h.update(f.encode())
         with open(os.path.join(csrc, f), "rb") as fh:
             h.update(fh.read())

@@ -9,11 +9,14 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "adac_internal.h"
+#include "adac_owned.h"
 #include "adacodec.h"
 
+using adac::DeviceArray;
 using adac::RangeArgs;
 using adac::TileRef;
 
@@ -31,6 +34,27 @@ static adac_status fail_hip(hipError_t e, const char *what) {
 		hipError_t _e = (expr);                                                                                        \
 		if (_e != hipSuccess) return fail_hip(_e, #expr);                                                              \
 	} while (0)
+
+// The memory calls behind every owner (adac_owned.h), on the current device.
+int adac::owned_alloc(adac::Mem kind, void **p, size_t bytes) {
+	switch (kind) {
+	case adac::Mem::Device: return hipMalloc(p, bytes);
+	case adac::Mem::Pinned: return hipHostMalloc(p, bytes, hipHostMallocDefault);
+	case adac::Mem::Event: return hipEventCreateWithFlags(reinterpret_cast<hipEvent_t *>(p), hipEventDisableTiming);
+	}
+	return hipErrorInvalidValue;
+}
+int adac::owned_free(adac::Mem kind, void *p) {
+	switch (kind) {
+	case adac::Mem::Device: return hipFree(p);
+	case adac::Mem::Pinned: return hipHostFree(p);
+	case adac::Mem::Event: return hipEventDestroy(static_cast<hipEvent_t>(p));
+	}
+	return hipErrorInvalidValue;
+}
+using OwnedEvent = adac::Owned<std::remove_pointer_t<hipEvent_t>, adac::Mem::Event>;
+// what ADAC_HIP takes
+static hipError_t hip_code(int e) { return static_cast<hipError_t>(e); }
 
 struct adac_ctx {
 	int device = 0;
@@ -60,7 +84,7 @@ struct adac_layout {
 	uint64_t null_bits = 0; // NullValue<T>() as the bit pattern of T, zero-extended (null_value.hpp:26-28)
 	uint64_t nseg = 0, ntiles = 0, total_values = 0, value_span = 0, max_arena_words = 0;
 	bool single_pass_ok = true; // every segment fits the single-pass encode kernel's registers
-	void *d_scan_state = nullptr; // its look-back words + ticket (allocated on first use)
+	DeviceArray<uint64_t> d_scan_state; // its look-back words + ticket (allocated on first use)
 	bool dense_values = true; // segments back to back from element 0: no element index between them is unowned
 	bool has_empty_segments = false; // a segment without rows has no scan group: its result is cleared, not stored
 	// the widest segment among the descriptors that last passed through the host (adac_layout_get_descs / _set_descs), 0 =
@@ -68,38 +92,45 @@ struct adac_layout {
 	uint32_t hint_max_width = 0;
 	std::vector<uint32_t> counts;
 	std::vector<uint64_t> val_offs;
-	adac_segment_desc *d_descs = nullptr;
-	TileRef *d_tiles = nullptr;
+	DeviceArray<adac_segment_desc> d_descs;
+	DeviceArray<TileRef> d_tiles;
 	// the decode's own tiles, cut on 128-byte lines of the output (adac_tile_cut.h): adac_unpack walks these, everything
 	// else the segment-relative d_tiles
-	TileRef *d_unpack_tiles = nullptr;
+	DeviceArray<TileRef> d_unpack_tiles;
 	uint64_t n_unpack_tiles = 0;
-	uint64_t *d_minmax = nullptr;
+	DeviceArray<uint64_t> d_minmax; // two words per segment
 	// fused-scan work items (see ScanGroup): built lazily for the current scan_tiles_per_wg, re-expanded when
 	// the descriptors changed
-	adac::ScanGroupRef *d_group_refs = nullptr;
-	adac::ScanGroup *d_groups = nullptr;
+	DeviceArray<adac::ScanGroupRef> d_group_refs;
+	DeviceArray<adac::ScanGroup> d_groups;
 	uint64_t ngroups = 0;
-	int groups_tiles = 0;
+	int groups_tiles = 0; // 0: no table; else the four tables of that deal, complete (ensure_scan_groups)
 	bool groups_dirty = true;
-	adac::TileRec *d_tile_recs = nullptr; // the tiles with their segments' current descriptors folded in (decode side)
+	DeviceArray<adac::TileRec> d_tile_recs; // the tiles with their segments' current descriptors folded in (decode side)
 	bool tile_recs_dirty = true;
 	// the groups of segments at widths 2 and 3, which a scan kernel of their own takes (k_scan_agg<.., NARROW>): the
 	// expansion lists them on the device and their number comes back through a page-locked word; the first scan after
 	// an expansion waits for that copy (it would wait for the same stream work in its own launch anyway)
-	uint32_t *d_narrow_idx = nullptr, *d_narrow_count = nullptr, *h_narrow_count = nullptr;
-	hipEvent_t narrow_ev = nullptr;
+	DeviceArray<uint32_t> d_narrow_idx, d_narrow_count;
+	adac::Owned<uint32_t, adac::Mem::Pinned> h_narrow_count;
+	OwnedEvent narrow_ev;
 	bool narrow_pending = false;
 	// scratch of adac_unpack_selected: selected rows per tile, their exclusive prefix, block totals + grand total
-	uint32_t *d_tile_cnt = nullptr;
-	uint64_t *d_tile_off = nullptr;
-	uint64_t *d_block_tot = nullptr;
-	// arrival cells of the fused scans (ScanGroupRef): zero between calls
-	unsigned long long *d_res_cells = nullptr;
-	uint32_t *d_edge_cells = nullptr;
-	void *d_sel_edges = nullptr;     // shared-word records of the selection scan (two per scan group)
-	uint64_t sel_edges_groups = 0;   // ... sized for this many groups
-	void *d_group_partial = nullptr; // per-workgroup partials of adac_scan_group_sum (allocated on first use)
+	DeviceArray<uint32_t> d_tile_cnt;
+	DeviceArray<uint64_t> d_tile_off;
+	DeviceArray<uint64_t> d_block_tot;
+	// arrival cells of the fused scans (ScanGroupRef), one per segment and one per group: zero between calls
+	struct ResCell {
+		unsigned long long w[adac::kResCellWords];
+	};
+	struct EdgeCell {
+		uint32_t w[adac::kEdgeCellWords];
+	};
+	DeviceArray<ResCell> d_res_cells;
+	DeviceArray<EdgeCell> d_edge_cells;
+	DeviceArray<uint8_t> d_sel_edges; // shared-word records of the selection scan (two per scan group)
+	uint64_t sel_edges_groups = 0;    // ... sized for this many groups
+	DeviceArray<uint8_t> d_group_partial; // per-workgroup partials of adac_scan_group_sum (allocated on first use)
 	uint32_t group_calls = 0;        // ... and how often it ran: its hand-over word alternates between two slots
 };
 
@@ -302,13 +333,11 @@ extern "C" adac_status adac_blocks_write(adac_ctx *ctx, int physical_type, const
 	adac_status st = blocks_jobs(physical_type, descs, block_offs, nseg, jobs, max_units);
 	if (st != ADAC_OK || nseg == 0) return st;
 	ADAC_HIP(hipSetDevice(ctx->device));
-	adac::BlockJob *d_jobs = nullptr;
-	ADAC_HIP(hipMalloc((void **)&d_jobs, nseg * sizeof(adac::BlockJob)));
-	hipError_t e = hipMemcpyAsync(d_jobs, jobs.data(), nseg * sizeof(adac::BlockJob), hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess) e = adac::launch_blocks_write(ctx->stream, d_jobs, nseg, max_units, d_words, d_blocks);
-	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); // the job table is a local: done before it goes
-	(void)hipFree(d_jobs);
-	ADAC_HIP(e);
+	DeviceArray<adac::BlockJob> d_jobs;
+	ADAC_HIP(hip_code(d_jobs.alloc(nseg)));
+	ADAC_HIP(hipMemcpyAsync(d_jobs, jobs.data(), d_jobs.bytes(), hipMemcpyHostToDevice, ctx->stream));
+	ADAC_HIP(adac::launch_blocks_write(ctx->stream, d_jobs, nseg, max_units, d_words, d_blocks));
+	ADAC_HIP(hipStreamSynchronize(ctx->stream)); // the job table is a local: done before it goes
 	return ADAC_OK;
 }
 
@@ -322,19 +351,17 @@ extern "C" adac_status adac_blocks_read(adac_ctx *ctx, int physical_type, const 
 	adac_status st = blocks_jobs(physical_type, descs, block_offs, nseg, jobs, max_units);
 	if (st != ADAC_OK || nseg == 0) return st;
 	ADAC_HIP(hipSetDevice(ctx->device));
-	void *d_scratch = nullptr;
 	const size_t jobs_bytes = nseg * sizeof(adac::BlockJob);
-	ADAC_HIP(hipMalloc(&d_scratch, jobs_bytes + 16));
-	adac::BlockJob *d_jobs = static_cast<adac::BlockJob *>(d_scratch);
-	uint32_t *d_bad = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_scratch) + jobs_bytes);
+	DeviceArray<uint8_t> d_scratch; // the job table, then 16 bytes for the kernel's verdict
+	ADAC_HIP(hip_code(d_scratch.alloc(jobs_bytes + 16)));
+	adac::BlockJob *d_jobs = reinterpret_cast<adac::BlockJob *>(d_scratch.get());
+	uint32_t *d_bad = reinterpret_cast<uint32_t *>(d_scratch + jobs_bytes);
 	uint32_t bad = 0;
-	hipError_t e = hipMemcpyAsync(d_jobs, jobs.data(), jobs_bytes, hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 16, ctx->stream);
-	if (e == hipSuccess) e = adac::launch_blocks_read(ctx->stream, d_jobs, nseg, max_units, d_blocks, d_words, d_bad);
-	if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-	(void)hipFree(d_scratch);
-	ADAC_HIP(e);
+	ADAC_HIP(hipMemcpyAsync(d_jobs, jobs.data(), jobs_bytes, hipMemcpyHostToDevice, ctx->stream));
+	ADAC_HIP(hipMemsetAsync(d_bad, 0, 16, ctx->stream));
+	ADAC_HIP(adac::launch_blocks_read(ctx->stream, d_jobs, nseg, max_units, d_blocks, d_words, d_bad));
+	ADAC_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+	ADAC_HIP(hipStreamSynchronize(ctx->stream)); // the scratch is a local: done before it goes
 	return bad ? ADAC_ERR_INVALID_ARGUMENT : ADAC_OK; // an image whose header is not the one the descriptor was made from
 }
 
@@ -581,18 +608,16 @@ extern "C" adac_status adac_layout_create(adac_ctx *c, int type, const uint32_t 
 		return ADAC_ERR_INVALID_ARGUMENT;
 	}
 	hipError_t e = hipSetDevice(c->device);
-	if (e == hipSuccess) e = hipMalloc((void **)&l->d_descs, (nseg ? nseg : 1) * sizeof(adac_segment_desc));
-	if (e == hipSuccess) e = hipMalloc((void **)&l->d_tiles, (l->ntiles ? l->ntiles : 1) * sizeof(TileRef));
 	if (e == hipSuccess)
-		e = hipMalloc((void **)&l->d_unpack_tiles, (l->n_unpack_tiles ? l->n_unpack_tiles : 1) * sizeof(TileRef));
-	if (e == hipSuccess) e = hipMalloc((void **)&l->d_minmax, (nseg ? nseg : 1) * 2 * sizeof(uint64_t));
+		e = hip_code(adac::alloc_group(l->d_descs, nseg, l->d_tiles, l->ntiles, l->d_unpack_tiles, l->n_unpack_tiles,
+		                               l->d_minmax, 2 * nseg));
 	if (e == hipSuccess && nseg)
-		e = hipMemcpyAsync(l->d_descs, descs.data(), nseg * sizeof(adac_segment_desc), hipMemcpyHostToDevice, c->stream);
+		e = hipMemcpyAsync(l->d_descs, descs.data(), l->d_descs.bytes(), hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess && l->ntiles)
-		e = hipMemcpyAsync(l->d_tiles, tiles.data(), l->ntiles * sizeof(TileRef), hipMemcpyHostToDevice, c->stream);
+		e = hipMemcpyAsync(l->d_tiles, tiles.data(), l->d_tiles.bytes(), hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess && l->n_unpack_tiles)
-		e = hipMemcpyAsync(l->d_unpack_tiles, unpack_tiles.data(), l->n_unpack_tiles * sizeof(TileRef),
-		                   hipMemcpyHostToDevice, c->stream);
+		e = hipMemcpyAsync(l->d_unpack_tiles, unpack_tiles.data(), l->d_unpack_tiles.bytes(), hipMemcpyHostToDevice,
+		                   c->stream);
 	if (e == hipSuccess) e = adac::launch_minmax_init(c->stream, l->d_minmax, nseg);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // descs/tiles are stack-local
 	if (e != hipSuccess) {
@@ -607,27 +632,8 @@ extern "C" adac_status adac_layout_create(adac_ctx *c, int type, const uint32_t 
 extern "C" void adac_layout_destroy(adac_layout *l) {
 	if (!l) return;
 	(void)hipSetDevice(l->ctx->device);
-	if (l->d_descs) (void)hipFree(l->d_descs);
-	if (l->d_tiles) (void)hipFree(l->d_tiles);
-	if (l->d_unpack_tiles) (void)hipFree(l->d_unpack_tiles);
-	if (l->d_minmax) (void)hipFree(l->d_minmax);
-	if (l->d_tile_cnt) (void)hipFree(l->d_tile_cnt);
-	if (l->d_tile_off) (void)hipFree(l->d_tile_off);
-	if (l->d_block_tot) (void)hipFree(l->d_block_tot);
-	if (l->d_group_refs) (void)hipFree(l->d_group_refs);
-	if (l->d_groups) (void)hipFree(l->d_groups);
-	if (l->d_narrow_idx) (void)hipFree(l->d_narrow_idx);
-	if (l->d_narrow_count) (void)hipFree(l->d_narrow_count);
-	if (l->h_narrow_count) (void)hipHostFree(l->h_narrow_count);
-	if (l->narrow_ev) (void)hipEventDestroy(l->narrow_ev);
-	if (l->d_scan_state) (void)hipFree(l->d_scan_state);
-	if (l->d_group_partial) (void)hipFree(l->d_group_partial);
-	if (l->d_sel_edges) (void)hipFree(l->d_sel_edges);
-	if (l->d_tile_recs) (void)hipFree(l->d_tile_recs);
-	if (l->d_res_cells) (void)hipFree(l->d_res_cells);
-	if (l->d_edge_cells) (void)hipFree(l->d_edge_cells);
 	adac_ctx *c = l->ctx;
-	delete l;
+	delete l; // its owners free their buffers: before the stream may go
 	ctx_release(c);
 }
 
@@ -636,7 +642,7 @@ extern "C" uint64_t adac_layout_ntiles(const adac_layout *l) { return l ? l->nti
 extern "C" uint64_t adac_layout_total_values(const adac_layout *l) { return l ? l->total_values : 0; }
 extern "C" uint64_t adac_layout_value_span(const adac_layout *l) { return l ? l->value_span : 0; }
 extern "C" uint64_t adac_layout_max_arena_words(const adac_layout *l) { return l ? l->max_arena_words : 0; }
-extern "C" const adac_segment_desc *adac_layout_device_descs(const adac_layout *l) { return l ? l->d_descs : nullptr; }
+extern "C" const adac_segment_desc *adac_layout_device_descs(const adac_layout *l) { return l ? l->d_descs.get() : nullptr; }
 
 extern "C" adac_status adac_layout_set_descs(adac_layout *l, const adac_segment_desc *descs) {
 	if (!l || (l->nseg && !descs)) return ADAC_ERR_INVALID_ARGUMENT;
@@ -701,7 +707,7 @@ static adac_status expand_groups(adac_layout *l) {
 static adac_status tile_records(adac_layout *l, const adac::TileRec **out) {
 	*out = nullptr;
 	if (!adac::g_tuning.tile_records || l->ntiles == 0) return ADAC_OK;
-	if (!l->d_tile_recs) ADAC_HIP(hipMalloc((void **)&l->d_tile_recs, l->ntiles * sizeof(adac::TileRec)));
+	ADAC_HIP(hip_code(adac::ensure_group(l->d_tile_recs, l->ntiles)));
 	if (l->tile_recs_dirty) {
 		ADAC_HIP(adac::launch_expand_tiles(l->ctx->stream, l->type_size, l->d_descs, l->d_tiles, l->ntiles, l->d_tile_recs));
 		l->tile_recs_dirty = false;
@@ -713,7 +719,7 @@ static adac_status tile_records(adac_layout *l, const adac::TileRec **out) {
 static adac_status descs_changed(adac_layout *l) {
 	l->groups_dirty = true;
 	l->tile_recs_dirty = true;
-	if (l->d_groups && l->groups_tiles > 0) return expand_groups(l);
+	if (l->groups_tiles > 0) return expand_groups(l);
 	return ADAC_OK;
 }
 
@@ -727,7 +733,7 @@ static adac_status scan_group_list(adac_layout *l, adac::ScanGroupList *gl) {
 	}
 	const bool cells = adac::g_tuning.scan_cells != 0;
 	*gl = adac::ScanGroupList {l->d_groups, l->ngroups, l->d_narrow_idx, *l->h_narrow_count,
-	                           cells ? l->d_res_cells : nullptr, cells ? l->d_edge_cells : nullptr};
+	                           cells ? l->d_res_cells.get()->w : nullptr, cells ? l->d_edge_cells.get()->w : nullptr};
 	return ADAC_OK;
 }
 
@@ -808,7 +814,7 @@ extern "C" adac_status adac_encode(adac_layout *l, const void *d_vals, const uin
 		if (rule != ADAC_RULE_APPEND && rule != ADAC_RULE_RECOMPACT) return ADAC_ERR_INVALID_ARGUMENT;
 		if (!aligned16(d_vals) || !aligned16(d_words)) return ADAC_ERR_INVALID_ARGUMENT;
 		ADAC_HIP(hipSetDevice(l->ctx->device));
-		if (!l->d_scan_state) ADAC_HIP(hipMalloc(&l->d_scan_state, adac::encode_1p_state_words(l->nseg) * sizeof(uint64_t)));
+		ADAC_HIP(hip_code(adac::ensure_group(l->d_scan_state, adac::encode_1p_state_words(l->nseg))));
 		ADAC_HIP(adac::launch_encode_1p(l->ctx->stream, l->type_size, l->is_signed, l->null_bits, rule,
 		                                pad_to_byte ? 1 : 0, l->d_descs, l->nseg, d_vals, d_validity, l->d_minmax,
 		                                l->d_scan_state, d_words));
@@ -941,27 +947,20 @@ extern "C" adac_status adac_unpack_jobs(adac_ctx *ctx, int physical_type, const 
 
 struct adac_event {
 	adac_ctx *ctx = nullptr;
-	hipEvent_t ev = nullptr;
+	OwnedEvent ev;
 };
 
 extern "C" adac_status adac_event_record(adac_ctx *ctx, adac_event **out) {
 	if (!ctx || !out) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(ctx->device));
-	hipEvent_t ev = nullptr;
-	ADAC_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-	hipError_t e = hipEventRecord(ev, ctx->stream);
-	if (e != hipSuccess) {
-		(void)hipEventDestroy(ev);
-		return fail_hip(e, "hipEventRecord");
-	}
+	OwnedEvent ev;
+	ADAC_HIP(hip_code(ev.alloc(1)));
+	ADAC_HIP(hipEventRecord(ev, ctx->stream));
 	adac_event *h = new (std::nothrow) adac_event();
-	if (!h) {
-		(void)hipEventDestroy(ev);
-		return ADAC_ERR_OUT_OF_MEMORY;
-	}
+	if (!h) return ADAC_ERR_OUT_OF_MEMORY;
 	ctx_retain(ctx);
 	h->ctx = ctx;
-	h->ev = ev;
+	h->ev = std::move(ev);
 	*out = h;
 	return ADAC_OK;
 }
@@ -976,9 +975,9 @@ extern "C" int adac_event_done(adac_event *ev) { return ev && hipEventQuery(ev->
 
 extern "C" void adac_event_destroy(adac_event *ev) {
 	if (!ev) return;
-	(void)hipEventDestroy(ev->ev);
-	ctx_release(ev->ctx);
+	adac_ctx *c = ev->ctx;
 	delete ev;
+	ctx_release(c);
 }
 
 extern "C" adac_status adac_fetch_rows(adac_layout *l, const uint64_t *d_words, const uint32_t *d_segs,
@@ -993,100 +992,43 @@ extern "C" adac_status adac_fetch_rows(adac_layout *l, const uint64_t *d_words, 
 
 // The scans' work items for the current grouping knob; the expansion kernel runs on the codec stream, so it is
 // ordered after the plan / descriptor upload that made it necessary.
+// A new deal (first use, or the knob changed) goes in three steps: PLAN the groups on the host (adac_scan_deal.h), BUILD
+// their four tables in locals — allocated as one group, cleared, uploaded — and only then COMMIT them to the layout with
+// ngroups and groups_tiles.  A failure on the way leaves the layout with its previous table, complete, or with none.
 static adac_status ensure_scan_groups(adac_layout *l) {
-	// A segment's tiles are dealt EVENLY to ceil(tiles / target) workgroups.  Default target: 12 tiles of u64, 6 of
-	// u32 (~24 K rows), 8 of u16, 4 of u8 (64 K rows): a 16-tile DuckDB segment becomes two to four groups.  Measured (tools/ab_tuning.py,
-	// 400 M rows): a whole 32 767-row segment per workgroup puts the workgroups' packed streams and bitmap regions
-	// at the same power-of-two stride (32 KiB / 4 KiB) and costs 6-25 %; 16-24 K rows is the best of 4 .. 32 tiles
-	const uint32_t tile = adac::tile_values(l->type_size);
-	int per = adac::g_tuning.scan_tiles_per_wg;
-	if (per < 1) { // by type: best of 1 .. 32 tiles in tools/ab_tuning.py (u8 and u16 want more rows per workgroup)
-		per = l->type_size == 8 ? 12 : l->type_size == 4 ? 6 : l->type_size == 2 ? 8 : 4;
-	}
-	if ((uint64_t)per * tile > 65536) per = (int)(65536 / tile); // the selection scan's LDS image holds 64 Ki rows
+	const int per = adac::scan_tiles_per_group(l->type_size, adac::g_tuning.scan_tiles_per_wg);
 	if (l->groups_tiles != per) {
-		std::vector<adac::ScanGroupRef> refs;
-		for (uint64_t s = 0; s < l->nseg; s++) {
-			const uint64_t ntiles = ((uint64_t)l->counts[s] + tile - 1) / tile;
-			if (ntiles == 0) continue;
-			const uint64_t ngroups = (ntiles + (uint64_t)per - 1) / (uint64_t)per;
-			const uint64_t rows_per_group = ((ntiles + ngroups - 1) / ngroups) * tile;
-			const size_t seg_first = refs.size();
-			for (uint64_t first = 0; first < l->counts[s]; first += rows_per_group) {
-				const uint64_t left = l->counts[s] - first;
-				adac::ScanGroupRef r {};
-				r.seg = (uint32_t)s;
-				r.first = (uint32_t)first;
-				r.rows = (uint32_t)(left < rows_per_group ? left : rows_per_group);
-				refs.push_back(r);
-			}
-			for (size_t g = seg_first; g < refs.size(); g++) refs[g].seg_groups = (uint32_t)(refs.size() - seg_first);
-		}
-		if (refs.size() >= 0x7fffffffull) return ADAC_ERR_INVALID_ARGUMENT;
-		if (l->dense_values) {
-			// Bitmap words that groups cover in part (sel_write_out's test: word 0 of a group unless the group starts on a
-			// word boundary and fills it; its last word, if it has more than one, unless it ends on a boundary).  The
-			// groups are in element order, so the arrivals at one word are neighbours in this list: a run of equal words
-			// shares the cell named after its first arrival and expects as many arrivals as the run is long.
-			struct Arrival {
-				uint64_t word;
-				uint32_t group, which;
-			};
-			std::vector<Arrival> arr;
-			for (size_t g = 0; g < refs.size(); g++) {
-				const uint64_t p0 = l->val_offs[refs[g].seg] + refs[g].first, p1 = p0 + refs[g].rows;
-				const uint64_t nwords = ((p1 + 31) >> 5) - (p0 >> 5);
-				if (!((p0 & 31) == 0 && p0 + 32 <= p1)) arr.push_back(Arrival {p0 >> 5, (uint32_t)g, 0u});
-				if (nwords > 1 && (p1 & 31) != 0) arr.push_back(Arrival {(p1 - 1) >> 5, (uint32_t)g, 1u});
-			}
-			for (size_t a = 0; a < arr.size();) {
-				size_t b = a;
-				while (b < arr.size() && arr[b].word == arr[a].word) b++;
-				const uint32_t cell = 2u * arr[a].group + arr[a].which;
-				const uint16_t n = (uint16_t)(b - a); // a word holds 32 rows and every group at least one: n <= 32
-				for (size_t i = a; i < b; i++) {
-					adac::ScanGroupRef &r = refs[arr[i].group];
-					if (arr[i].which == 0) {
-						r.cell_first = cell;
-						r.n_first = n;
-					} else {
-						r.cell_last = cell;
-						r.n_last = n;
-					}
-				}
-				a = b;
-			}
-		}
-		if (refs.size() >= 0x7fffffffull) return ADAC_ERR_INVALID_ARGUMENT;
-		if (l->d_group_refs) (void)hipFree(l->d_group_refs);
-		if (l->d_groups) (void)hipFree(l->d_groups);
-		if (l->d_narrow_idx) (void)hipFree(l->d_narrow_idx);
-		if (l->d_edge_cells) (void)hipFree(l->d_edge_cells);
-		l->d_edge_cells = nullptr;
-		l->d_group_refs = nullptr;
-		l->d_groups = nullptr;
-		l->d_narrow_idx = nullptr;
-		l->ngroups = refs.size();
-		ADAC_HIP(hipMalloc((void **)&l->d_group_refs, (refs.size() ? refs.size() : 1) * sizeof(adac::ScanGroupRef)));
-		ADAC_HIP(hipMalloc((void **)&l->d_groups, (refs.size() ? refs.size() : 1) * sizeof(adac::ScanGroup)));
-		ADAC_HIP(hipMalloc((void **)&l->d_narrow_idx, (refs.size() ? refs.size() : 1) * sizeof(uint32_t)));
-		ADAC_HIP(hipMalloc((void **)&l->d_edge_cells, adac::scan_edge_cell_bytes(refs.size())));
-		ADAC_HIP(hipMemsetAsync(l->d_edge_cells, 0, adac::scan_edge_cell_bytes(refs.size()), l->ctx->stream));
+		const std::vector<adac::ScanGroupRef> refs =
+		    adac::deal_scan_groups(l->type_size, l->counts.data(), l->val_offs.data(), l->nseg, l->dense_values, per);
+		const size_t n = refs.size();
+		if (n >= 0x7fffffffull) return ADAC_ERR_INVALID_ARGUMENT; // grid.x limit
+		hipStream_t stream = l->ctx->stream;
+		DeviceArray<adac::ScanGroupRef> d_refs;
+		DeviceArray<adac::ScanGroup> d_groups;
+		DeviceArray<uint32_t> d_narrow_idx;
+		DeviceArray<adac_layout::EdgeCell> d_edge_cells;
+		ADAC_HIP(hip_code(adac::alloc_group(d_refs, n, d_groups, n, d_narrow_idx, n, d_edge_cells, n)));
+		ADAC_HIP(hipMemsetAsync(d_edge_cells, 0, d_edge_cells.bytes(), stream));
+		// what every deal shares, made on first use: the result cells, and where the narrow groups' count arrives
 		if (!l->d_res_cells) {
-			ADAC_HIP(hipMalloc((void **)&l->d_res_cells, adac::scan_res_cell_bytes(l->nseg)));
-			ADAC_HIP(hipMemsetAsync(l->d_res_cells, 0, adac::scan_res_cell_bytes(l->nseg), l->ctx->stream));
+			DeviceArray<adac_layout::ResCell> cells;
+			ADAC_HIP(hip_code(cells.alloc(l->nseg)));
+			ADAC_HIP(hipMemsetAsync(cells, 0, cells.bytes(), stream));
+			l->d_res_cells = std::move(cells);
 		}
 		if (!l->d_narrow_count) {
-			ADAC_HIP(hipMalloc((void **)&l->d_narrow_count, sizeof(uint32_t)));
-			ADAC_HIP(hipHostMalloc((void **)&l->h_narrow_count, sizeof(uint32_t), hipHostMallocDefault));
-			ADAC_HIP(hipEventCreateWithFlags(&l->narrow_ev, hipEventDisableTiming));
+			ADAC_HIP(hip_code(adac::alloc_group(l->d_narrow_count, 1, l->h_narrow_count, 1, l->narrow_ev, 1)));
 			*l->h_narrow_count = 0;
 		}
-		if (!refs.empty()) {
-			ADAC_HIP(hipMemcpyAsync(l->d_group_refs, refs.data(), refs.size() * sizeof(adac::ScanGroupRef),
-			                        hipMemcpyHostToDevice, l->ctx->stream));
-			ADAC_HIP(hipStreamSynchronize(l->ctx->stream)); // refs is stack-local
+		if (n) {
+			ADAC_HIP(hipMemcpyAsync(d_refs, refs.data(), d_refs.bytes(), hipMemcpyHostToDevice, stream));
+			ADAC_HIP(hipStreamSynchronize(stream)); // refs is stack-local
 		}
+		l->d_group_refs = std::move(d_refs);
+		l->d_groups = std::move(d_groups);
+		l->d_narrow_idx = std::move(d_narrow_idx);
+		l->d_edge_cells = std::move(d_edge_cells);
+		l->ngroups = n;
 		l->groups_tiles = per;
 		l->groups_dirty = true;
 	}
@@ -1465,13 +1407,15 @@ static adac_status group_scan_setup(const ColumnArg (&cols)[N], uint32_t ngroups
 	adac_layout *a = cols[0].l;
 	ADAC_HIP(hipSetDevice(a->ctx->device));
 	if (!a->d_group_partial) {
-		ADAC_HIP(hipMalloc(&a->d_group_partial, adac::group_sum_partial_bytes()));
-		ADAC_HIP(hipMemsetAsync(a->d_group_partial, 0, adac::group_sum_partial_bytes(), a->ctx->stream));
+		DeviceArray<uint8_t> partial;
+		ADAC_HIP(hip_code(partial.alloc(adac::group_sum_partial_bytes())));
+		ADAC_HIP(hipMemsetAsync(partial, 0, partial.bytes(), a->ctx->stream));
+		a->d_group_partial = std::move(partial);
 	}
 	return ensure_scan_groups(a);
 }
 // the state of a's next grouped scan
-static adac::GroupScanState next_group_call(adac_layout *a) { return {a->d_group_partial, a->group_calls++}; }
+static adac::GroupScanState next_group_call(adac_layout *a) { return {a->d_group_partial.get(), a->group_calls++}; }
 
 // ... restricted to the rows whose bit is set in d_validity (the value layout's element space; NULL = every row)
 extern "C" adac_status adac_scan_group_sum_valid(adac_layout *values, const uint64_t *d_value_words, adac_layout *keys,
@@ -1542,7 +1486,7 @@ extern "C" adac_status adac_debug_group_handover(adac_layout *l, uint64_t *left)
 	if (!l->d_group_partial || l->group_calls == 0) return ADAC_OK;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	ADAC_HIP(hipStreamSynchronize(l->ctx->stream));
-	const uint64_t *word = static_cast<const uint64_t *>(l->d_group_partial) + adac::group_sum_handover_word(l->group_calls - 1u);
+	const uint64_t *word = reinterpret_cast<const uint64_t *>(l->d_group_partial.get()) + adac::group_sum_handover_word(l->group_calls - 1u);
 	ADAC_HIP(hipMemcpy(left, word, sizeof(uint64_t), hipMemcpyDeviceToHost));
 	return ADAC_OK;
 }
@@ -1594,15 +1538,12 @@ static adac_status scan_range(adac_layout *l, const uint64_t *d_words, const uin
 	const uint64_t tail_word = (words32 & 1) ? words32 : ~0ull;
 	const bool edge_cells = edges_only && gl.d_edge_cells != nullptr; // shared words finished inside the scan kernel
 	if (edges_only && !edge_cells && l->sel_edges_groups < l->ngroups) {
-		if (l->d_sel_edges) ADAC_HIP(hipFree(l->d_sel_edges));
-		l->d_sel_edges = nullptr;
-		l->sel_edges_groups = 0;
-		ADAC_HIP(hipMalloc(&l->d_sel_edges, adac::sel_edge_bytes(l->ngroups)));
+		ADAC_HIP(hip_code(l->d_sel_edges.alloc(adac::sel_edge_bytes(l->ngroups)))); // the old one stays if this fails
 		l->sel_edges_groups = l->ngroups;
 	}
 	ADAC_HIP(adac::launch_scan_count_range(l->ctx->stream, ColumnArg {l, d_words}, gl, d_validity, blo, bhi - blo,
 	                                       d_counts, want_bitmap ? d_bitmap : nullptr,
-	                                       edges_only && !edge_cells ? l->d_sel_edges : nullptr, edge_cells, tail_word));
+	                                       edges_only && !edge_cells ? l->d_sel_edges.get() : nullptr, edge_cells, tail_word));
 	if (edges_only && !edge_cells) {
 		ADAC_HIP(adac::launch_sel_merge_edges(l->ctx->stream, l->d_sel_edges, l->ngroups, d_bitmap, tail_word));
 	}
@@ -1625,13 +1566,8 @@ extern "C" adac_status adac_unpack_selected(adac_layout *l, const uint64_t *d_wo
 	if (!l || (l->total_values && (!d_words || !d_bitmap || !d_out))) return ADAC_ERR_INVALID_ARGUMENT;
 	if (!aligned16(d_words)) return ADAC_ERR_INVALID_ARGUMENT;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
-	if (!l->d_tile_cnt) {
-		const uint64_t nt = l->ntiles ? l->ntiles : 1;
-		ADAC_HIP(hipMalloc((void **)&l->d_tile_cnt, nt * sizeof(uint32_t)));
-		ADAC_HIP(hipMalloc((void **)&l->d_tile_off, nt * sizeof(uint64_t)));
-		ADAC_HIP(hipMalloc((void **)&l->d_block_tot, ((nt + 1023) / 1024 + 1) * sizeof(uint64_t)));
-	}
 	const uint64_t nblocks = (l->ntiles + 1023) / 1024;
+	ADAC_HIP(hip_code(adac::ensure_group(l->d_tile_cnt, l->ntiles, l->d_tile_off, l->ntiles, l->d_block_tot, nblocks + 1)));
 	uint64_t *d_total = l->d_block_tot + nblocks; // the spare slot after the block totals
 	const adac::TileRec *recs = nullptr;
 	adac_status rst = tile_records(l, &recs);
@@ -1661,15 +1597,15 @@ struct adac_bp_layout {
 	std::vector<uint64_t> seg_first_group; // index of each segment's first metadata group in the group table
 	std::vector<uint64_t> group_out_off;   // of every group: what two layouts must share for a pair scan
 	std::vector<uint32_t> group_rows;
-	void *d_groups = nullptr;
-	uint32_t *d_group_seg = nullptr; // segment of every group (the fused scans' results are per segment)
-	uint64_t *d_block_offs = nullptr;
+	DeviceArray<adac::BpGroupHost> d_groups;
+	DeviceArray<uint32_t> d_group_seg; // segment of every group (the fused scans' results are per segment)
+	DeviceArray<uint64_t> d_block_offs;
 	const void *bound_blocks = nullptr; // blocks buffer whose group headers are parsed into d_groups
 	// scratch of adac_bp_unpack_selected (allocated on first use): selected rows per metadata group, their exclusive
 	// prefix, block totals + grand total
-	uint32_t *d_group_cnt = nullptr;
-	uint64_t *d_group_off = nullptr;
-	uint64_t *d_block_tot = nullptr;
+	DeviceArray<uint32_t> d_group_cnt;
+	DeviceArray<uint64_t> d_group_off;
+	DeviceArray<uint64_t> d_block_tot;
 };
 
 extern "C" adac_status adac_bp_layout_create(adac_ctx *c, int physical_type, const uint64_t *block_offs,
@@ -1713,17 +1649,14 @@ extern "C" adac_status adac_bp_layout_create(adac_ctx *c, int physical_type, con
 		return ADAC_ERR_INVALID_ARGUMENT;
 	}
 	hipError_t e = hipSetDevice(c->device);
-	if (e == hipSuccess) e = hipMalloc(&l->d_groups, (l->ngroups ? l->ngroups : 1) * sizeof(adac::BpGroupHost));
-	if (e == hipSuccess) e = hipMalloc((void **)&l->d_group_seg, (l->ngroups ? l->ngroups : 1) * sizeof(uint32_t));
-	if (e == hipSuccess) e = hipMalloc((void **)&l->d_block_offs, (nseg ? nseg : 1) * sizeof(uint64_t));
+	if (e == hipSuccess)
+		e = hip_code(adac::alloc_group(l->d_groups, l->ngroups, l->d_group_seg, l->ngroups, l->d_block_offs, nseg));
 	if (e == hipSuccess && l->ngroups)
-		e = hipMemcpyAsync(l->d_groups, groups.data(), l->ngroups * sizeof(adac::BpGroupHost), hipMemcpyHostToDevice,
-		                   c->stream);
+		e = hipMemcpyAsync(l->d_groups, groups.data(), l->d_groups.bytes(), hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess && l->ngroups)
-		e = hipMemcpyAsync(l->d_group_seg, group_seg.data(), l->ngroups * sizeof(uint32_t), hipMemcpyHostToDevice,
-		                   c->stream);
+		e = hipMemcpyAsync(l->d_group_seg, group_seg.data(), l->d_group_seg.bytes(), hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess && nseg)
-		e = hipMemcpyAsync(l->d_block_offs, block_offs, nseg * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
+		e = hipMemcpyAsync(l->d_block_offs, block_offs, l->d_block_offs.bytes(), hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
 	if (e != hipSuccess) {
 		adac_status st = fail_hip(e, "adac_bp_layout_create");
@@ -1737,12 +1670,6 @@ extern "C" adac_status adac_bp_layout_create(adac_ctx *c, int physical_type, con
 extern "C" void adac_bp_layout_destroy(adac_bp_layout *l) {
 	if (!l) return;
 	(void)hipSetDevice(l->ctx->device);
-	if (l->d_groups) (void)hipFree(l->d_groups);
-	if (l->d_group_seg) (void)hipFree(l->d_group_seg);
-	if (l->d_block_offs) (void)hipFree(l->d_block_offs);
-	if (l->d_group_cnt) (void)hipFree(l->d_group_cnt);
-	if (l->d_group_off) (void)hipFree(l->d_group_off);
-	if (l->d_block_tot) (void)hipFree(l->d_block_tot);
 	adac_ctx *c = l->ctx;
 	delete l;
 	ctx_release(c);
@@ -1819,9 +1746,7 @@ extern "C" adac_status adac_bp_unpack_selected(adac_bp_layout *l, const void *d_
 	if (st != ADAC_OK) return st;
 	ADAC_HIP(hipSetDevice(l->ctx->device));
 	const uint64_t nblocks = (l->ngroups + 1023) / 1024;
-	if (!l->d_group_cnt) ADAC_HIP(hipMalloc((void **)&l->d_group_cnt, l->ngroups * sizeof(uint32_t)));
-	if (!l->d_group_off) ADAC_HIP(hipMalloc((void **)&l->d_group_off, l->ngroups * sizeof(uint64_t)));
-	if (!l->d_block_tot) ADAC_HIP(hipMalloc((void **)&l->d_block_tot, (nblocks + 1) * sizeof(uint64_t)));
+	ADAC_HIP(hip_code(adac::ensure_group(l->d_group_cnt, l->ngroups, l->d_group_off, l->ngroups, l->d_block_tot, nblocks + 1)));
 	uint64_t *d_total = l->d_block_tot + nblocks; // the spare slot after the block totals
 	ADAC_HIP(adac::launch_bp_gather_selected(l->ctx->stream, bp_column(l, d_blocks), l->ngroups, d_bitmap, l->d_group_cnt,
 	                                         l->d_group_off, l->d_block_tot, d_out, d_out_ids, d_total));
@@ -2064,13 +1989,12 @@ struct adac_bp_plan {
 	};
 	std::vector<Seg> segs;
 	uint64_t by_mode[5] = {0, 0, 0, 0, 0};
-	void *d_recs = nullptr;
+	DeviceArray<adac::BpWriteHost> d_recs;
 };
 
 extern "C" void adac_bp_plan_destroy(adac_bp_plan *p) {
 	if (!p) return;
 	(void)hipSetDevice(p->ctx->device);
-	if (p->d_recs) (void)hipFree(p->d_recs);
 	adac_ctx *c = p->ctx;
 	delete p;
 	ctx_release(c);
@@ -2101,14 +2025,14 @@ extern "C" adac_status adac_bp_plan_create(adac_ctx *c, int physical_type, const
 	const uint64_t t_min = t.sg ? ((~ts_max) & t.mask) : 0ull;
 
 	std::vector<adac::BpStatsHost> stats(p->ngroups);
-	void *d_stats = nullptr;
+	DeviceArray<adac::BpStatsHost> d_stats; // stays null without groups
 	hipError_t e = hipSetDevice(c->device);
-	if (e == hipSuccess && p->ngroups) e = hipMalloc(&d_stats, p->ngroups * sizeof(adac::BpStatsHost));
+	if (e == hipSuccess && p->ngroups) e = hip_code(d_stats.alloc(p->ngroups));
 	if (e == hipSuccess) e = adac::launch_bp_stats(c->stream, p->type_size, p->is_signed, d_vals, d_validity, n, d_stats);
 	if (e == hipSuccess && p->ngroups)
-		e = hipMemcpyAsync(stats.data(), d_stats, p->ngroups * sizeof(adac::BpStatsHost), hipMemcpyDeviceToHost, c->stream);
+		e = hipMemcpyAsync(stats.data(), d_stats, d_stats.bytes(), hipMemcpyDeviceToHost, c->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-	if (d_stats) (void)hipFree(d_stats);
+	d_stats.reset();
 	if (e != hipSuccess) {
 		adac_status st = fail_hip(e, "adac_bp_plan_create");
 		adac_bp_plan_destroy(p);
@@ -2214,10 +2138,8 @@ extern "C" adac_status adac_bp_plan_create(adac_ctx *c, int physical_type, const
 	if (p->encodable) {
 		finish_segment(p->ngroups);
 		if (p->ngroups) {
-			e = hipMalloc(&p->d_recs, p->ngroups * sizeof(adac::BpWriteHost));
-			if (e == hipSuccess)
-				e = hipMemcpyAsync(p->d_recs, recs.data(), p->ngroups * sizeof(adac::BpWriteHost), hipMemcpyHostToDevice,
-				                   c->stream);
+			e = hip_code(p->d_recs.alloc(p->ngroups));
+			if (e == hipSuccess) e = hipMemcpyAsync(p->d_recs, recs.data(), p->d_recs.bytes(), hipMemcpyHostToDevice, c->stream);
 			if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
 			if (e != hipSuccess) {
 				adac_status st2 = fail_hip(e, "adac_bp_plan_create(upload)");

@@ -299,7 +299,10 @@ __global__ __launch_bounds__(kEncThreads) void k_encode_1p(adac_segment_desc *__
 		} else {
 			const uint32_t c = (uint32_t)r * kEncThreads + tid;
 			const int32_t row0 = (int32_t)(c * K) - (int32_t)align;
-			const uint32_t vbits = chunk_validity(validity, (seg_val_off - align) + (uint64_t)c * K);
+			// (a chunk past the segment's last reads that one's mask word and ignores it, as the data loads do: up to 1023
+			// chunks past the end the mask may be unmapped memory)
+			const uint32_t cv = c < nchunks ? c : cur.last_chunk;
+			const uint32_t vbits = chunk_validity(validity, (seg_val_off - align) + (uint64_t)cv * K);
 #pragma unroll
 			for (int j = 0; j < K; j++) {
 				if (c >= nchunks || (uint32_t)(row0 + j) >= n) continue;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "adacodec.h"
+#include "adac_scan_deal.h"
 #include "adac_tile_cut.h"
 
 namespace adac {
@@ -15,6 +16,7 @@ constexpr int kTileBytes = 16384;     // decoded bytes per tile: tile = 16 KiB /
 constexpr uint32_t kNoTile = 0xffffffffu;
 constexpr int kLineBytes = 128;       // one cache line of the output: the decode's tiles are cut on them
 static_assert(kCutTileBytes == (uint32_t)kTileBytes && kCutLineBytes == (uint32_t)kLineBytes, "adac_tile_cut.h");
+static_assert(kDealTileBytes == (uint32_t)kTileBytes, "adac_scan_deal.h");
 
 // TileRef (adac_tile_cut.h): one tile of one segment.  A layout keeps two tables of them: the segment-relative one
 // (`first` a multiple of the type's tile size; analyze, pack, the gather, the scan groups, the expanded records) and the
@@ -35,26 +37,9 @@ struct alignas(32) TileRec {
 };
 static_assert(sizeof(TileRec) == 32, "device record");
 
-// Work item of the fused scans: `ntiles` consecutive tiles of ONE segment starting at row `first` (static per
-// layout and grouping), and its expansion with the segment's current descriptor (rebuilt whenever descriptors
-// change): a scan workgroup then needs ONE 64-byte load before its first data load instead of the dependent
-// chain tile entry -> descriptor.
-// The ARRIVAL fields (round 3) let a scan finish its results inside the one kernel — no clearing pass before it and no
-// merge kernel after it: `seg_groups` groups add into the segment's result cell and the last one to arrive stores the
-// total; a bitmap word that several groups cover in part (dense value spaces only) is ORed into an edge cell by
-// `n_first` / `n_last` groups and stored by the last of them.  Cells are zero between calls (the last arriver resets).
-struct ScanGroupRef {
-	uint32_t seg;
-	uint32_t first;
-	uint32_t rows; // a segment's tiles are dealt evenly to its groups, so group sizes differ between segments
-	uint32_t seg_groups; // scan groups of this segment
-	uint32_t cell_first; // edge cell of the group's first bitmap word when that word is covered in part
-	uint32_t cell_last;  // ... of its last word (groups of more than one word)
-	uint16_t n_first;    // groups that cover the first word in part (0: the word is whole, or the value space has gaps)
-	uint16_t n_last;
-	uint32_t pad;
-};
-static_assert(sizeof(ScanGroupRef) == 32, "device record");
+// ScanGroupRef (adac_scan_deal.h): work item of the fused scans, static per layout and grouping.  ScanGroup is its
+// expansion with the segment's current descriptor (rebuilt whenever descriptors change): a scan workgroup then needs ONE
+// 64-byte load before its first data load instead of the dependent chain tile entry -> descriptor.
 struct alignas(64) ScanGroup {
 	adac_segment_desc d;
 	uint32_t seg;
@@ -278,8 +263,8 @@ struct ScanGroupList {
 	unsigned long long *d_res_cells; // per segment: four words (arrive_sum / arrive_count)
 	uint32_t *d_edge_cells;          // two per group: one 64-bit word each (arrive_or)
 };
-inline uint64_t scan_res_cell_bytes(uint64_t nseg) { return (nseg ? nseg : 1) * 4 * sizeof(unsigned long long); }
-inline uint64_t scan_edge_cell_bytes(uint64_t ngroups) { return (ngroups ? ngroups : 1) * 4 * sizeof(uint32_t); }
+constexpr uint64_t kResCellWords = 4;  // unsigned long long per segment
+constexpr uint64_t kEdgeCellWords = 4; // uint32_t per group
 hipError_t launch_expand_tiles(hipStream_t s, uint32_t type_size, const adac_segment_desc *d_descs, const TileRef *d_tiles,
                                uint64_t ntiles, TileRec *d_recs);
 hipError_t launch_expand_groups(hipStream_t s, const adac_segment_desc *d_descs, const ScanGroupRef *d_refs,

@@ -527,3 +527,48 @@ def test_first_come_placement_every_read(adac, oracle, gpu_ctx, dtype):
                 assert np.array_equal(w_first[a:a + len(e[4])], w_ord[b:b + len(e[4])]), s
     finally:
         set_knobs(adac, DEFAULT_KNOBS)
+
+
+def test_context_handle_goes_first_then_its_objects_in_every_order(adac):
+    """The context handle is destroyed FIRST, then the layout, the BITPACKING layout, the plan and the event made on it,
+    in each of the 24 orders: every object frees its own buffers against the stream that the last of them releases.
+    All four have been used, so their lazily made buffers exist (scan groups, arrival cells, the narrow-count words and
+    event, both gathers' scratch).  A fresh context decodes 1,000 values after every order."""
+    import itertools
+    rows = 1000
+    vals = ((np.arange(rows, dtype=np.int64) * 2654435761) % 4001).astype(np.int32)
+    counts = np.array([rows], dtype=np.uint32)
+    sel = np.arange(1024) % 2 == 0
+    sel[rows:] = False
+    bitmap = np.packbits(sel, bitorder="little").view(np.uint64)
+    for order in itertools.permutations(range(4)):
+        ctx = adac.Context(0)
+        d_vals, d_bitmap = ctx.upload(vals), ctx.upload(bitmap)
+        d_out, d_sum = ctx.alloc(rows * 4 + 16), ctx.alloc(8)
+        lay = adac.Layout(ctx, np.int32, counts)
+        d_words = ctx.alloc(lay.max_arena_words * 8 + 16).zero()
+        lay.encode(d_vals, d_words)
+        lay.scan_sum(d_words, d_sum)
+        assert lay.unpack_selected(d_words, d_bitmap, d_out) == rows // 2
+        assert int(d_sum.download(np.uint64, 1)[0]) == int(vals.sum())
+        plan = adac.BitpackingPlan(ctx, np.int32, d_vals, rows)
+        d_blocks = ctx.alloc(plan.nseg * plan.BLOCK_STRIDE + 64)
+        plan.write(d_vals, d_blocks)
+        bp = adac.BitpackingLayout(ctx, np.int32, np.arange(plan.nseg, dtype=np.uint64) * plan.BLOCK_STRIDE,
+                                   [plan.segment(i)[1] for i in range(plan.nseg)])
+        assert bp.unpack_selected(d_blocks, d_bitmap, d_out) == rows // 2
+        ev = adac.Event(ctx)
+        ev.wait()
+        ctx.close()   # frees the raw buffers; the C context lives on in the four objects
+        objs = [lay, bp, plan, ev]
+        for i in order:
+            objs[i].close()
+        ctx2 = adac.Context(0)
+        lay2 = adac.Layout(ctx2, np.int32, counts)
+        d2, out2 = ctx2.upload(vals), ctx2.alloc(rows * 4 + 16)
+        w2 = ctx2.alloc(lay2.max_arena_words * 8 + 16).zero()
+        lay2.encode(d2, w2)
+        lay2.unpack(w2, out2)
+        assert np.array_equal(out2.download(np.int32, rows), vals), order
+        lay2.close()
+        ctx2.close()

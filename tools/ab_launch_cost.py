@@ -79,8 +79,14 @@ class Calls:
         built, seg = ctx.alloc(56), ctx.alloc(8)
         dn_s, dn_c = ctx.alloc(8 * 50), ctx.alloc(8 * 50)
         mp_s, mp_c, pm_ab, pm_a, pm_c = (ctx.alloc(8 * (NGROUPS + 1)) for _ in range(5))
+        # the cheapest entry points, without a mask: what a change to the host side of every call shows on first
+        sums, range_out, bp_sums = ctx.alloc(8), ctx.alloc(4 * ROWS + 16), ctx.alloc(8 * plan.nseg)
         self.keep += [mask, member_set, d_blocks, bp, plan, d_map]
         self.calls = {
+            "adac_scan_sum": (lambda: a.scan_sum(wa, sums), sums, 1),
+            "adac_scan_count_between": (lambda: a.scan_count_between(wa, 5000, 60000, cnt), cnt, 1),
+            "adac_unpack_range": (lambda: a.unpack_range(wa, 0, 0, ROWS, range_out), range_out, ROWS // 2),
+            "adac_bp_scan_sum": (lambda: bp.scan_sum(d_blocks, bp_sums), bp_sums, plan.nseg),
             "adac_scan_group_sum_q1": (lambda: a.scan_group_sum_q1(wa, b, wb, c, wc, q, wq, k, wk, NGROUPS, out_q1, mask),
                                        out_q1, 7 * (NGROUPS + 1)),
             "adac_scan_group_sum_product3": (lambda: a.scan_group_sum_product3(wa, b, wb, c, wc, k, wk, NGROUPS, out_p3,
@@ -134,11 +140,15 @@ def main():
     ap.add_argument("--calls", type=int, default=4000)
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--burst", type=int, default=32)
+    ap.add_argument("--only", nargs="+", default=None, help="time these entry points only")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     libs = {"parent_1": a.parent[0], "parent_2": a.parent[1], "new": a.new}
     sets = {tag: Calls(binding("adac_" + tag, path)) for tag, path in libs.items()}
-    names = list(sets["new"].calls)
+    unknown = sorted(set(a.only or ()) - set(sets["new"].calls))
+    if unknown:
+        ap.error("--only: not a timed entry point: %s (known: %s)" % (", ".join(unknown), ", ".join(sets["new"].calls)))
+    names = [n for n in sets["new"].calls if a.only is None or n in a.only]
     first = {n: sets["parent_1"].result(n) for n in names}
     for tag, s in sets.items():
         for n in names:
@@ -167,7 +177,8 @@ def main():
 
     cells = {n: dict(cell(us[n]), host_only=cell(host[n])) for n in names}
     table = {"unit": "microseconds of wall time per call: %d back-to-back calls + one sync, median of %d rounds, "
-                     "libraries alternating in one process; one segment of %d rows, every call under a mask; "
+                     "libraries alternating in one process; one segment of %d rows, a mask wherever the call takes "
+                     "one (not adac_scan_sum, _scan_count_between, _unpack_range, _bp_scan_sum); "
                      "outputs equal between the libraries.  host_only: the same per call over bursts of %d calls "
                      "enqueued on an idle stream, the sync not timed" % (a.calls, a.rounds, ROWS, a.burst),
              "libs": libs, "cells": cells}
